@@ -5,7 +5,11 @@ A "step" = one pass of the binarize path (Binarizer + VideoToDigital bit-cell ex
 over one batch of synthetic NTSC frames that is already resident in HBM (workload = BASELINE.json
 configs[1]: 10k-frame synthetic STC-007 NTSC batch, 1 x MI355X, binarize + bit-extract + CRC only).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full [--details FILE]]
+  A plain run sets up, warms up, times the K steps and prints the headline line (with its roofline).  --full adds every other
+  leg (stitch, PAL, damaged tapes, PCM-1, PCM-16x0, audio, configs[4], the sharded whole path) and the CPU baselines.
+  --dump-outputs DIR: what the last timed step returned (line records and frame statistics, fixed samples of large batches), field by
+  field as DIR/<name>.npy in float64, so that two builds can be compared output for output.
   N > 1: launched by torch.distributed.run, one rank per GPU; ONE tape of N x `--frames` frames per step is sharded
   over the ranks in contiguous frame ranges (weak scaling: per-GPU work fixed).  The only collective is the all-gather
   (RCCL) of every rank's 120-byte final chain state per step, against which each rank checks the state it started its
@@ -13,7 +17,7 @@ configs[1]: 10k-frame synthetic STC-007 NTSC batch, 1 x MI355X, binarize + bit-e
   ONE JSON line.
 
 Extra objects in the JSON line: "roofline" (HBM: algorithmic bytes per launch / HIP-event kernel time,
-measured live on the stream the kernel runs on) and "cpu_baseline" (the real reference, or the oracle
+measured live on the stream the kernel runs on) and, with --full, "cpu_baseline" (the real reference, or the oracle
 port when the reference build is not loadable, timed on this host on a bounded sample)."""
 import argparse
 import json
@@ -238,6 +242,33 @@ def cpu_baseline_all_cores(luma_sample, mode, single_core_frames_per_s=None):
         shutil.rmtree(d, ignore_errors=True)
 
 
+DUMP_RECORDS = 1 << 16          # line records in the sample --dump-outputs writes, over all ranks (30 float64 values each: 16 MB)
+DUMP_FRAMES = 1 << 16           # frame statistics in it, over all ranks (15 float64 values each: 8 MB)
+
+
+def dump_outputs(out_dir, last, world=1, rank=0):
+    """--dump-outputs: what the last timed step returned, (lines, stats) of sdv_binarize_frames, field by field as float64 .npy files.
+    Both are fixed samples when there are more of them than DUMP_RECORDS / DUMP_FRAMES (seeded, sorted indices, kept in lines_record_index.npy and
+    stats_frame_index.npy); up to those counts every record and every frame is written."""
+    import numpy as np
+    import torch
+    from sdvpcmdecoder_amd import LINE_DTYPE, STATS_DTYPE
+    lines, stats = last
+    os.makedirs(out_dir, exist_ok=True)
+    def sample(rows, k, seed):
+        n_ = rows.shape[0]
+        return np.arange(n_) if n_ <= k else np.sort(np.random.default_rng(seed).choice(n_, k, replace=False))
+    idx = sample(lines, DUMP_RECORDS // world, rank)
+    fidx = sample(stats, DUMP_FRAMES // world, 1000 + rank)
+    recs = lines[torch.from_numpy(idx).to(lines.device)].cpu().numpy().view(LINE_DTYPE).reshape(-1)
+    st = stats[torch.from_numpy(fidx).to(stats.device)].cpu().numpy().view(STATS_DTYPE).reshape(-1)
+    arrays = {"lines_record_index": idx, "stats_frame_index": fidx}
+    arrays.update(("lines_" + f, recs[f]) for f in LINE_DTYPE.names)
+    arrays.update(("stats_" + f, st[f]) for f in STATS_DTYPE.names if not f.startswith("_"))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ("" if world == 1 else "_rank%d" % rank) + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     if len(sys.argv) >= 6 and sys.argv[1] == "--cpu-worker":
         cpu_worker(sys.argv[2], int(sys.argv[3]), sys.argv[4], sys.argv[5])
@@ -254,7 +285,14 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-stitch", action="store_true", help="skip the extra stitch-stage measurement")
     ap.add_argument("--configs4-frames", type=int, default=100000, help="length of the one tape of BASELINE configs[4] (sharded over the ranks: strong scaling); 0 = skip that leg")
+    ap.add_argument("--full", action="store_true", help="every other leg and the CPU baselines besides the headline (a plain run times the headline only)")
+    ap.add_argument("--details", metavar="FILE", help="with --full: write the full objects of every leg to FILE as well as to stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.details and not args.full:
+        ap.error("--details needs --full (a plain run has no other legs to detail)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves - as fresh child processes, before this process
@@ -317,12 +355,12 @@ def main():
         loop = ShardedBinarizeLoop(eng, rank, world, torch_all_gather(dev if backend == "nccl" else None))
 
         def decode_batch(first_frame_no, new_file, out):
-            loop.step(luma, first_frame_no + rank * n, new_file=new_file, out_lines=out, out_stats=out_stats, stream=stream)
+            return loop.step(luma, first_frame_no + rank * n, new_file=new_file, out_lines=out, out_stats=out_stats, stream=stream)
     else:
         loop = None
 
         def decode_batch(first_frame_no, new_file, out):
-            eng.binarize_frames(luma, first_frame_no=first_frame_no, new_file=new_file, out_lines=out, out_stats=out_stats, stream=stream)
+            return eng.binarize_frames(luma, first_frame_no=first_frame_no, new_file=new_file, out_lines=out, out_stats=out_stats, stream=stream)
 
     # first pass: start of the stream (cold chain: NEW_FILE, first frame decoded alone)
     decode_batch(1, True, out_lines if rank == 0 else out_lines[1:])
@@ -340,7 +378,7 @@ def main():
     general = 0             # frames that needed the full kernel (0 on a tape in steady state)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        decode_batch(tape_pos, False, out_lines[1:])
+        last = decode_batch(tape_pos, False, out_lines[1:])
         tape_pos += n * world
         info = eng.run_info()
         kernel_ms += info.kernel_ms
@@ -355,11 +393,13 @@ def main():
         dt = float(t.item())
     # what the timed steps left (looked at below; the legs that follow decode other tapes into the same buffer)
     timed_host = out_lines[1:1 + 8 * (H + 3)].cpu().numpy().view(LINE_DTYPE).reshape(8, H + 3).copy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, world, rank)
 
     # N > 1, beyond BASELINE's metric: the whole path frames -> PCMSamplePair for ONE tape sharded over the ranks (ShardedDecoder: warm-up,
     # all-gather of the two workers' hand-over states, verify, repair - DESIGN.md section 7), NEW_FILE .. END_FILE, timed as one job
     sharded_full = None
-    if use_dist and not args.no_stitch:
+    if args.full and use_dist and not args.no_stitch:
         try:
             from sdvpcmdecoder_amd.sharded import ShardedDecoder
             ns = n                                              # frames per rank of this leg: as many as in the timed loop
@@ -409,7 +449,7 @@ def main():
     # every N (at N = 1 through the same code, the "all-gather" being the rank's own bytes when no process group exists), so that the driver's
     # 1/2/4/8 runs give the curve north_star asks for.  Reported as absolute frames/s and as a fraction of the HBM roofline on SURVEY 8d's bytes.
     configs4 = None
-    if args.configs4_frames > 0 and not args.no_stitch:
+    if args.full and args.configs4_frames > 0 and not args.no_stitch:
         try:
             from sdvpcmdecoder_amd.sharded import ShardedDecoder
             total = args.configs4_frames
@@ -462,7 +502,7 @@ def main():
     # beyond BASELINE's metric: the stitch stage (STC007DataStitcher -> PCMSamplePair) over the records just produced, and the
     # whole path frames -> PCM, both as a continuing stream (every step continues the tape, like the binarize steps above)
     stitch = None
-    if not args.no_stitch and world == 1:
+    if args.full and not args.no_stitch and world == 1:
         eng.reset_stitcher()
         lines_all = out_lines[:1 + nrec]                                  # NEW_FILE line + n frames
         sp = torch.empty((n * 1470 + 65536, 12), dtype=torch.uint8, device=dev)
@@ -538,7 +578,7 @@ def main():
     # BASELINE configs[2]: STC-007 PAL 720x576, Deinterleaver + P/Q error correction on - a clean tape, and the tape of SURVEY 8d C3 (every 97th
     # line of a frame lost, a bit cell inverted on one line in 53: P and Q corrections, BROKEN blocks, seam masking at work)
     pal = None
-    if not args.no_stitch and world == 1:
+    if args.full and not args.no_stitch and world == 1:
         HP = 576
         PAL_BYTES = W * HP + HP * 32 + 1764 * 8         # 414 720 + 18 432 + 14 112 = 447 264 B per PAL frame
         npal = n
@@ -616,7 +656,7 @@ def main():
     # damaged tapes in the binarize stage (the speculation across frames has to repair what it predicted wrong): 16 lost lines and 16 jumps of
     # the data window per 10 000 frames - the workloads of tools/dropout_probe.py / tools/jump_probe.py, on the tape `value` was measured on
     damaged = None
-    if not args.no_stitch and world == 1:
+    if args.full and not args.no_stitch and world == 1:
         damaged = {"note": "sdv_binarize_frames over the benchmark's tape with damage (16 lost lines / 16 jumps of the data window per 10 000 frames; the whole tape two pixels beside its coordinates; "
                            "every 97th row of every frame lost), continuing stream, wall clock per batch; rounds = launches of the frame kernels "
                            "until every frame was decoded from its predecessor's real state; frames_launched counts re-decodes; frames_by_full_kernel those that "
@@ -670,7 +710,7 @@ def main():
 
     # the other format branch built so far: the PCM-1 back half (PCM1DataStitcher -> PCMSamplePair) over a tape of the same length
     pcm1 = None
-    if not args.no_stitch and world == 1:
+    if args.full and not args.no_stitch and world == 1:
         from sdvpcmdecoder_amd import synth as _synth
         p1_recs = _synth.pcm1_tape(n)
         p1_dev = torch.from_numpy(p1_recs.view(np.uint8).reshape(len(p1_recs), 32)).to(dev)
@@ -693,7 +733,7 @@ def main():
 
     # ... the PCM-16x0 back half (PCM16X0DataStitcher): sub-line records -> sample pairs, both interleave formats
     pcm16 = None
-    if not args.no_stitch and world == 1:
+    if args.full and not args.no_stitch and world == 1:
         from sdvpcmdecoder_amd import synth as _synth
         pcm16 = {"note": "PCM-1630 frames (1470 sub-line records each, damaged tape with rows lost at the top and bottom of the fields) -> trim, "
                          "field split, padding detection by P-code checks over every candidate padding, deinterleave + P-code correction to "
@@ -725,7 +765,7 @@ def main():
     # the consumer of every PCMSamplePair stream: AudioProcessor (dropout masking) on the pair stream of a tape of the same length,
     # in three states of wear; the output of each is packed to WAV bytes (SamplesToWAV, 8f-2)
     audio = None
-    if not args.no_stitch and world == 1:
+    if args.full and not args.no_stitch and world == 1:
         import audio_api as _A
         audio = {"note": "PCMSamplePair stream of n frames (1470 pairs each, NEW_FILE .. END_FILE) -> AudioProcessor window automaton in linear-interpolation "
                          "mode (sdv_audio_process) -> 16-bit stereo PCM of the WAV file (sdv_wav_pack); wall clock per tape incl. the host round trips; "
@@ -769,7 +809,7 @@ def main():
     # ... and its front half: video lines -> PCM1Line records (sdv_pcm1_binarize_lines), a tape that plays (every line preset from a
     # decoded neighbour) and the cold case (nothing preset: the marker-less coordinate search on every line)
     pcm1f = None
-    if not args.no_stitch and world == 1:
+    if args.full and not args.no_stitch and world == 1:
         from sdvpcmdecoder_amd import synth as _synth
         LPF = 490
         f_frames = min(n, 2000)
@@ -817,7 +857,7 @@ def main():
     # ... and the frame drivers of the two marker-less formats (VideoToDigital::doBinarize with TYPE_PCM1 / TYPE_PCM16X0): whole frames in,
     # line records out, with the reference's per-frame coordinate prescan - BASELINE configs[3], the format dispatch
     fmt_stages = {}
-    if not args.no_stitch and world == 1:
+    if args.full and not args.no_stitch and world == 1:
         from sdvpcmdecoder_amd import synth as _synth
         nf = min(n, 10000)         # BASELINE's batch (the frame kernels want more frames than the GPU has SIMDs: 2 000 frames leave half of them idle)
         for key, gen, call, rec_bytes, per_frame in (("pcm1_frames_stage", _synth.pcm1_frames, eng.pcm1_binarize_frames, 40, H + 3),
@@ -886,7 +926,7 @@ def main():
             out["sharded_full_path"] = sharded_full
         if configs4 is not None:
             out["configs4_strong"] = configs4
-        if world == 1 and not args.no_stitch:
+        if args.full and world == 1 and not args.no_stitch:
             # the boundary takes device pointers; a caller that keeps its frames in host memory pays this on top (never part of `value`)
             try:
                 hb = torch.empty(256 << 20, dtype=torch.uint8).pin_memory()
@@ -974,7 +1014,7 @@ def main():
                     pal[tape_name]["cpu_baseline"] = {"error": repr(ex)}
         for key, (stage, _b, _f) in fmt_stages.items():
             out[key] = stage
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             # the frame drivers of PCM-1 / PCM-16x0 on the CPU: the real reference's worker (or the oracle port) on the first eight frames
             import libs as _libs
             for key, (stage, base2, first) in fmt_stages.items():
@@ -991,7 +1031,7 @@ def main():
                 stage["cpu_baseline"] = {"value": len(base2) / dtc, "unit": "frames/s", "cores": 1, "kind": "reference" if use_ref else "port",
                                          "sample": f"the first {len(base2)} frames of the tape, {dtc:.2f} s of CPU work",
                                          "bit_exact_vs_gpu_on_overlap": bool(cr.tobytes()[:first.nbytes] == first.tobytes())}
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             ncpu = min(args.cpu_frames, n)
             sample = luma[:ncpu].cpu().numpy()
             cb, cpu_recs = cpu_baseline(sample, args.mode)
@@ -1072,8 +1112,8 @@ def main():
                                          "bit_exact_vs_gpu_on_overlap": bool(cw.tobytes() == wgot.view(pfa.BIN1_DTYPE).tobytes()
                                                                              and cc.tobytes() == cgot.view(pfa.BIN1_DTYPE).tobytes())}
         # The driver keeps the tail of what this prints: the line of BASELINE's metric goes LAST and stays short - the headline, its roofline and CPU
-        # baseline, and the other legs as plain numbers; everything else (the full objects of every leg) goes to stderr and, where the directory can be
-        # made, to gpurun_out/bench_details.json.
+        # baseline, and the other legs as plain numbers; with --full everything else (the full objects of every leg) goes to stderr and, when
+        # --details names a file, to that file.
         def pick(d, *path):
             for k_ in path:
                 if not isinstance(d, dict) or k_ not in d:
@@ -1107,16 +1147,14 @@ def main():
         short = {k_: out[k_] for k_ in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
                                         "config", "roofline", "cpu_baseline") if k_ in out}
         short["roofline"] = {k_: v_ for k_, v_ in out["roofline"].items() if k_ not in ("traffic_unit", "traffic_from_committed_profile")}
-        short["summary"] = {k_: v_ for k_, v_ in summary.items() if v_ is not None}
-        short["details"] = "the full objects of every leg: stderr of this run, gpurun_out/bench_details.json"
-        full = json.dumps(out)
-        try:
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            with open(os.path.join(ROOT, "gpurun_out", "bench_details.json"), "w") as fh:
-                fh.write(full + "\n")
-        except OSError:
-            pass
-        print(full, file=sys.stderr, flush=True)
+        if args.full:
+            short["summary"] = {k_: v_ for k_, v_ in summary.items() if v_ is not None}
+            short["details"] = "the full objects of every leg: stderr of this run" + (", " + args.details if args.details else "")
+            full = json.dumps(out)
+            if args.details:
+                with open(args.details, "w") as fh:
+                    fh.write(full + "\n")
+            print(full, file=sys.stderr, flush=True)
         print(json.dumps(short), flush=True)
     if use_dist:
         dist.destroy_process_group()

@@ -37,7 +37,7 @@ rows = [
     ("frames → pairs, fused (`sdv_decode_frames`)", f"{g('end_to_end', 'fused_entry_ms_per_step'):.3f} ms = {10000 / g('end_to_end', 'fused_entry_ms_per_step') / 1e3:.2f} M frames/s, {g('end_to_end', 'roofline', 'frac'):.2f} of peak on 377 232 B per frame; the two entry points one after the other: {g('end_to_end', 'two_calls_ms_per_step'):.3f} ms", "what the fused entry saves: §6, stitch stage"),
 ]
 if c4:
-    rows.append(("**configs[4]**: one 100 000-frame stream, NEW_FILE … END_FILE, frames → pairs (`ShardedDecoder`, strong scaling)", f"{c4['ms']:.2f} ms = {c4['frames_per_s'] / 1e6:.2f} M frames/s at {c4['ranks']} rank, {c4['roofline']['frac']:.2f} of peak on 377 232 B per frame", "the same leg runs at every N (`bench.py --gpus N`): the tape is cut into N frame ranges, one all-gather of the hand-over states"))
+    rows.append(("**configs[4]**: one 100 000-frame stream, NEW_FILE … END_FILE, frames → pairs (`ShardedDecoder`, strong scaling)", f"{c4['ms']:.2f} ms = {c4['frames_per_s'] / 1e6:.2f} M frames/s at {c4['ranks']} rank, {c4['roofline']['frac']:.2f} of peak on 377 232 B per frame", "the same leg runs at every N with `--full` (`bench.py --gpus N --full`): the tape is cut into N frame ranges, one all-gather of the hand-over states"))
 rows += [
     ("stitch stage alone", f"{g('stitch_stage', 'stitch_ms_per_step'):.3f} ms ({g('stitch_stage', 'stitch_device_ms_per_step'):.3f} ms on the device)", f"CPU: {g('stitch_stage', 'cpu_baseline', 'value'):.0f} frames/s"),
     ("PAL (configs[2]) clean, binarize + stitch", f"{pal['clean']['ms_per_step']:.2f} ms = {pal['clean']['frames_per_s'] / 1e6:.2f} M frames/s for the two entry points one after the other" + (f"; fused entry {pal['clean']['fused_entry_ms_per_step']:.2f} ms = {pal['clean']['frames_per_step'] / pal['clean']['fused_entry_ms_per_step'] / 1e3:.2f} M frames/s" if pal['clean'].get('fused_entry_ms_per_step') else ""), f"{pal['clean']['frames_per_step']} frames of 720 x 576 per step"),

@@ -3,16 +3,17 @@
 # Results land in gpurun_out/ (copied to profiles/ by hand when they are the ones to keep).
 cd $GRAFT_REPO_ROOT
 R=$GRAFT_REPO_ROOT
+export OUT=${OUT:-$R/bench_out}       # the benchmark's lines and full objects (bench.py --full), read by tools/refresh_profiles.py
+mkdir -p "$OUT"
 mkdir -p gpurun_out
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
 timeout 1800 python -m pytest tests -m gpu -x -q 2>&1 | tail -3
-python bench.py > gpurun_out/bench_line.json 2> gpurun_out/bench_full.err; echo "bench rc=$?"; cut -c1-300 gpurun_out/bench_line.json
-cp gpurun_out/bench_details.json gpurun_out/bench_full.json      # the full objects of this run (later bench runs of this script write the file again)
-SDV_BENCH_FORCE_DIST=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29655 bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu 2> gpurun_out/bench_nccl1.err | tail -1 > gpurun_out/bench_nccl_1rank.json; echo "nccl 1-rank rc=$?"
-SDV_BENCH_BACKEND=gloo timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --steps 3 --warmup 1 --frames 4000 --no-cpu 2> gpurun_out/bench_2rank.err | tail -1 > gpurun_out/bench_2rank_gloo.json; echo "2-rank rc=$?"
+timeout 900 python bench.py --full --details "$OUT/bench_full.json" > "$OUT/bench_line.json" 2> "$OUT/bench_full.err"; echo "bench rc=$?"; cut -c1-300 "$OUT/bench_line.json"
+SDV_BENCH_FORCE_DIST=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29655 bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu --full 2> "$OUT/bench_nccl1.err" | tail -1 > "$OUT/bench_nccl_1rank.json"; echo "nccl 1-rank rc=$?"
+SDV_BENCH_BACKEND=gloo timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --steps 3 --warmup 1 --frames 4000 --no-cpu --full 2> "$OUT/bench_2rank.err" | tail -1 > "$OUT/bench_2rank_gloo.json"; echo "2-rank rc=$?"
 cd /tmp && export TMPDIR=/tmp
 rm -rf $R/gpurun_out/prof_bench $R/gpurun_out/prof_stitch $R/gpurun_out/pmc1 $R/gpurun_out/pmc2 $R/gpurun_out/pmc3 $R/gpurun_out/pmc4
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_bench -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu > $R/gpurun_out/prof_bench.json 2> $R/gpurun_out/prof_bench.err; echo "rocprof bench rc=$?"
+rm -rf "$OUT/prof_bench"; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_bench" -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu --full > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.err"; echo "rocprof bench rc=$?"
 # ... and of the headline leg alone (no other leg launches the lean kernel there: its average is the launch duration the roofline line quotes)
 rm -rf $R/gpurun_out/prof_headline
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_headline -- python3 $R/bench.py --steps 20 --warmup 2 --no-cpu --no-stitch > $R/gpurun_out/prof_headline.json 2> $R/gpurun_out/prof_headline.err; echo "rocprof headline rc=$?"

@@ -4,6 +4,7 @@ import csv, glob, json, os, shutil, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.chdir(ROOT)
 RND = sys.argv[1] if len(sys.argv) > 1 else 'r06'      # the round the summaries are named for
+OUT = os.environ.get('OUT', 'bench_out')                # where tools/gpu_validate.sh put the benchmark's lines and full objects
 
 
 def newest(pat):
@@ -22,7 +23,7 @@ def trim(src, dst):
             w.writerow(r)
 
 
-trim(newest('gpurun_out/prof_bench/*/*kernel_stats.csv'), f'profiles/{RND}_rocprofv3_kernel_stats.csv')
+trim(newest(os.path.join(OUT, 'prof_bench/*/*kernel_stats.csv')), f'profiles/{RND}_rocprofv3_kernel_stats.csv')
 trim(newest('gpurun_out/prof_stitch/*/*kernel_stats.csv'), f'profiles/{RND}_rocprofv3_stitch_kernel_stats.csv')
 if glob.glob('gpurun_out/prof_headline/*/*kernel_stats.csv'):
     trim(newest('gpurun_out/prof_headline/*/*kernel_stats.csv'), f'profiles/{RND}_rocprofv3_headline_kernel_stats.csv')
@@ -35,11 +36,11 @@ if glob.glob('gpurun_out/prof_pcm1f/*/*kernel_stats.csv'):
     trim(newest('gpurun_out/prof_pcm1f/*/*kernel_stats.csv'), f'profiles/{RND}_rocprofv3_pcm1_front_kernel_stats.csv')
     subprocess.check_call([sys.executable, 'tools/pmc_to_json.py', 'sdv_k_pcm1_lines', f'profiles/{RND}_pmc_sdv_k_pcm1_lines.json', 'p1fpmc'], stdout=subprocess.DEVNULL)
     subprocess.check_call([sys.executable, 'tools/pmc_to_json.py', 'sdv_k_pcm1_lines_lean', f'profiles/{RND}_pmc_sdv_k_pcm1_lines_lean.json', 'p1fpmc'], stdout=subprocess.DEVNULL)
-shutil.copy('gpurun_out/bench_full.json', f'profiles/{RND}_bench_full.json')       # every leg's full object (bench.py's gpurun_out/bench_details.json)
-if os.path.exists('gpurun_out/bench_line.json'): shutil.copy('gpurun_out/bench_line.json', f'profiles/{RND}_bench_line.json')      # the one line the driver reads
-shutil.copy('gpurun_out/bench_2rank_gloo.json', f'profiles/{RND}_bench_2rank_gloo_one_gpu.json')
-if os.path.exists('gpurun_out/bench_nccl_1rank.json') and os.path.getsize('gpurun_out/bench_nccl_1rank.json') > 100:
-    shutil.copy('gpurun_out/bench_nccl_1rank.json', f'profiles/{RND}_bench_nccl_1rank.json')
+shutil.copy(os.path.join(OUT, 'bench_full.json'), f'profiles/{RND}_bench_full.json')       # every leg's full object (bench.py --full --details)
+if os.path.exists(os.path.join(OUT, 'bench_line.json')): shutil.copy(os.path.join(OUT, 'bench_line.json'), f'profiles/{RND}_bench_line.json')      # the one line the driver reads
+shutil.copy(os.path.join(OUT, 'bench_2rank_gloo.json'), f'profiles/{RND}_bench_2rank_gloo_one_gpu.json')
+if os.path.exists(os.path.join(OUT, 'bench_nccl_1rank.json')) and os.path.getsize(os.path.join(OUT, 'bench_nccl_1rank.json')) > 100:
+    shutil.copy(os.path.join(OUT, 'bench_nccl_1rank.json'), f'profiles/{RND}_bench_nccl_1rank.json')
 subprocess.check_call([sys.executable, 'tools/pmc_to_json.py', 'sdv_k_stc007_frames_lean', f'profiles/{RND}_pmc_sdv_k_stc007_frames_lean.json', 'pmc'], stdout=subprocess.DEVNULL)
 subprocess.check_call([sys.executable, 'tools/pmc_to_json.py', 'sdv_k_pcm1_frames', f'profiles/{RND}_pmc_sdv_k_pcm1_frames.json', 'p1pmc'], stdout=subprocess.DEVNULL)
 if glob.glob('gpurun_out/apmc3/**/*_counter_collection.csv', recursive=True):
@@ -61,7 +62,7 @@ for kern, prefix, name, workload in (
         subprocess.check_call([sys.executable, 'tools/pmc_to_json.py', kern, f'profiles/{RND}_pmc_{name}.json', prefix, workload], stdout=subprocess.DEVNULL)
 if glob.glob('gpurun_out/prof_vis/*/*kernel_stats.csv'):
     trim(newest('gpurun_out/prof_vis/*/*kernel_stats.csv'), f'profiles/{RND}_rocprofv3_vis_kernel_stats.csv')
-d = json.loads(open('gpurun_out/bench_full.json').read().strip().split('\n')[-1])
+d = json.loads(open(os.path.join(OUT, 'bench_full.json')).read().strip().split('\n')[-1])
 if os.path.exists('gpurun_out/prof_audio.log'):
     shutil.copy('gpurun_out/prof_audio.log', f'profiles/{RND}_audio_prof.log')
 print('value', d['value'], 'ms/step', d['ms_per_step'], 'frac', d['roofline']['frac'], 'launch ms', d['roofline']['avg_launch_ms'], 'traffic', d['roofline']['traffic'])
