@@ -391,7 +391,27 @@ struct sdv_engine {
      * that plays settles in that round, and the stage behind need not wait for the host to have seen that.  One call only; returns SDV_OK or an error. */
     int (*after_first_round)(void *ctx); void *after_ctx;
     bool binarize_settled_at_once;      /* the last sdv_binarize_frames call of the fused entry needed one round */
+#ifdef SDV_DEV_AIDS
+    uint32_t dev_counts[16];            /* developer builds: the launches of the last sdv_binarize_frames / sdv_binarize_lines call, by build (DevCount) */
+#endif
 };
+
+/* Developer builds count, per call, which builds of the frame kernel and the sweep kernels were launched and on how much work (sdv_dev_launch_counts):
+ * tests prove with them that a tape reached the build it was made for.  Counted here, in the host code the HIP and the emulator builds share, with the
+ * same choice rt::launch_frames makes. */
+enum DevCount { DEV_LEAN = 0, DEV_SNAP = 2, DEV_PLAIN = 4, DEV_FAT = 6, DEV_SWEEP_LEVELS = 8, DEV_SWEEP_PICK = 10, DEV_LINES = 12, DEV_N_COUNTS = 14 };
+#ifdef SDV_DEV_AIDS
+static inline void dev_reset_counts(sdv_engine *e) { memset(e->dev_counts, 0, sizeof(e->dev_counts)); }
+static inline void dev_count(sdv_engine *e, int what, size_t work) { e->dev_counts[what]++; e->dev_counts[what + 1] += (uint32_t)work; }     /* launches, then frames / requests / lines */
+static inline void dev_count_frames(sdv_engine *e, const sdv::FrameArgs &a, bool lean, int n)
+{
+    if (n > 0) dev_count(e, lean ? DEV_LEAN : a.fat_levels ? DEV_FAT : a.tc_hdr ? DEV_SNAP : DEV_PLAIN, (size_t)n);
+}
+#else
+static inline void dev_reset_counts(sdv_engine *) {}
+static inline void dev_count(sdv_engine *, int, size_t) {}
+static inline void dev_count_frames(sdv_engine *, const sdv::FrameArgs &, bool, int) {}
+#endif
 
 static thread_local std::string g_last_error;      /* sdv_last_error(NULL): the last failure on the calling thread */
 static void set_error(sdv_engine *e, const std::string &msg) { if (e) e->last_error = msg; g_last_error = msg; }
@@ -451,6 +471,7 @@ sdv_engine *sdv_engine_create(int device)
     e->have_events = false; e->have_mark = false;
 #endif
     e->after_first_round = NULL; e->after_ctx = NULL; e->binarize_settled_at_once = false;
+    dev_reset_counts(e);
     return e;
 }
 
@@ -558,6 +579,16 @@ int sdv_get_pcm16x0_chain_state(const sdv_engine *e, void *out, size_t cap) { if
 int sdv_set_pcm16x0_chain_state(sdv_engine *e, const void *in, size_t n) { if (!e || !in || n < sizeof(sdvp16f::State16)) return SDV_ERR_BAD_ARG; memcpy(&e->chain16, in, sizeof(e->chain16)); return SDV_OK; }
 int sdv_set_profiling(sdv_engine *e, int on) { if (!e) return SDV_ERR_BAD_ARG; e->profiling = on != 0; return SDV_OK; }
 int sdv_get_run_info(const sdv_engine *e, sdv_run_info *out) { if (!e || !out) return SDV_ERR_BAD_ARG; *out = e->info; return SDV_OK; }
+#ifdef SDV_DEV_AIDS
+/* developer builds: the launch counts of the last call (DevCount: launches and work of the lean, snapshot, plain and five-wave frame kernels, sweep_levels,
+ * sweep_pick, stc007_lines passes); copies min(n, DEV_N_COUNTS) of them, returns DEV_N_COUNTS */
+int sdv_dev_launch_counts(const sdv_engine *e, uint32_t *out, size_t n)
+{
+    if (!e || (n > 0 && !out)) return SDV_ERR_BAD_ARG;
+    for (size_t i = 0; i < n && i < (size_t)DEV_N_COUNTS; i++) out[i] = e->dev_counts[i];
+    return DEV_N_COUNTS;
+}
+#endif
 
 size_t sdv_records_per_frame(int height) { return (size_t)height + 3; }
 size_t sdv_pcm16x0_binarize_records(int height, int n_frames, unsigned flags)
@@ -748,6 +779,7 @@ int sdv_binarize_frames(sdv_engine *e, const uint8_t *luma, size_t row_stride, s
     }
 
     memset(&e->info, 0, sizeof(e->info));
+    dev_reset_counts(e);
     e->info.frames = (uint32_t)n_frames;
     /* A stream that plays (the chain is tuned, the last call's frames did not need the full kernel): the waves of the first round make the state they start
      * from themselves, from the one state that is known (FrameArgs::predict_in_kernel) - no copy and no kernel in front of the frame kernel.  The states go to
@@ -816,6 +848,7 @@ int sdv_binarize_frames(sdv_engine *e, const uint8_t *luma, size_t row_stride, s
             sa.doubled = a.doubled; sa.mode = a.mode; sa.preset = a.preset;
             sa.memo = e->d_memo; sa.first = lo; sa.count = cnt; sa.levels = e->d_sweep_levels;
             RT_CHECK(rt::launch_sweeps(sa, s));
+            dev_count(e, DEV_SWEEP_LEVELS, (size_t)cnt); dev_count(e, DEV_SWEEP_PICK, (size_t)cnt);
             e->info.sweeps += (uint32_t)cnt;
         }
         memo_done = have;
@@ -856,6 +889,7 @@ int sdv_binarize_frames(sdv_engine *e, const uint8_t *luma, size_t row_stride, s
              * for sweeps, ten each: those are better settled side by side - 400 PAL frames 7.7 against 8.4 ms) */
             const bool fat = range_full && memo_ready && cold_frame && hi - lo == 1 && !dev_env("SDV_NO_FAT");
             if (fat) { a.fat_levels = e->d_sweep_levels; round_fat = true; }
+            dev_count_frames(e, a, range_lean, hi - lo);
             RT_CHECK(rt::launch_frames(a, s, range_lean));
             a.fat_levels = NULL;
             launched += (uint32_t)(hi - lo); if (range_full) general += (uint32_t)(hi - lo);
@@ -869,6 +903,7 @@ int sdv_binarize_frames(sdv_engine *e, const uint8_t *luma, size_t row_stride, s
             }
             if (!list_lean.empty()) {
                 a.frame_list = e->d_list_lean;
+                dev_count_frames(e, a, true, (int)list_lean.size());
                 RT_CHECK(rt::launch_frames(a, s, true, (int)list_lean.size()));
                 launched += (uint32_t)list_lean.size();
             }
@@ -879,6 +914,7 @@ int sdv_binarize_frames(sdv_engine *e, const uint8_t *luma, size_t row_stride, s
                  * better settled all at once: the machine is full of them.) */
                 const bool fat = memo_ready && sweeps_seen > 0 && list_full.size() <= (e->cap_sweep_levels < 512 ? e->cap_sweep_levels : (size_t)512) && !dev_env("SDV_NO_FAT");
                 if (fat) { a.fat_levels = e->d_sweep_levels; round_fat = true; }
+                dev_count_frames(e, a, false, (int)list_full.size());
                 RT_CHECK(rt::launch_frames(a, s, false, (int)list_full.size()));
                 a.fat_levels = NULL;
                 launched += (uint32_t)list_full.size(); general += (uint32_t)list_full.size();
@@ -1244,13 +1280,16 @@ int sdv_binarize_lines(sdv_engine *e, const uint8_t *luma, size_t row_stride, in
     a.doubled = (flags & SDV_FLAG_DOUBLED) ? 1 : 0; a.mode = (uint8_t)e->mode; a.preset = e->preset;
     a.out = out_lines; a.done = e->d_line_done;
     a.memo = e->d_memo; a.memo_head = e->d_memo_head; a.memo_count = e->d_memo_count; a.memo_cap = (int32_t)e->cap_memo;
+    dev_reset_counts(e);
     int settled = 0;
     for (int pass = 0;; pass++) {
         if (pass > 4) { set_error(e, "the sweeps of the lines did not settle"); return SDV_ERR_HIP; }
+        dev_count(e, DEV_LINES, n_lines);
         RT_CHECK(rt::launch_stc_lines(a, s));
         int32_t count = 0;
         RT_CHECK(rt::d2h(&count, e->d_memo_count, sizeof(count), s));
-        if (count > (int32_t)e->cap_memo) count = (int32_t)e->cap_memo;
+        /* (the pool holds a request per line and more: a line asks for one sweep at most - one that did not fit would leave its line waiting for good) */
+        if (count > (int32_t)e->cap_memo) { set_error(e, "the pool of sweep requests ran over: " + std::to_string(count) + " requests, room for " + std::to_string(e->cap_memo)); return SDV_ERR_HIP; }
         if (count <= settled) break;
         enum { CHUNK = 16384 };
         for (int lo = settled; lo < count; lo += CHUNK) {
@@ -1266,9 +1305,18 @@ int sdv_binarize_lines(sdv_engine *e, const uint8_t *luma, size_t row_stride, in
             sa.luma = luma; sa.frame_stride = (size_t)sdv::LINES_PER_MEMO_FRAME * row_stride; sa.row_stride = row_stride; sa.width = width;
             sa.doubled = a.doubled; sa.mode = a.mode; sa.preset = a.preset;
             sa.memo = e->d_memo; sa.first = lo; sa.count = cnt; sa.levels = e->d_sweep_levels;
+            dev_count(e, DEV_SWEEP_LEVELS, (size_t)cnt); dev_count(e, DEV_SWEEP_PICK, (size_t)cnt);
             RT_CHECK(rt::launch_sweeps(sa, s));
         }
         settled = count;
+    }
+    /* every line's record is final: a line still waiting for a sweep holds a placeholder record, and the call says so instead of handing it out */
+    {
+        std::vector<uint8_t> done(n_lines);
+        RT_CHECK(rt::d2h(done.data(), e->d_line_done, n_lines, s));
+        size_t pending = 0;
+        for (size_t i = 0; i < n_lines; i++) pending += done[i] == 0;
+        if (pending) { set_error(e, std::to_string(pending) + " of " + std::to_string(n_lines) + " lines were left waiting for a reference-level sweep"); return SDV_ERR_HIP; }
     }
     return SDV_OK;
 }

@@ -190,3 +190,18 @@ def emu_binarize(lib, eng, luma, first_frame_no=1, flags=1, row_stride=None, mis
     rc = lib.sdv_binarize_frames(eng, luma.ctypes.data, w, w * h, w, h, n, first_frame_no, flags, recs.ctypes.data, len(recs),
                                  stats.ctypes.data, len(stats), None)
     return rc, recs, stats
+
+
+LAUNCH_COUNT_NAMES = ("lean", "lean_frames", "snap", "snap_frames", "plain", "plain_frames", "fat", "fat_frames",
+                      "sweep_levels", "sweep_levels_reqs", "sweep_pick", "sweep_pick_reqs", "lines", "lines_lines")
+
+
+def launch_counts(lib, eng):
+    """Developer builds only (SDV_DEV_AIDS: the emulator build, libsdvpcm_hip_dev.so): the launches of the last sdv_binarize_frames /
+    sdv_binarize_lines call by kernel build, and the frames / sweep requests / lines they were given (sdv_dev_launch_counts, engine.inc DevCount)."""
+    f = lib.sdv_dev_launch_counts
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    out = (C.c_uint32 * len(LAUNCH_COUNT_NAMES))()
+    assert f(eng, out, len(out)) == len(LAUNCH_COUNT_NAMES)
+    return dict(zip(LAUNCH_COUNT_NAMES, (int(x) for x in out)))

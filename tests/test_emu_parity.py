@@ -258,11 +258,17 @@ def test_emu_cold_chain_settles_its_first_sweep_in_one_pass(emu_lib, oracle_lib,
     seen = {}
     for switch in (None, "SDV_NO_FAT"):
         if switch: monkeypatch.setenv(switch, "1")
-        got, got_stats, info = emu_run(emu_lib, luma, 2)
+        eng = C.c_void_p(emu_lib.sdv_engine_create(0))
+        emu_lib.sdv_set_mode(eng, 2)
+        got, got_stats, info = emu_run(emu_lib, luma, 2, eng=eng)
+        counts = engine_api.launch_counts(emu_lib, eng)
+        emu_lib.sdv_engine_destroy(eng)
         if switch: monkeypatch.delenv(switch)
         assert got.tobytes() == want.tobytes(), golden_cases.diff_report(got, want)
         assert got_stats.view(np.uint8).tobytes() == want_stats.tobytes()
         seen[switch] = (info.rounds, info.sweeps)
+        if switch: assert counts["fat"] == 0 and counts["sweep_levels"] >= 1, counts
+        else: assert counts["fat"] == 1 and counts["fat_frames"] == 1 and counts["sweep_levels"] == 0, counts
     assert seen[None] == (2, seen["SDV_NO_FAT"][1]) and seen["SDV_NO_FAT"][0] == 3 and seen[None][1] >= 1, seen
 
 
@@ -278,11 +284,17 @@ def test_emu_small_rounds_settle_their_sweeps_themselves(emu_lib, oracle_lib, mo
     seen = {}
     for switch in (None, "SDV_NO_FAT"):
         if switch: monkeypatch.setenv(switch, "1")
-        got, got_stats, info = emu_run(emu_lib, luma, 2)
+        eng = C.c_void_p(emu_lib.sdv_engine_create(0))
+        emu_lib.sdv_set_mode(eng, 2)
+        got, got_stats, info = emu_run(emu_lib, luma, 2, eng=eng)
+        counts = engine_api.launch_counts(emu_lib, eng)
+        emu_lib.sdv_engine_destroy(eng)
         if switch: monkeypatch.delenv(switch)
         assert got.tobytes() == want.tobytes(), golden_cases.diff_report(got, want)
         assert got_stats.view(np.uint8).tobytes() == want_stats.tobytes()
         seen[switch] = (info.rounds, info.frames_general, info.sweeps)
+        assert (counts["fat"] == 0) == bool(switch), counts
+        assert counts["snap_frames"] + counts["plain_frames"] + counts["fat_frames"] == info.frames_general, (counts, info.frames_general)
     assert seen[None][0] < seen["SDV_NO_FAT"][0] and seen[None][1] < seen["SDV_NO_FAT"][1], seen
     assert seen[None][2] > 40, seen
 
@@ -366,6 +378,9 @@ def test_emu_worn_tape_without_meetings_takes_the_plain_general_kernel(emu_lib, 
     for k in range(4):
         b, sb, info = emu_run(emu_lib, lum[k * n:(k + 1) * n], 2, flags=1 if k == 0 else 0, first=1 + k * n, eng=eng)
         got.append(b); gs.append(sb); met.append(info.frames_met); general.append(info.frames_general)
+        counts = engine_api.launch_counts(emu_lib, eng)
+        if k == 0: assert counts["plain"] == 0, counts
+        else: assert counts["plain_frames"] >= n and counts["snap"] == 0, (k, counts)          # every frame's first round: the plain build
     emu_lib.sdv_engine_destroy(eng)
     got = np.concatenate(got)
     assert got.tobytes() == want.tobytes(), golden_cases.diff_report(got, want)
@@ -442,8 +457,12 @@ def test_emu_worn_tape_mark_comes_and_goes(emu_lib, oracle_lib):
     # ... so the next call starts on the full kernel; its frames are clean: the mark comes off, the call behind it is the lean kernel's again
     more, _, _ = synth.stc007_frames(40, seed=92, noise_sigma=3.0, height=96, lines_per_field=48)
     _, _, info3 = emu_run(emu_lib, more[:12], 2, flags=0, first=26, eng=eng)
+    c3 = engine_api.launch_counts(emu_lib, eng)
     _, _, info4 = emu_run(emu_lib, more[12:24], 2, flags=0, first=38, eng=eng)
+    c4 = engine_api.launch_counts(emu_lib, eng)
     emu_lib.sdv_engine_destroy(eng)
+    assert c3["snap_frames"] + c3["plain_frames"] >= 12 and c3["lean"] == 0, c3          # the worn call: every frame on a general build from the start
+    assert c4["lean_frames"] >= 12 and c4["snap"] + c4["plain"] + c4["fat"] == 0, c4
     assert info3.frames_general >= 12 and info4.frames_general == 0, (info3.frames_general, info4.frames_general)
 
 
@@ -500,3 +519,29 @@ def test_emu_lines_that_read_on_other_rungs_of_the_ladder(emu_lib, oracle_lib, s
     got, stats, info = emu_run(emu_lib, luma, 2)
     assert got.tobytes() == want.tobytes(), golden_cases.diff_report(got, want)
     assert stats.view(np.uint8).tobytes() == want_stats.tobytes()
+
+
+def test_emu_worn_tape_plain_build_and_its_reprobe(emu_lib, oracle_lib):
+    """The worn tape of the test above in ten calls of twelve frames (at a small height): the first call looks at the tape with the snapshots, calls 2-8 and
+    10 take the plain build, call 9 looks again with the snapshots (engine.inc: plain_calls % 8) - launch counts by build, records, frame descriptors and the
+    chain state at the end against the sequential oracle."""
+    import kernel_path_tapes as K
+    luma = K.worn_tape(120, 24)
+    want, want_stats, want_state = oracle_binarize(luma, mode=2, return_state=True)
+    eng = C.c_void_p(emu_lib.sdv_engine_create(0))
+    emu_lib.sdv_set_mode(eng, 2)
+
+    def call(chunk, first, new_file):
+        rc, r, st = engine_api.emu_binarize(emu_lib, eng, chunk, first_frame_no=first, flags=1 if new_file else 0)
+        assert rc == 0
+        info = engine_api.RunInfo(); emu_lib.sdv_get_run_info(eng, C.byref(info))
+        return r, st, info, engine_api.launch_counts(emu_lib, eng)
+
+    recs, stats, per_call = K.run_stream(call, luma, [12] * 10)
+    state = C.create_string_buffer(120)
+    assert emu_lib.sdv_get_chain_state(eng, state) == 0
+    emu_lib.sdv_engine_destroy(eng)
+    assert recs.tobytes() == want.tobytes(), golden_cases.diff_report(recs.view(libs.LINE_DTYPE), want)
+    assert stats.tobytes() == want_stats.tobytes() and state.raw == want_state.tobytes()
+    counts = [c for _, c in per_call]
+    assert K.check_counts("worn_plain_reprobe", counts) is None, counts

@@ -93,7 +93,8 @@ def _states_behind(recs, mode):
     return st
 
 
-def _engine_lines_host(lib, eng, rows, states, mode, doubled=False, first_line=1, line_step=2, frame=7):
+def _engine_lines_host(lib, eng, rows, states, mode, doubled=False, first_line=1, line_step=2, frame=7, pad=0):
+    """pad > 0: the lines in a buffer of rows pad bytes longer than a line (row_stride > width), the bytes between them 0x5A."""
     f = lib.sdv_binarize_lines
     f.restype = C.c_int
     f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint16, C.c_uint16, C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -101,7 +102,11 @@ def _engine_lines_host(lib, eng, rows, states, mode, doubled=False, first_line=1
     lib.sdv_set_mode(eng, mode)
     out = np.zeros(len(rows), dtype=libs.LINE_DTYPE)
     st = None if states is None else np.ascontiguousarray(states)
-    rc = f(eng, rows.ctypes.data, rows.shape[1], rows.shape[1], len(rows), None if st is None else st.ctypes.data, frame, first_line, line_step,
+    buf = rows
+    if pad:
+        buf = np.full((len(rows), rows.shape[1] + pad), 0x5A, dtype=np.uint8)
+        buf[:, :rows.shape[1]] = rows
+    rc = f(eng, buf.ctypes.data, buf.shape[1], rows.shape[1], len(rows), None if st is None else st.ctypes.data, frame, first_line, line_step,
            2 if doubled else 0, out.ctypes.data, len(out), None)
     return rc, out
 
@@ -142,6 +147,23 @@ def test_emu_lines_equal_the_oracle(emu_lib, oracle_lib, mode):
     emu_lib.sdv_engine_destroy(eng)
 
 
+# other line shapes: widths of half and double the usual without doubling, an odd width, rows padded beyond the line (row_stride > width), MODE_DRAFT
+LINE_SHAPES = [(360, 0, 2), (1440, 0, 2), (721, 0, 2), (720, 13, 2), (720, 0, 0)]
+
+
+@pytest.mark.parametrize("width,pad,mode", LINE_SHAPES)
+def test_emu_lines_other_shapes(emu_lib, oracle_lib, width, pad, mode):
+    rows = _lines(seed=10, width=width)
+    eng = C.c_void_p(emu_lib.sdv_engine_create(0))
+    for states in (None, "behind"):
+        if states == "behind":
+            states = _states_behind(_oracle_lines(rows, None, mode), mode)
+        want = _oracle_lines(rows, states, mode)
+        rc, got = _engine_lines_host(emu_lib, eng, rows, states, mode, pad=pad)
+        assert rc == 0 and got.tobytes() == want.tobytes()
+    emu_lib.sdv_engine_destroy(eng)
+
+
 def test_emu_lines_refuse_bad_arguments(emu_lib):
     eng = C.c_void_p(emu_lib.sdv_engine_create(0))
     rows = np.zeros((2, 100), dtype=np.uint8)
@@ -177,4 +199,25 @@ def test_gpu_lines_equal_the_oracle(oracle_lib, mode, doubled):
         want = _oracle_lines(np.ascontiguousarray(luma.reshape(-1, 720)[::2]), None, mode)
         got = eng.binarize_lines(field, None, frame_number=7, first_line=1, line_step=2).cpu().numpy()
         assert got.tobytes() == want.tobytes()
+    eng.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("width,pad,mode", LINE_SHAPES)
+def test_gpu_lines_other_shapes(oracle_lib, width, pad, mode):
+    import torch
+    from sdvpcmdecoder_amd import Engine
+    rows = _lines(seed=10, width=width)
+    cold = _oracle_lines(rows, None, mode)
+    states = _states_behind(cold, mode)
+    behind = _oracle_lines(rows, states, mode)
+    buf = torch.full((len(rows), width + pad), 0x5A, dtype=torch.uint8, device="cuda:0")
+    buf[:, :width] = torch.from_numpy(rows).cuda()
+    view = buf[:, :width]
+    assert view.stride(0) == width + pad
+    eng = Engine(0); eng.setBinarizationMode(mode)
+    got = eng.binarize_lines(view, None, frame_number=7, first_line=1, line_step=2).cpu().numpy()
+    assert got.tobytes() == cold.tobytes()
+    got = eng.binarize_lines(view, torch.from_numpy(states.view(np.uint8).reshape(len(states), 10)).cuda(), frame_number=7, first_line=1, line_step=2).cpu().numpy()
+    assert got.tobytes() == behind.tobytes()
     eng.close()
