@@ -51,6 +51,12 @@ def source_hash(kernel=None):
     return h.hexdigest()[:16]
 
 
+def hip_sources():
+    """Every file the HIP library and the emulator build of the same engine are compiled from: csrc/ and the C-ABI header."""
+    csrc = os.path.join(PKG, "csrc")
+    return [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".h", ".hip", ".inc"))] + [os.path.join(ROOT, "include", "sdvpcm.h")]
+
+
 def _newer(target, sources):
     if not os.path.exists(target):
         return True
@@ -65,8 +71,7 @@ def build_hip_dev(force=False):
     """TEST ONLY: the developer build of the same sources (-DSDV_DEV_AIDS: the scheduler's off-switches and traces can be set through the environment).
     The product never loads it; tests/test_decode_frames.py runs the fused entry's defensive ways through it on the GPU, in a process of its own."""
     csrc = os.path.join(PKG, "csrc")
-    srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".h", ".hip", ".inc"))] + [os.path.join(ROOT, "include", "sdvpcm.h")]
-    if not force and not _newer(HIP_DEV_LIB, srcs):
+    if not force and not _newer(HIP_DEV_LIB, hip_sources()):
         return HIP_DEV_LIB
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     subprocess.check_call([hipcc, "-DSDV_DEV_AIDS", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-value",
@@ -76,10 +81,7 @@ def build_hip_dev(force=False):
 
 def build_hip(force=False):
     csrc = os.path.join(PKG, "csrc")
-    srcs = [os.path.join(csrc, f) for f in ("sdvpcm_hip.hip", "stc007_device.h", "stc007_sweep_device.h", "stc007_deint_device.h", "stc007_stitch_device.h", "engine.inc",
-                                              "stitch_engine.inc", "pcm1_stitch_device.h", "pcm1_bin_device.h", "pcm1_engine.inc", "pcm1_frames_device.h", "pcm1_frames_engine.inc", "pcm16_bin_device.h", "pcm16_frames_device.h", "pcm16_frames_engine.inc", "pcm16_engine.inc", "pcm16_stitch_device.h", "audio_device.h", "audio_engine.inc", "vis_device.h", "vis_engine.inc")] + \
-           [os.path.join(ROOT, "include", "sdvpcm.h")]
-    if not force and not _newer(HIP_LIB, srcs):
+    if not force and not _newer(HIP_LIB, hip_sources()):
         return HIP_LIB
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-value",
@@ -146,12 +148,7 @@ def build_reference():
 def build_emu(force=False):
     d = os.path.join(ROOT, "tests", "emu")
     out = os.path.join(d, "libsdvpcm_emu.so")
-    srcs = [os.path.join(d, "emu_engine.cpp"), os.path.join(d, "hip_emu.h"),
-            os.path.join(PKG, "csrc", "stc007_device.h"), os.path.join(PKG, "csrc", "stc007_sweep_device.h"), os.path.join(PKG, "csrc", "stc007_deint_device.h"),
-            os.path.join(PKG, "csrc", "engine.inc"), os.path.join(PKG, "csrc", "stc007_stitch_device.h"),
-            os.path.join(PKG, "csrc", "stitch_engine.inc"),
-            os.path.join(PKG, "csrc", "pcm1_stitch_device.h"), os.path.join(PKG, "csrc", "pcm1_bin_device.h"), os.path.join(PKG, "csrc", "pcm1_engine.inc"), os.path.join(PKG, "csrc", "pcm1_frames_device.h"), os.path.join(PKG, "csrc", "pcm1_frames_engine.inc"), os.path.join(PKG, "csrc", "pcm16_bin_device.h"), os.path.join(PKG, "csrc", "pcm16_frames_device.h"), os.path.join(PKG, "csrc", "pcm16_frames_engine.inc"), os.path.join(PKG, "csrc", "pcm16_engine.inc"), os.path.join(PKG, "csrc", "pcm16_stitch_device.h"), os.path.join(PKG, "csrc", "audio_device.h"), os.path.join(PKG, "csrc", "audio_engine.inc"),
-            os.path.join(PKG, "csrc", "vis_device.h"), os.path.join(PKG, "csrc", "vis_engine.inc"), os.path.join(ROOT, "include", "sdvpcm.h")]
+    srcs = [os.path.join(d, "emu_engine.cpp"), os.path.join(d, "hip_emu.h")] + hip_sources()
     if not force and not _newer(out, srcs):
         return out
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-function", "-o", out,

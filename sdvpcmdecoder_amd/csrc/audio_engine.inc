@@ -12,25 +12,25 @@
 #include <algorithm>
 
 struct sdv_audio {
+    /* (made by new sdv_audio(): everything that is not a buffer starts as zero) */
     int mask_mode;
-    sdv_sample_pair *d_carry, *d_carry_spare, *d_carry_snap; uint32_t n_carry;    /* what waits in the window (at most 512 pairs each) */
+    rt::DevBuf<sdv_sample_pair> d_carry, d_carry_spare, d_carry_snap; uint32_t n_carry;    /* what waits in the window (at most 512 pairs each) */
     uint64_t next_index;            /* PCMSample::index of the next pair that leaves */
     bool stalled;                   /* the window is full and its first pairs can never leave: the worker takes no more input (audioprocessor.cpp:108) */
-    uint32_t *d_count; uint64_t *d_tags;
-    sdva::Stretch *d_st; sdva::StretchResult *d_res; size_t cap_st;
-    sdv_sample_pair *d_w; size_t cap_w;
-    uint64_t *d_bad1, *d_bad3, *d_v0, *d_v1, *d_m0, *d_m1; size_t cap_bad;
-    uint8_t *d_bad2;
-    sdva::WinRec *d_wins; size_t cap_wins; uint32_t *d_win_base; size_t cap_win_base;
+    rt::DevBuf<uint32_t> d_count; rt::DevBuf<uint64_t> d_tags;
+    rt::DevBuf<sdva::Stretch> d_st; rt::DevBuf<sdva::StretchResult> d_res;
+    rt::DevBuf<sdv_sample_pair> d_w;
+    rt::DevBuf<uint64_t> d_bad1, d_bad3, d_v0, d_v1, d_m0, d_m1;
+    rt::DevBuf<uint8_t> d_bad2;
+    rt::DevBuf<sdva::WinRec> d_wins; rt::DevBuf<uint32_t> d_win_base;
     /* sdv_decode_frames: what passes from stage to stage */
-    uint8_t *d_chain_recs; size_t cap_chain_recs; sdv_frame_stats *d_chain_stats; size_t cap_chain_stats; sdv_sample_pair *d_chain_pairs; size_t cap_chain_pairs;
+    rt::DevBuf<uint8_t> d_chain_recs; rt::DevBuf<sdv_frame_stats> d_chain_stats; rt::DevBuf<sdv_sample_pair> d_chain_pairs;
 };
 
 static sdv_audio *audio_get(sdv_engine *e)
 {
     if (e->audio) return e->audio;
     sdv_audio *t = new sdv_audio();
-    memset(t, 0, sizeof(*t));
     t->mask_mode = SDV_DROP_IGNORE;     /* the constructor's DROP_IGNORE (audioprocessor.cpp:15) */
     e->audio = t;
     return t;
@@ -39,8 +39,6 @@ static void audio_free(sdv_engine *e)
 {
     sdv_audio *t = e->audio;
     if (!t) return;
-    void *ptrs[] = { t->d_carry, t->d_carry_spare, t->d_carry_snap, t->d_count, t->d_tags, t->d_st, t->d_res, t->d_w, t->d_bad1, t->d_bad2, t->d_bad3, t->d_v0, t->d_v1, t->d_m0, t->d_m1, t->d_wins, t->d_win_base, t->d_chain_recs, t->d_chain_stats, t->d_chain_pairs };
-    for (void *p : ptrs) if (p) rt::dfree(p);
     delete t;
     e->audio = NULL;
 }
@@ -138,7 +136,7 @@ static int audio_process_span(sdv_engine *e, sdv_audio *t, const sdv_sample_pair
     uint32_t left = 0, carry_from = 0;
     sdv_sample_pair *work = NULL; bool is_direct = false;
     if (total_w > 0) {
-        if (n_st > t->cap_st) { const size_t c = n_st + n_st / 2 + 16; ST_GROW(t->d_st, sdva::Stretch, c); ST_GROW(t->d_res, sdva::StretchResult, c); t->cap_st = c; }
+        RT_CHECK(rt::reserve_all(n_st, n_st + n_st / 2 + 16, t->d_st, t->d_res));
         /* The work array.  Where every stretch that can put something out lies at the same index in the work array as in the output - a
          * burst that continues or holds one file, the streaming case: only a purge that drops a pair shifts what follows it - the caller's
          * buffer is the work array and the emit pass falls away (the pairs cross HBM once in each direction); else a buffer of the engine. */
@@ -146,22 +144,21 @@ static int audio_process_span(sdv_engine *e, sdv_audio *t, const sdv_sample_pair
         if (direct && pairs && (const char *)pairs < (const char *)(out_pairs + out_cap) && (const char *)out_pairs < (const char *)(pairs + n_pairs))
             direct = false;         /* input and output overlap (a call in place): the input has to be read before anything is written */
         for (size_t k = 0; k < n_st && direct; k++) if (st[k].v_len > 1 && (uint64_t)st[k].w_base != st[k].out_base) direct = false;
-        if (!direct && total_w > t->cap_w) { const size_t c = (size_t)total_w + total_w / 8 + 4096; ST_GROW(t->d_w, sdv_sample_pair, c); t->cap_w = c; }
-        work = direct ? out_pairs : t->d_w; is_direct = direct;
+        if (!direct) RT_CHECK(t->d_w.reserve((size_t)total_w, (size_t)total_w + total_w / 8 + 4096));
+        work = direct ? out_pairs : t->d_w.p; is_direct = direct;
         const size_t n1 = ((size_t)total_w + 63) / 64, n2 = (n1 + 63) / 64, n3 = (n2 + 63) / 64;
-        if (n1 > t->cap_bad) {
+        {
             const size_t c = n1 + n1 / 8 + 64;
-            ST_GROW(t->d_bad1, uint64_t, c); ST_GROW(t->d_bad2, uint8_t, (c + 63) / 64 * 64 + 64); ST_GROW(t->d_bad3, uint64_t, (c + 4095) / 4096 + 1);
-            ST_GROW(t->d_v0, uint64_t, c); ST_GROW(t->d_v1, uint64_t, c); ST_GROW(t->d_m0, uint64_t, c); ST_GROW(t->d_m1, uint64_t, c);
-            t->cap_bad = c;
+            RT_CHECK(rt::reserve_all(n1, c, t->d_bad1, t->d_v0, t->d_v1, t->d_m0, t->d_m1));
+            RT_CHECK(t->d_bad2.reserve((n1 + 63) / 64 * 64 + 64, (c + 63) / 64 * 64 + 64)); RT_CHECK(t->d_bad3.reserve((n1 + 4095) / 4096 + 1, (c + 4095) / 4096 + 1));
         }
         /* the window lists: a full window that does not stall puts out at least MIN_ADVANCE pairs */
         std::vector<uint32_t> win_base(n_st + 1);
         size_t n_slots = 0;
         for (size_t k = 0; k < n_st; k++) { win_base[k] = (uint32_t)n_slots; n_slots += st[k].v_len / (size_t)sdva::MIN_ADVANCE + 2; }
         win_base[n_st] = (uint32_t)n_slots;
-        if (n_slots > t->cap_wins) { const size_t c = n_slots + n_slots / 8 + 64; ST_GROW(t->d_wins, sdva::WinRec, c); t->cap_wins = c; }
-        if (n_st + 1 > t->cap_win_base) { const size_t c = n_st + 1 + n_st / 2 + 16; ST_GROW(t->d_win_base, uint32_t, c); t->cap_win_base = c; }
+        RT_CHECK(t->d_wins.reserve(n_slots, n_slots + n_slots / 8 + 64));
+        RT_CHECK(t->d_win_base.reserve(n_st + 1, n_st + 1 + n_st / 2 + 16));
         RT_CHECK(rt::h2d(t->d_win_base, win_base.data(), (n_st + 1) * sizeof(uint32_t), s));
         if (n_pairs == 0) RT_CHECK(rt::dzero(t->d_count + 1, sizeof(uint32_t), s));    /* has_mi (zeroed with the tag counter otherwise) */
         RT_CHECK(rt::h2d(t->d_st, st.data(), n_st * sizeof(sdva::Stretch), s));
@@ -253,7 +250,7 @@ static int audio_process_span(sdv_engine *e, sdv_audio *t, const sdv_sample_pair
         left = 1;
     }
     RT_CHECK(rt::ssync(s));
-    std::swap(t->d_carry, t->d_carry_spare);
+    t->d_carry.swap(t->d_carry_spare);
     t->n_carry = left;
     t->stalled = stalled;
     if (stalled) *split_at = n_pairs;           /* nothing behind the window is looked at */
@@ -274,13 +271,9 @@ int sdv_audio_process(sdv_engine *e, const sdv_sample_pair *pairs, size_t n_pair
     rt::stream_t s = (rt::stream_t)stream;
     SDV_ON_DEVICE(e);
     sdv_audio *t = audio_get(e);
-    if (!t->d_count) {
-        RT_CHECK(rt::dmalloc((void **)&t->d_count, 4 * sizeof(uint32_t)));
-        RT_CHECK(rt::dmalloc((void **)&t->d_tags, (size_t)sdva::MAX_TAGS * sizeof(uint64_t)));
-        RT_CHECK(rt::dmalloc((void **)&t->d_carry, (size_t)sdva::WIN * sizeof(sdv_sample_pair)));
-        RT_CHECK(rt::dmalloc((void **)&t->d_carry_spare, (size_t)sdva::WIN * sizeof(sdv_sample_pair)));
-        RT_CHECK(rt::dmalloc((void **)&t->d_carry_snap, (size_t)sdva::WIN * sizeof(sdv_sample_pair)));
-    }
+    RT_CHECK(t->d_count.reserve(4));
+    RT_CHECK(t->d_tags.reserve(sdva::MAX_TAGS));
+    RT_CHECK(rt::reserve_all(sdva::WIN, sdva::WIN, t->d_carry, t->d_carry_spare, t->d_carry_snap));
     /* The turns of the worker's loop end where its queue runs dry - the end of the call - and at an END_FILE tag (fillUntilBufferFull
      * leaves its loop there, :138-152).  An END_FILE that finds fewer than three pairs in the window does not purge (outputAudio :1298-1301):
      * the one or two pairs are scanned as the end of a file and stay, and the next turn fills up behind them.  Such a tag therefore splits
@@ -382,24 +375,21 @@ int sdv_decode_frames(sdv_engine *e, int pcm_type, const uint8_t *luma, size_t r
     const size_t n_recs = pcm_type == SDV_PCM_PCM16X0 ? sdv_pcm16x0_binarize_records(height, n_frames, flags) : sdv_binarize_records(height, n_frames, flags);
     const size_t rec_bytes = pcm_type == SDV_PCM_STC007 ? sizeof(sdv_line_rec) : pcm_type == SDV_PCM_PCM1 ? sizeof(sdv_pcm1_bin_rec) + sizeof(sdv_pcm1_line_rec) : sizeof(sdv_pcm16x0_bin_rec);
     const size_t stats_n = (size_t)n_frames + ((flags & SDV_FLAG_END_FILE) ? 1 : 0);
-    if (n_recs * rec_bytes > t->cap_chain_recs) {
-        const size_t c = n_recs * rec_bytes + n_recs * rec_bytes / 8 + 4096;
-        ST_GROW(t->d_chain_recs, uint8_t, c); t->cap_chain_recs = c;
-    }
-    if (!out_stats && stats_n > t->cap_chain_stats) { const size_t c = stats_n + stats_n / 8 + 16; ST_GROW(t->d_chain_stats, sdv_frame_stats, c); t->cap_chain_stats = c; }
-    sdv_frame_stats *stats = out_stats ? out_stats : t->d_chain_stats;
-    const size_t stats_room = out_stats ? stats_cap : t->cap_chain_stats;
+    RT_CHECK(t->d_chain_recs.reserve(n_recs * rec_bytes, n_recs * rec_bytes + n_recs * rec_bytes / 8 + 4096));
+    if (!out_stats) RT_CHECK(t->d_chain_stats.reserve(stats_n, stats_n + stats_n / 8 + 16));
+    sdv_frame_stats *stats = out_stats ? out_stats : t->d_chain_stats.p;
+    const size_t stats_room = out_stats ? stats_cap : t->d_chain_stats.cap;
     /* with the audio stage behind it the stitcher writes into a buffer of the engine (the caller's buffer takes the masked stream) */
     sdv_sample_pair *raw = out_pairs; size_t raw_cap = pairs_cap;
     if (with_audio) {
         const size_t want = (size_t)(n_frames + 2) * 1800 + 8192;          /* 1470 pairs per NTSC frame, 1764 per PAL frame, + what waited */
-        if (want > t->cap_chain_pairs) { const size_t c = want + want / 8; ST_GROW(t->d_chain_pairs, sdv_sample_pair, c); t->cap_chain_pairs = c; }
-        raw = t->d_chain_pairs; raw_cap = t->cap_chain_pairs;
+        RT_CHECK(t->d_chain_pairs.reserve(want, want + want / 8));
+        raw = t->d_chain_pairs; raw_cap = t->d_chain_pairs.cap;
     }
     int rc;
     size_t got_pairs = 0, got_frames = 0;
     if (pcm_type == SDV_PCM_STC007) {
-        sdv_line_rec *recs = (sdv_line_rec *)t->d_chain_recs;
+        sdv_line_rec *recs = (sdv_line_rec *)t->d_chain_recs.p;
         /* frames in the middle of a source: the records are n_frames runs of height + 3, the stitch stage need not look for the frame ends */
         StitchRegular reg; reg.recs_per_frame = (size_t)height + 3; reg.n_frames = (size_t)n_frames;
         const bool plain_frames = !(flags & (SDV_FLAG_NEW_FILE | SDV_FLAG_END_FILE)) && n_frames > 0 && n_recs == reg.recs_per_frame * reg.n_frames;
@@ -450,20 +440,17 @@ int sdv_decode_frames(sdv_engine *e, int pcm_type, const uint8_t *luma, size_t r
         }
         if (rc != SDV_OK && may_queue_ahead) (void)rt::ssync(s);
     } else if (pcm_type == SDV_PCM_PCM1) {
-        sdv_pcm1_bin_rec *recs = (sdv_pcm1_bin_rec *)t->d_chain_recs;
-        sdv_pcm1_line_rec *lines = (sdv_pcm1_line_rec *)(t->d_chain_recs + ((n_recs * sizeof(sdv_pcm1_bin_rec) + 255) & ~(size_t)255));
-        if (((n_recs * sizeof(sdv_pcm1_bin_rec) + 255) & ~(size_t)255) + n_recs * sizeof(sdv_pcm1_line_rec) > t->cap_chain_recs) {
-            const size_t c = ((n_recs * sizeof(sdv_pcm1_bin_rec) + 255) & ~(size_t)255) + n_recs * sizeof(sdv_pcm1_line_rec) + 4096;
-            ST_GROW(t->d_chain_recs, uint8_t, c); t->cap_chain_recs = c;
-            recs = (sdv_pcm1_bin_rec *)t->d_chain_recs; lines = (sdv_pcm1_line_rec *)(t->d_chain_recs + ((n_recs * sizeof(sdv_pcm1_bin_rec) + 255) & ~(size_t)255));
-        }
+        const size_t lines_ofs = (n_recs * sizeof(sdv_pcm1_bin_rec) + 255) & ~(size_t)255;
+        RT_CHECK(t->d_chain_recs.reserve(lines_ofs + n_recs * sizeof(sdv_pcm1_line_rec), lines_ofs + n_recs * sizeof(sdv_pcm1_line_rec) + 4096));
+        sdv_pcm1_bin_rec *recs = (sdv_pcm1_bin_rec *)t->d_chain_recs.p;
+        sdv_pcm1_line_rec *lines = (sdv_pcm1_line_rec *)(t->d_chain_recs + lines_ofs);
         rc = sdv_pcm1_binarize_frames(e, luma, row_stride, frame_stride, width, height, n_frames, first_frame_no, flags, recs, n_recs, stats, stats_room, stream);
         if (rc != SDV_OK) return rc;
         rc = sdv_pcm1_bin_to_line_recs(e, recs, n_recs, lines, stream);
         if (rc != SDV_OK) return rc;
         rc = sdv_pcm1_stitch_frames(e, lines, n_recs, raw, raw_cap, &got_pairs, (sdv_frame_asm_pcm1 *)out_frames, frames_cap, &got_frames, stream);
     } else {
-        sdv_pcm16x0_bin_rec *recs = (sdv_pcm16x0_bin_rec *)t->d_chain_recs;
+        sdv_pcm16x0_bin_rec *recs = (sdv_pcm16x0_bin_rec *)t->d_chain_recs.p;
         rc = sdv_pcm16x0_binarize_frames(e, luma, row_stride, frame_stride, width, height, n_frames, first_frame_no, flags, recs, n_recs, stats, stats_room, stream);
         if (rc != SDV_OK) return rc;
         rc = sdv_pcm16x0_stitch_frames(e, recs, n_recs, raw, raw_cap, &got_pairs, (sdv_frame_asm_pcm16x0 *)out_frames, frames_cap, &got_frames, stream);

@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 /* Developer aids (scheduler traces, cycle stamps, launch-shape overrides) are read from the environment only in builds made with
@@ -138,7 +139,8 @@ namespace rt {
 #ifndef SDV_EMU
 typedef hipStream_t stream_t;
 static inline const char *err_str(hipError_t e) { return hipGetErrorString(e); }
-#define RT_CHECK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error(e, std::string(#expr) + ": " + rt::err_str(_e)); return SDV_ERR_HIP; } } while (0)
+typedef hipError_t status_t;
+static const status_t OK = hipSuccess;
 static inline hipError_t dmalloc(void **p, size_t n) { return hipMalloc(p, n); }
 static inline hipError_t dfree(void *p) { return hipFree(p); }
 static inline hipError_t hpin(void **p, size_t n) { return hipHostMalloc(p, n, hipHostMallocDefault); }      /* page-locked host memory: copies into it are asynchronous */
@@ -247,11 +249,15 @@ static inline hipError_t launch_anchor(const sdv::AnchorArgs &a, stream_t s)
 }
 #else
 typedef void *stream_t;
-typedef int hipError_t_emu;
-#define RT_CHECK(expr) do { (void)(expr); } while (0)
-static inline int dmalloc(void **p, size_t n) { *p = malloc(n ? n : 1); return 0; }
+typedef int status_t;
+static const status_t OK = 0;
+static inline const char *err_str(int) { return "the emulated runtime refused"; }
+/* (tests: the fail_alloc_in-th allocation from now fails, once - sdv_emu_fail_alloc, tests/emu/emu_engine.cpp) */
+static int fail_alloc_in = 0;
+static inline int emu_alloc(void **p, size_t n) { if (fail_alloc_in > 0 && --fail_alloc_in == 0) { *p = NULL; return 1; } *p = malloc(n ? n : 1); return *p ? 0 : 1; }
+static inline int dmalloc(void **p, size_t n) { return emu_alloc(p, n); }
 static inline int dfree(void *p) { free(p); return 0; }
-static inline int hpin(void **p, size_t n) { *p = malloc(n ? n : 1); return 0; }
+static inline int hpin(void **p, size_t n) { return emu_alloc(p, n); }
 static inline int hunpin(void *p) { free(p); return 0; }
 static inline int h2d(void *d, const void *h, size_t n, stream_t) { memcpy(d, h, n); return 0; }
 static inline int d2h(void *h, const void *d, size_t n, stream_t) { memcpy(h, d, n); return 0; }
@@ -296,6 +302,37 @@ static inline int launch_hist_carry(const sdv::HistCarryArgs &a, stream_t) { for
 static inline int launch_ref_patch(const sdv::RefPatchArgs &a, stream_t) { for (int i = 0; i < a.n; i++) sdv::ref_patch_body(a, i); return 0; }
 static inline int launch_double(const sdv::DoubleArgs &a, stream_t) { for (size_t r = 0; r < a.rows; r++) for (int x4 = 0; 4 * x4 < a.width; x4++) sdv::double_body(a, r, x4); return 0; }
 #endif
+#define RT_CHECK(expr) do { rt::status_t _e = (expr); if (_e != rt::OK) { set_error(e, std::string(#expr) + ": " + rt::err_str(_e)); return SDV_ERR_HIP; } } while (0)
+
+/* Device memory (DevBuf) and page-locked host memory (PinBuf) of the engines: grow-only, counted in elements, freed by the destructor - which must run
+ * with the engine's device current (sdv_engine_destroy).  reserve(n) leaves a buffer of at least n elements whose old contents are gone; alloc_n is what
+ * a growing buffer asks the runtime for (the call site's growth rule).  After a failure the buffer is empty: p == NULL and cap == 0 always go together. */
+struct DevMem { static status_t get(void **p, size_t bytes) { return dmalloc(p, bytes); } static void put(void *p) { (void)dfree(p); } };
+struct PinMem { static status_t get(void **p, size_t bytes) { return hpin(p, bytes); } static void put(void *p) { (void)hunpin(p); } };
+template <typename T, typename Mem> struct Buf {
+    T *p = NULL; size_t cap = 0;
+    Buf() = default;
+    Buf(const Buf &) = delete;
+    Buf &operator=(const Buf &) = delete;
+    ~Buf() { release(); }
+    operator T *() const { return p; }
+    void release() { if (p) Mem::put(p); p = NULL; cap = 0; }
+    void swap(Buf &o) { std::swap(p, o.p); std::swap(cap, o.cap); }
+    status_t reserve(size_t n, size_t alloc_n = 0)
+    {
+        if (n <= cap) return OK;
+        if (alloc_n < n) alloc_n = n;
+        release();
+        const status_t st = Mem::get((void **)&p, alloc_n * sizeof(T));
+        if (st != OK) { p = NULL; return st; }
+        cap = alloc_n;
+        return OK;
+    }
+};
+template <typename T> using DevBuf = Buf<T, DevMem>;
+template <typename T> using PinBuf = Buf<T, PinMem>;
+/* buffers that grow by one rule, in one statement: the first failure ends it */
+template <typename... B> static inline status_t reserve_all(size_t n, size_t alloc_n, B &...b) { status_t st = OK; (void)(((st = b.reserve(n, alloc_n)) == OK) && ...); return st; }
 } // namespace rt
 
 /* Every entry point runs on its engine's device and leaves the caller's current device as it found it. */
@@ -333,66 +370,65 @@ static void pcm16_free(sdv_engine *e);
 static void audio_free(sdv_engine *e);
 static void vis_free(sdv_engine *e);
 struct sdv_engine {
-    int device;
+    int device = 0;
     std::string last_error;
-    sdv_bin_preset preset;
-    int mode;
-    int check_line_dup, coordinate_damper, m2_format;
-    sdv_v2d_state chain;            /* true state after the last decoded frame of the stream */
-    /* device scratch, grown on demand */
-    sdv_v2d_state *d_states_in, *d_states_out;
-    uint32_t *d_scratch;
-    uint8_t *h_flag;            /* page-locked mirror of d_flag (the round's read-back queues up behind the kernels) */
-    int *h_lists;               /* page-locked staging of the round's lists (lean, full, anchors, first_of, patches: n_frames ints each): copies out of it are queued, not waited for */
-    uint8_t *d_refs, *h_refs;       /* per frame: reference level in / out, history pushed (3 bytes) */
-    uint8_t *d_patched, *h_patched;                 /* per frame: the history carry gave it another start state (sdv_k_hist_carry) */
-    uint8_t *d_skip;                                /* per frame: this round need not decode it again (sdv_k_predict; FrameArgs::skip) */
-    uint8_t *d_line_done; size_t cap_line_done;     /* sdv_binarize_lines: per line, its record is final */
-    uint8_t *d_flag; int *d_first_of, *d_list_lean, *d_list_full, *d_anchors;   /* per frame, grown with d_states_*: flags; a round's lean and full lists (STC-007: both in d_list_lean);
+    sdv_bin_preset preset = {};
+    int mode = SDV_MODE_NORMAL;                 /* VideoToDigital ctor, videotodigital.cpp:16 */
+    int check_line_dup = 1, coordinate_damper = 1, m2_format = 0;
+    sdv_v2d_state chain = {};       /* true state after the last decoded frame of the stream */
+    /* device scratch, grown on demand (ensure_capacity: the per-frame buffers grow together) */
+    rt::DevBuf<sdv_v2d_state> d_states_in, d_states_out;
+    rt::DevBuf<uint32_t> d_scratch;
+    rt::PinBuf<uint8_t> h_flag;     /* page-locked mirror of d_flag (the round's read-back queues up behind the kernels) */
+    rt::PinBuf<int> h_lists;        /* page-locked staging of the round's lists (lean, full, anchors, first_of, patches: n_frames ints each): copies out of it are queued, not waited for */
+    rt::DevBuf<uint8_t> d_refs; rt::PinBuf<uint8_t> h_refs;             /* per frame: reference level in / out, history pushed (3 bytes) */
+    rt::DevBuf<uint8_t> d_patched; rt::PinBuf<uint8_t> h_patched;       /* per frame: the history carry gave it another start state (sdv_k_hist_carry) */
+    rt::DevBuf<uint8_t> d_skip;                     /* per frame: this round need not decode it again (sdv_k_predict; FrameArgs::skip) */
+    rt::DevBuf<uint8_t> d_line_done;                /* sdv_binarize_lines: per line, its record is final */
+    rt::DevBuf<uint8_t> d_flag; rt::DevBuf<int> d_first_of, d_list_lean, d_list_full, d_anchors;   /* per frame: flags; a round's lean and full lists (STC-007: both in d_list_lean);
                                      * its anchors, level patches and first_of (STC-007: all three in d_anchors; d_first_of and d_list_full: the PCM-1 / PCM-16x0 frame drivers') */
-    size_t cap_frames, cap_scratch;
     /* reference-level sweeps off the frame kernel (stc007_sweep_device.h): pool of requests / outcomes, list head per frame, count; per-level records of a chunk of sweeps */
-    sdv::SweepMemo *d_memo; int32_t *d_memo_head, *d_memo_count; size_t cap_memo, cap_memo_head;
-    sdv::SweepEnt *d_sweep_levels; size_t cap_sweep_levels;
-    unsigned long long *d_bw_memo; size_t cap_bw_memo;      /* per line of the batch: what findBlackWhite found there (stc007_device.h, find_black_white) */
+    rt::DevBuf<sdv::SweepMemo> d_memo; rt::DevBuf<int32_t> d_memo_head, d_memo_count;
+    rt::DevBuf<sdv::SweepEnt> d_sweep_levels;       /* (256 records per sweep of a chunk) */
+    rt::DevBuf<unsigned long long> d_bw_memo;       /* per line of the batch: what findBlackWhite found there (stc007_device.h, find_black_white) */
     /* trajectory snapshots of the general kernel (stc007_device.h, TcSnap): per frame two sets of snapshots, a header, a second list of coordinate keys */
-    sdv::TcSnap *d_tc_snaps; uint32_t *d_tc_hdr, *d_tc_keys; size_t cap_tc_frames, cap_tc_keys;
+    rt::DevBuf<sdv::TcSnap> d_tc_snaps; rt::DevBuf<uint32_t> d_tc_hdr, d_tc_keys;
     /* sdv_set_frame_flags: the marks of the next frame entry call (host copy) and their device buffer */
-    std::vector<uint8_t> frame_flags; bool frame_flags_pending; uint8_t *d_frame_flags; size_t cap_frame_flags;
+    std::vector<uint8_t> frame_flags; bool frame_flags_pending = false; rt::DevBuf<uint8_t> d_frame_flags;
     /* statistics of the last call */
-    sdv_run_info info;
-    int profiling;
+    sdv_run_info info = {};
+    int profiling = 0;
 #ifndef SDV_EMU
-    rt::BounceSlot bounce;          /* page-locked staging of the small synchronous read-backs (rt::d2h) */
+    rt::BounceSlot bounce = { NULL, false };        /* page-locked staging of the small synchronous read-backs (rt::d2h) */
 #endif
-    bool worn_tape;                 /* most frames of the last sdv_binarize_frames call took lines through the general path */
+    bool worn_tape = false;         /* most frames of the last sdv_binarize_frames call took lines through the general path */
     /* ... and hardly any of their decodes met the frame's last pass (a tape whose damage re-tunes the binarizer for good every few dozen lines): the general
      * kernel's build without the snapshots is a sixth faster there (stc007_device.h, kMeet).  Looked at again with the snapshots every eighth call. */
-    bool plain_general; unsigned plain_calls;
+    bool plain_general = false; unsigned plain_calls = 0;
     /* set by sdv_decode_frames for the one sdv_binarize_frames call it makes next (taken and cleared there): the stitcher's field buffers, for the frames the
      * whole-frame capture takes from end to end (FrameArgs::direct_fields) */
-    void *direct_fields; sdv::DirectFrame *direct_frames; int direct_seg_ofs, direct_pitch, direct_lines;
-    sdv_stitcher *stitch;
-    sdv_pcm1_stitcher *pcm1;
+    void *direct_fields = NULL; sdv::DirectFrame *direct_frames = NULL; int direct_seg_ofs = 0, direct_pitch = 0, direct_lines = 0;
+    sdv_stitcher *stitch = NULL;
+    sdv_pcm1_stitcher *pcm1 = NULL;
     /* PCM-16x0 streams: their chain state is longer (pcm16_frames_device.h, State16) */
-    sdvp16f::State16 chain16;
-    sdvp16f::State16 *d_states16_in, *d_states16_out; size_t cap_states16;
-    void *d_prescan16; size_t cap_prescan16;
-    uint8_t *d_sticky16; size_t cap_sticky16;     /* per repaired frame: which model (PCM-1 and PCM-16x0 frame drivers) */
-    sdv_pcm16_stitcher *pcm16;
-    sdv_audio *audio;
-    sdv_vis *vis;
+    sdvp16f::State16 chain16 = {};
+    rt::DevBuf<sdvp16f::State16> d_states16_in, d_states16_out;
+    rt::DevBuf<uint8_t> d_prescan16;                /* prescan results of the PCM-16x0 frame driver, a median per frame behind them (pcm16_frames_engine.inc) */
+    rt::DevBuf<uint8_t> d_sticky16;                 /* per repaired frame: which model (PCM-1 and PCM-16x0 frame drivers) */
+    sdv_pcm16_stitcher *pcm16 = NULL;
+    sdv_audio *audio = NULL;
+    sdv_vis *vis = NULL;
 #ifndef SDV_EMU
     hipEvent_t ev0, ev1;
-    bool have_events;
-    hipEvent_t ev_mark; bool have_mark;      /* behind the first round's read-back of sdv_binarize_frames when work of the next stage is queued behind it */
+    bool have_events = false;
+    hipEvent_t ev_mark; bool have_mark = false;     /* behind the first round's read-back of sdv_binarize_frames when work of the next stage is queued behind it */
 #endif
     /* the fused entry (sdv_decode_frames): device work of the stage behind, queued right behind the first round of the next sdv_binarize_frames call - a tape
      * that plays settles in that round, and the stage behind need not wait for the host to have seen that.  One call only; returns SDV_OK or an error. */
-    int (*after_first_round)(void *ctx); void *after_ctx;
-    bool binarize_settled_at_once;      /* the last sdv_binarize_frames call of the fused entry needed one round */
+    int (*after_first_round)(void *ctx) = NULL; void *after_ctx = NULL;
+    bool binarize_settled_at_once = false;      /* the last sdv_binarize_frames call of the fused entry needed one round */
 #ifdef SDV_DEV_AIDS
-    uint32_t dev_counts[16];            /* developer builds: the launches of the last sdv_binarize_frames / sdv_binarize_lines call, by build (DevCount) */
+    uint32_t dev_counts[16] = {};            /* developer builds: the launches of the last sdv_binarize_frames / sdv_binarize_lines call, by build (DevCount) */
 #endif
 };
 
@@ -448,30 +484,8 @@ sdv_engine *sdv_engine_create(int device)
     sdv_engine *e = new sdv_engine();
     e->device = device;
     sdv_default_bin_preset(&e->preset);
-    e->mode = SDV_MODE_NORMAL;                 /* VideoToDigital ctor, videotodigital.cpp:16 */
-    e->check_line_dup = 1; e->coordinate_damper = 1; e->m2_format = 0;
     chain_reset(&e->chain);
-    memset(&e->chain16, 0, sizeof(e->chain16)); chain_reset(&e->chain16.s);
-    e->d_states16_in = e->d_states16_out = NULL; e->cap_states16 = 0; e->d_prescan16 = NULL; e->cap_prescan16 = 0; e->pcm16 = NULL; e->audio = NULL; e->vis = NULL; e->d_sticky16 = NULL; e->cap_sticky16 = 0;
-    e->d_states_in = e->d_states_out = NULL; e->d_scratch = NULL;
-    e->h_flag = NULL; e->h_lists = NULL; e->d_refs = e->h_refs = NULL; e->d_patched = e->h_patched = NULL; e->d_skip = NULL; e->d_line_done = NULL; e->cap_line_done = 0;
-    e->d_flag = NULL; e->d_first_of = e->d_list_lean = e->d_list_full = e->d_anchors = NULL;
-    e->cap_frames = e->cap_scratch = 0;
-    e->d_memo = NULL; e->d_memo_head = e->d_memo_count = NULL; e->cap_memo = e->cap_memo_head = 0; e->d_sweep_levels = NULL; e->cap_sweep_levels = 0; e->d_bw_memo = NULL; e->cap_bw_memo = 0;
-    e->d_tc_snaps = NULL; e->d_tc_hdr = e->d_tc_keys = NULL; e->cap_tc_frames = e->cap_tc_keys = 0;
-    e->frame_flags_pending = false; e->d_frame_flags = NULL; e->cap_frame_flags = 0;
-    memset(&e->info, 0, sizeof(e->info));
-    e->profiling = 0; e->worn_tape = false; e->plain_general = false; e->plain_calls = 0;
-    e->direct_fields = NULL; e->direct_frames = NULL; e->direct_seg_ofs = 0; e->direct_pitch = 0; e->direct_lines = 0;
-#ifndef SDV_EMU
-    e->bounce.p = NULL; e->bounce.tried = false;
-#endif
-    e->stitch = NULL; e->pcm1 = NULL;
-#ifndef SDV_EMU
-    e->have_events = false; e->have_mark = false;
-#endif
-    e->after_first_round = NULL; e->after_ctx = NULL; e->binarize_settled_at_once = false;
-    dev_reset_counts(e);
+    chain_reset(&e->chain16.s);
     return e;
 }
 
@@ -484,32 +498,14 @@ void sdv_engine_destroy(sdv_engine *e)
     pcm16_free(e);
     audio_free(e);
     vis_free(e);
-    if (e->d_states16_in) rt::dfree(e->d_states16_in);
-    if (e->d_states16_out) rt::dfree(e->d_states16_out);
-    if (e->d_prescan16) rt::dfree(e->d_prescan16);
-    if (e->d_sticky16) rt::dfree(e->d_sticky16);
-    if (e->d_states_in) rt::dfree(e->d_states_in);
-    if (e->d_states_out) rt::dfree(e->d_states_out);
-    if (e->d_scratch) rt::dfree(e->d_scratch);
-    if (e->d_frame_flags) rt::dfree(e->d_frame_flags);
-    { void *ptrs[] = { e->d_memo, e->d_memo_head, e->d_memo_count, e->d_sweep_levels, e->d_bw_memo, e->d_tc_snaps, e->d_tc_hdr, e->d_tc_keys }; for (void *p : ptrs) if (p) rt::dfree(p); }
 #ifndef SDV_EMU
     if (e->bounce.p) (void)hipHostFree(e->bounce.p);
 #endif
-    if (e->h_flag) (void)rt::hunpin(e->h_flag);
-    if (e->h_lists) (void)rt::hunpin(e->h_lists);
-    if (e->h_refs) (void)rt::hunpin(e->h_refs);
-    if (e->d_refs) rt::dfree(e->d_refs);
-    if (e->d_patched) rt::dfree(e->d_patched);
-    if (e->d_skip) rt::dfree(e->d_skip);
-    if (e->d_line_done) rt::dfree(e->d_line_done);
-    if (e->h_patched) (void)rt::hunpin(e->h_patched);
-    { void *ptrs[] = { e->d_flag, e->d_first_of, e->d_list_lean, e->d_list_full, e->d_anchors }; for (void *p : ptrs) if (p) rt::dfree(p); }
 #ifndef SDV_EMU
     if (e->have_events) { (void)hipEventDestroy(e->ev0); (void)hipEventDestroy(e->ev1); }
     if (e->have_mark) (void)hipEventDestroy(e->ev_mark);
 #endif
-    delete e;
+    delete e;       /* (frees the buffers: the guard above is still in place) */
 }
 
 const char *sdv_last_error(const sdv_engine *e) { return e ? e->last_error.c_str() : g_last_error.c_str(); }
@@ -623,12 +619,7 @@ static int take_frame_flags(sdv_engine *e, size_t n_frames, rt::stream_t s, cons
     bool any = false;
     for (size_t i = 0; i < n_frames; i++) any = any || e->frame_flags[i] != 0;
     if (!any) return SDV_OK;
-    if (n_frames > e->cap_frame_flags) {
-        if (e->d_frame_flags) rt::dfree(e->d_frame_flags);
-        e->d_frame_flags = NULL; e->cap_frame_flags = 0;
-        RT_CHECK(rt::dmalloc((void **)&e->d_frame_flags, n_frames + 64));
-        e->cap_frame_flags = n_frames;
-    }
+    RT_CHECK(e->d_frame_flags.reserve(n_frames + 64));
     RT_CHECK(rt::h2d(e->d_frame_flags, e->frame_flags.data(), n_frames, s));
     *out = e->d_frame_flags;
     return SDV_OK;
@@ -642,40 +633,17 @@ static inline size_t flag_block_bytes(size_t n_frames) { return flag_tail_ofs(n_
 
 static int ensure_capacity(sdv_engine *e, size_t n_frames, size_t height)
 {
-    if (n_frames > e->cap_frames) {
-        if (e->d_states_in) rt::dfree(e->d_states_in);
-        if (e->d_states_out) rt::dfree(e->d_states_out);
-        e->d_states_in = e->d_states_out = NULL; e->cap_frames = 0;
-        RT_CHECK(rt::dmalloc((void **)&e->d_states_in, n_frames * sizeof(sdv_v2d_state)));
-        RT_CHECK(rt::dmalloc((void **)&e->d_states_out, n_frames * sizeof(sdv_v2d_state)));
-        { void *ptrs[] = { e->d_flag, e->d_first_of, e->d_list_lean, e->d_list_full, e->d_anchors }; for (void *p : ptrs) if (p) rt::dfree(p); }
-        e->d_flag = NULL; e->d_first_of = e->d_list_lean = e->d_list_full = e->d_anchors = NULL;
-        RT_CHECK(rt::dmalloc((void **)&e->d_flag, flag_block_bytes(n_frames)));      /* flags, then a copy of the last frame's outgoing state and the count of sweep requests, then the give-up signatures */
-        if (e->h_flag) { RT_CHECK(rt::hunpin(e->h_flag)); e->h_flag = NULL; }
-        if (e->h_lists) { RT_CHECK(rt::hunpin(e->h_lists)); e->h_lists = NULL; }
-        if (e->h_refs) { RT_CHECK(rt::hunpin(e->h_refs)); e->h_refs = NULL; }
-        if (e->d_refs) { rt::dfree(e->d_refs); e->d_refs = NULL; }
-        RT_CHECK(rt::dmalloc((void **)&e->d_refs, 3 * n_frames)); RT_CHECK(rt::hpin((void **)&e->h_refs, 3 * n_frames));
-        if (e->d_patched) { rt::dfree(e->d_patched); e->d_patched = NULL; }
-        if (e->h_patched) { RT_CHECK(rt::hunpin(e->h_patched)); e->h_patched = NULL; }
-        RT_CHECK(rt::dmalloc((void **)&e->d_patched, n_frames)); RT_CHECK(rt::hpin((void **)&e->h_patched, n_frames));
-        if (e->d_skip) { rt::dfree(e->d_skip); e->d_skip = NULL; }
-        RT_CHECK(rt::dmalloc((void **)&e->d_skip, n_frames));
-        RT_CHECK(rt::hpin((void **)&e->h_flag, flag_block_bytes(n_frames)));
-        RT_CHECK(rt::hpin((void **)&e->h_lists, 5 * n_frames * sizeof(int)));
-        RT_CHECK(rt::dmalloc((void **)&e->d_first_of, n_frames * sizeof(int)));
-        RT_CHECK(rt::dmalloc((void **)&e->d_list_full, n_frames * sizeof(int)));
-        RT_CHECK(rt::dmalloc((void **)&e->d_list_lean, 2 * n_frames * sizeof(int)));       /* the lean list, the full list behind it: one copy per round (their staging slots lie side by side) */
-        RT_CHECK(rt::dmalloc((void **)&e->d_anchors, 3 * n_frames * sizeof(int)));      /* anchors, patches and first_of of a round travel in one copy (their three staging slots lie side by side) */
-        e->cap_frames = n_frames;
-    }
-    size_t need = n_frames * 2 * height;
-    if (need > e->cap_scratch) {
-        if (e->d_scratch) rt::dfree(e->d_scratch);
-        e->d_scratch = NULL; e->cap_scratch = 0;
-        RT_CHECK(rt::dmalloc((void **)&e->d_scratch, need * sizeof(uint32_t)));
-        e->cap_scratch = need;
-    }
+    RT_CHECK(rt::reserve_all(n_frames, n_frames, e->d_states_in, e->d_states_out));
+    RT_CHECK(e->d_flag.reserve(flag_block_bytes(n_frames)));      /* flags, then a copy of the last frame's outgoing state and the count of sweep requests, then the give-up signatures */
+    RT_CHECK(e->d_refs.reserve(3 * n_frames)); RT_CHECK(e->h_refs.reserve(3 * n_frames));
+    RT_CHECK(e->d_patched.reserve(n_frames)); RT_CHECK(e->h_patched.reserve(n_frames));
+    RT_CHECK(e->d_skip.reserve(n_frames));
+    RT_CHECK(e->h_flag.reserve(flag_block_bytes(n_frames)));
+    RT_CHECK(e->h_lists.reserve(5 * n_frames));
+    RT_CHECK(rt::reserve_all(n_frames, n_frames, e->d_first_of, e->d_list_full));
+    RT_CHECK(e->d_list_lean.reserve(2 * n_frames));     /* the lean list, the full list behind it: one copy per round (their staging slots lie side by side) */
+    RT_CHECK(e->d_anchors.reserve(3 * n_frames));       /* anchors, patches and first_of of a round travel in one copy (their three staging slots lie side by side) */
+    RT_CHECK(e->d_scratch.reserve(n_frames * 2 * height));
     return SDV_OK;
 }
 
@@ -685,44 +653,32 @@ static int ensure_capacity(sdv_engine *e, size_t n_frames, size_t height)
  * (12 bytes per video line: about 59 MB for 10 000 NTSC frames). */
 static int ensure_memo_capacity(sdv_engine *e, size_t n_frames, size_t height, bool with_snapshots = true)
 {
-    if (n_frames * height > e->cap_memo_head || !e->d_memo_count) {
-        if (e->d_memo_head) rt::dfree(e->d_memo_head);
-        e->d_memo_head = NULL; e->cap_memo_head = 0;
-        RT_CHECK(rt::dmalloc((void **)&e->d_memo_head, n_frames * height * sizeof(int32_t)));
-        e->cap_memo_head = n_frames * height;
-        if (!e->d_memo_count) RT_CHECK(rt::dmalloc((void **)&e->d_memo_count, 16));
-    }
-    if (n_frames * 16 + 4096 > e->cap_memo) {
-        if (e->d_memo) rt::dfree(e->d_memo);
-        e->d_memo = NULL; e->cap_memo = 0;
-        RT_CHECK(rt::dmalloc((void **)&e->d_memo, (n_frames * 16 + 4096) * sizeof(sdv::SweepMemo)));
-        e->cap_memo = n_frames * 16 + 4096;
-    }
-    if (!e->d_sweep_levels) {
-        RT_CHECK(rt::dmalloc((void **)&e->d_sweep_levels, (size_t)1024 * 256 * sizeof(sdv::SweepEnt)));
-        e->cap_sweep_levels = 1024;
-    }
-    if (n_frames * height > e->cap_bw_memo) {
-        if (e->d_bw_memo) rt::dfree(e->d_bw_memo);
-        e->d_bw_memo = NULL; e->cap_bw_memo = 0;
-        RT_CHECK(rt::dmalloc((void **)&e->d_bw_memo, n_frames * height * sizeof(unsigned long long)));
-        e->cap_bw_memo = n_frames * height;
-    }
+    RT_CHECK(e->d_memo_head.reserve(n_frames * height));
+    RT_CHECK(e->d_memo_count.reserve(4));
+    RT_CHECK(e->d_memo.reserve(n_frames * 16 + 4096));
+    RT_CHECK(e->d_sweep_levels.reserve((size_t)1024 * 256));
+    RT_CHECK(e->d_bw_memo.reserve(n_frames * height));
     /* the snapshots: 16 KB per frame (two sets of 64 entries of 128 bytes) - left out for calls whose frames would need more than 4 GB of them */
     if (!with_snapshots) return SDV_OK;
-    if (n_frames > e->cap_tc_frames && n_frames * 2 * sdv::TC_ENTRIES * sizeof(sdv::TcSnap) <= ((size_t)4 << 30)) {
-        if (e->d_tc_snaps) rt::dfree(e->d_tc_snaps);
-        if (e->d_tc_hdr) rt::dfree(e->d_tc_hdr);
-        e->d_tc_snaps = NULL; e->d_tc_hdr = NULL; e->cap_tc_frames = 0;
-        RT_CHECK(rt::dmalloc((void **)&e->d_tc_snaps, n_frames * 2 * sdv::TC_ENTRIES * sizeof(sdv::TcSnap)));
-        RT_CHECK(rt::dmalloc((void **)&e->d_tc_hdr, n_frames * 2 * sizeof(uint32_t)));
-        e->cap_tc_frames = n_frames;
+    if (n_frames * 2 * sdv::TC_ENTRIES * sizeof(sdv::TcSnap) <= ((size_t)4 << 30)) {
+        RT_CHECK(e->d_tc_snaps.reserve(n_frames * 2 * sdv::TC_ENTRIES));
+        RT_CHECK(e->d_tc_hdr.reserve(n_frames * 2));
     }
-    if (n_frames * 2 * height > e->cap_tc_keys) {
-        if (e->d_tc_keys) rt::dfree(e->d_tc_keys);
-        e->d_tc_keys = NULL; e->cap_tc_keys = 0;
-        RT_CHECK(rt::dmalloc((void **)&e->d_tc_keys, n_frames * 2 * height * sizeof(uint32_t)));
-        e->cap_tc_keys = n_frames * 2 * height;
+    RT_CHECK(e->d_tc_keys.reserve(n_frames * 2 * height));
+    return SDV_OK;
+}
+
+/* Settle the requests [lo, hi) of the sweep pool, a chunk at a time; sa holds the video and the settings.  The per-level records have room for the 1024
+ * sweeps of a tape with a dropout now and then; a chunk that is larger gets room for a whole chunk, once. */
+static int settle_sweep_chunks(sdv_engine *e, sdv::SweepArgs sa, int lo, int hi, rt::stream_t s)
+{
+    enum { CHUNK = 16384 };
+    for (; lo < hi; lo += CHUNK) {
+        const int cnt = hi - lo < CHUNK ? hi - lo : CHUNK;
+        RT_CHECK(e->d_sweep_levels.reserve((size_t)cnt * 256, (size_t)CHUNK * 256));
+        sa.memo = e->d_memo; sa.first = lo; sa.count = cnt; sa.levels = e->d_sweep_levels;
+        RT_CHECK(rt::launch_sweeps(sa, s));
+        dev_count(e, DEV_SWEEP_LEVELS, (size_t)cnt); dev_count(e, DEV_SWEEP_PICK, (size_t)cnt);
     }
     return SDV_OK;
 }
@@ -816,59 +772,47 @@ int sdv_binarize_frames(sdv_engine *e, const uint8_t *luma, size_t row_stride, s
         RT_CHECK(rt::dfill_bytes(e->d_bw_memo, 0, (size_t)n * (size_t)height * sizeof(unsigned long long), s));
         a.bw_memo = e->d_bw_memo;
         const bool plain_now = e->plain_general && (e->plain_calls % 8u) != 7u;
-        if ((size_t)n <= e->cap_tc_frames && !dev_env("SDV_NO_TC") && !plain_now) {
+        if ((size_t)n * 2 * sdv::TC_ENTRIES <= e->d_tc_snaps.cap && !dev_env("SDV_NO_TC") && !plain_now) {
             RT_CHECK(rt::dfill_bytes(e->d_tc_hdr, 0, (size_t)n * 2 * sizeof(uint32_t), s));        /* no frame has a complete pass yet */
             a.tc_snaps = e->d_tc_snaps; a.tc_hdr = e->d_tc_hdr; a.tc_keys = e->d_tc_keys;
         }
-        a.memo = e->d_memo; a.memo_head = e->d_memo_head; a.memo_count = d_count; a.memo_cap = (int32_t)e->cap_memo;
+        a.memo = e->d_memo; a.memo_head = e->d_memo_head; a.memo_count = d_count; a.memo_cap = (int32_t)e->d_memo.cap;
         memo_ready = true; memo_done = 0;
         return SDV_OK;
     };
     /* settle what the last round asked for; count = requests handed out so far (read back with the flags) */
     auto settle_sweeps = [&](int count) -> int {
         if (!memo_ready) return SDV_OK;
-        const int cap = (int)e->cap_memo, have = count < cap ? count : cap;
+        const int cap = (int)e->d_memo.cap, have = count < cap ? count : cap;
         sweeps_seen = count;
         if (round_fat) {            /* settled where they were asked for */
             round_fat = false;
             if (have > memo_done) { e->info.sweeps += (uint32_t)(have - memo_done); memo_done = have; }
         }
-        enum { CHUNK = 16384 };
-        for (int lo = memo_done; lo < have; lo += CHUNK) {
-            const int cnt = have - lo < CHUNK ? have - lo : CHUNK;
-            if ((size_t)cnt > e->cap_sweep_levels) {        /* more than the 1024 of a tape with a dropout now and then: room for a whole chunk, once */
-                if (e->d_sweep_levels) rt::dfree(e->d_sweep_levels);
-                e->d_sweep_levels = NULL; e->cap_sweep_levels = 0;
-                RT_CHECK(rt::dmalloc((void **)&e->d_sweep_levels, (size_t)CHUNK * 256 * sizeof(sdv::SweepEnt)));
-                e->cap_sweep_levels = CHUNK;
-            }
+        if (have > memo_done) {
             sdv::SweepArgs sa;
             memset(&sa, 0, sizeof(sa));
             sa.luma = a.luma; sa.frame_stride = a.frame_stride; sa.row_stride = a.row_stride; sa.width = a.width;
             sa.doubled = a.doubled; sa.mode = a.mode; sa.preset = a.preset;
-            sa.memo = e->d_memo; sa.first = lo; sa.count = cnt; sa.levels = e->d_sweep_levels;
-            RT_CHECK(rt::launch_sweeps(sa, s));
-            dev_count(e, DEV_SWEEP_LEVELS, (size_t)cnt); dev_count(e, DEV_SWEEP_PICK, (size_t)cnt);
-            e->info.sweeps += (uint32_t)cnt;
+            { const int src = settle_sweep_chunks(e, sa, memo_done, have, s); if (src != SDV_OK) return src; }
+            e->info.sweeps += (uint32_t)(have - memo_done);
         }
         memo_done = have;
         if (count > cap) {
             /* the pool ran over: the requests that did not fit were dropped (their frames come again and ask again) - a bigger pool for them */
-            const size_t want = (size_t)count + (size_t)count / 2 + 4096;
-            sdv::SweepMemo *bigger = NULL;
-            RT_CHECK(rt::dmalloc((void **)&bigger, want * sizeof(sdv::SweepMemo)));
+            rt::DevBuf<sdv::SweepMemo> bigger;      /* (the one buffer that grows with its contents; an early return frees it) */
+            RT_CHECK(bigger.reserve((size_t)count + (size_t)count / 2 + 4096));
             RT_CHECK(rt::d2d(bigger, e->d_memo, (size_t)cap * sizeof(sdv::SweepMemo), s));
 #ifndef SDV_EMU
             RT_CHECK(hipStreamSynchronize(s));
 #endif
-            rt::dfree(e->d_memo);
-            e->d_memo = bigger; e->cap_memo = want;
+            e->d_memo.swap(bigger);
             const int32_t c32 = cap;
             RT_CHECK(rt::h2d(d_count, &c32, sizeof(c32), s));
 #ifndef SDV_EMU
             RT_CHECK(hipStreamSynchronize(s));      /* (the copy's source is on this stack frame) */
 #endif
-            a.memo = e->d_memo; a.memo_cap = (int32_t)e->cap_memo;
+            a.memo = e->d_memo; a.memo_cap = (int32_t)e->d_memo.cap;
         }
         return SDV_OK;
     };
@@ -912,7 +856,7 @@ int sdv_binarize_frames(sdv_engine *e, const uint8_t *luma, size_t row_stride, s
                 /* A small round on a tape whose lines ask for sweeps: the kernel that settles them while the frame waits (sdv_k_stc007_frames_fat) - no round
                  * for the frame to come again with the outcome at hand.  (The first rounds of a damaged tape are not small, and their thousands of sweeps are
                  * better settled all at once: the machine is full of them.) */
-                const bool fat = memo_ready && sweeps_seen > 0 && list_full.size() <= (e->cap_sweep_levels < 512 ? e->cap_sweep_levels : (size_t)512) && !dev_env("SDV_NO_FAT");
+                const bool fat = memo_ready && sweeps_seen > 0 && list_full.size() <= (e->d_sweep_levels.cap / 256 < 512 ? e->d_sweep_levels.cap / 256 : (size_t)512) && !dev_env("SDV_NO_FAT");
                 if (fat) { a.fat_levels = e->d_sweep_levels; round_fat = true; }
                 dev_count_frames(e, a, false, (int)list_full.size());
                 RT_CHECK(rt::launch_frames(a, s, false, (int)list_full.size()));
@@ -1206,7 +1150,7 @@ int sdv_binarize_frames(sdv_engine *e, const uint8_t *luma, size_t row_stride, s
         pa.skip = NULL;
         if (any_moved && !anchors.empty() && !dev_env("SDV_SCHED_NO_CARRY")) {     /* the history moves on (sdv_k_hist_carry): frames it reaches are decoded in this round too */
             RT_CHECK(rt::dfill_bytes(e->d_patched + first, 0, (size_t)(hi - first), s));
-            sdv::HistCarryArgs ha; ha.states_in = e->d_states_in; ha.refs = e->d_refs; ha.anchors = d_anch; ha.n_anchors = (int)anchors.size(); ha.hi = hi; ha.patched = e->d_patched; ha.skip = use_skip ? e->d_skip : NULL;
+            sdv::HistCarryArgs ha; ha.states_in = e->d_states_in; ha.refs = e->d_refs; ha.anchors = d_anch; ha.n_anchors = (int)anchors.size(); ha.hi = hi; ha.patched = e->d_patched; ha.skip = use_skip ? e->d_skip.p : NULL;
             RT_CHECK(rt::launch_hist_carry(ha, s));
             RT_CHECK(rt::d2h_pinned(e->h_patched + first, e->d_patched + first, (size_t)(hi - first), s));
             size_t reached = 0;
@@ -1218,7 +1162,7 @@ int sdv_binarize_frames(sdv_engine *e, const uint8_t *luma, size_t row_stride, s
                 }
             if (trace) fprintf(stderr, "[sched]   the history moved on into %zu more frames\n", reached);
         }
-        a.skip = use_skip ? e->d_skip : NULL;
+        a.skip = use_skip ? e->d_skip.p : NULL;
         if (!any_hard && contiguous) rc = run_round(run_lo, run_hi, true, false);
         else rc = run_round(0, 0, false, false);
         a.skip = NULL;
@@ -1264,12 +1208,7 @@ int sdv_binarize_lines(sdv_engine *e, const uint8_t *luma, size_t row_stride, in
     rt::stream_t s = (rt::stream_t)stream;
     SDV_ON_DEVICE(e);
     { const int mrc = ensure_memo_capacity(e, (n_lines + 15) / 16 + 1, 16, false); if (mrc != SDV_OK) return mrc; }       /* a list head per line, an entry per line and to spare */
-    if (n_lines > e->cap_line_done) {
-        if (e->d_line_done) rt::dfree(e->d_line_done);
-        e->d_line_done = NULL; e->cap_line_done = 0;
-        RT_CHECK(rt::dmalloc((void **)&e->d_line_done, n_lines + n_lines / 8 + 64));
-        e->cap_line_done = n_lines + n_lines / 8 + 64;
-    }
+    RT_CHECK(e->d_line_done.reserve(n_lines, n_lines + n_lines / 8 + 64));
     RT_CHECK(rt::dfill_bytes(e->d_line_done, 0, n_lines, s));
     RT_CHECK(rt::dfill_bytes(e->d_memo_head, 0xFF, n_lines * sizeof(int32_t), s));
     RT_CHECK(rt::dfill_bytes(e->d_memo_count, 0, 16, s));
@@ -1279,7 +1218,7 @@ int sdv_binarize_lines(sdv_engine *e, const uint8_t *luma, size_t row_stride, in
     a.frame_number = frame_number; a.first_line = first_line; a.line_step = line_step;
     a.doubled = (flags & SDV_FLAG_DOUBLED) ? 1 : 0; a.mode = (uint8_t)e->mode; a.preset = e->preset;
     a.out = out_lines; a.done = e->d_line_done;
-    a.memo = e->d_memo; a.memo_head = e->d_memo_head; a.memo_count = e->d_memo_count; a.memo_cap = (int32_t)e->cap_memo;
+    a.memo = e->d_memo; a.memo_head = e->d_memo_head; a.memo_count = e->d_memo_count; a.memo_cap = (int32_t)e->d_memo.cap;
     dev_reset_counts(e);
     int settled = 0;
     for (int pass = 0;; pass++) {
@@ -1289,25 +1228,13 @@ int sdv_binarize_lines(sdv_engine *e, const uint8_t *luma, size_t row_stride, in
         int32_t count = 0;
         RT_CHECK(rt::d2h(&count, e->d_memo_count, sizeof(count), s));
         /* (the pool holds a request per line and more: a line asks for one sweep at most - one that did not fit would leave its line waiting for good) */
-        if (count > (int32_t)e->cap_memo) { set_error(e, "the pool of sweep requests ran over: " + std::to_string(count) + " requests, room for " + std::to_string(e->cap_memo)); return SDV_ERR_HIP; }
+        if (count > (int32_t)e->d_memo.cap) { set_error(e, "the pool of sweep requests ran over: " + std::to_string(count) + " requests, room for " + std::to_string(e->d_memo.cap)); return SDV_ERR_HIP; }
         if (count <= settled) break;
-        enum { CHUNK = 16384 };
-        for (int lo = settled; lo < count; lo += CHUNK) {
-            const int cnt = count - lo < CHUNK ? count - lo : CHUNK;
-            if ((size_t)cnt > e->cap_sweep_levels) {
-                if (e->d_sweep_levels) rt::dfree(e->d_sweep_levels);
-                e->d_sweep_levels = NULL; e->cap_sweep_levels = 0;
-                RT_CHECK(rt::dmalloc((void **)&e->d_sweep_levels, (size_t)CHUNK * 256 * sizeof(sdv::SweepEnt)));
-                e->cap_sweep_levels = CHUNK;
-            }
-            sdv::SweepArgs sa;
-            memset(&sa, 0, sizeof(sa));
-            sa.luma = luma; sa.frame_stride = (size_t)sdv::LINES_PER_MEMO_FRAME * row_stride; sa.row_stride = row_stride; sa.width = width;
-            sa.doubled = a.doubled; sa.mode = a.mode; sa.preset = a.preset;
-            sa.memo = e->d_memo; sa.first = lo; sa.count = cnt; sa.levels = e->d_sweep_levels;
-            dev_count(e, DEV_SWEEP_LEVELS, (size_t)cnt); dev_count(e, DEV_SWEEP_PICK, (size_t)cnt);
-            RT_CHECK(rt::launch_sweeps(sa, s));
-        }
+        sdv::SweepArgs sa;
+        memset(&sa, 0, sizeof(sa));
+        sa.luma = luma; sa.frame_stride = (size_t)sdv::LINES_PER_MEMO_FRAME * row_stride; sa.row_stride = row_stride; sa.width = width;
+        sa.doubled = a.doubled; sa.mode = a.mode; sa.preset = a.preset;
+        { const int src = settle_sweep_chunks(e, sa, settled, count, s); if (src != SDV_OK) return src; }
         settled = count;
     }
     /* every line's record is final: a line still waiting for a sweep holds a placeholder record, and the call says so instead of handing it out */

@@ -41,18 +41,19 @@ struct side_t { int dummy; };
 
 struct sdv_pcm16_stitcher {
     sdv_pcm16x0_stitch_settings st;
-    sdv_pcm16x0_bin_rec *d_carry; size_t n_carry, cap_carry;
-    sdv_pcm16x0_bin_rec *d_carry_spare; size_t cap_carry_spare;
-    uint32_t *d_blk_count, *d_blk_ofs; size_t cap_blk;
-    uint8_t *d_svc; size_t cap_svc;
-    uint32_t *d_seg_end, *d_marks, *d_frasm_ofs, *d_vblk_ofs; uint64_t *d_pair_ofs; size_t cap_seg;
-    uint32_t *d_stat;
-    sdv_pcm16x0_bin_rec *vis_lines; size_t vis_lines_cap, vis_lines_n; uint32_t *d_vline_ofs, *d_field_src; size_t cap_field_src;       /* ... and its assembled sub-lines */
+    /* (made by new sdv_pcm16_stitcher(): everything that is not a buffer starts as zero) */
+    rt::DevBuf<sdv_pcm16x0_bin_rec> d_carry; size_t n_carry;
+    rt::DevBuf<sdv_pcm16x0_bin_rec> d_carry_spare;
+    rt::DevBuf<uint32_t> d_blk_count, d_blk_ofs;
+    rt::DevBuf<uint8_t> d_svc;
+    rt::DevBuf<uint32_t> d_seg_end, d_marks, d_frasm_ofs, d_vblk_ofs; rt::DevBuf<uint64_t> d_pair_ofs;
+    rt::DevBuf<uint32_t> d_stat;
+    sdv_pcm16x0_bin_rec *vis_lines; size_t vis_lines_cap, vis_lines_n; rt::DevBuf<uint32_t> d_vline_ofs, d_field_src;       /* ... and its assembled sub-lines */
     sdv_pcm16x0_block_rec *vis_blocks; size_t vis_blocks_cap, vis_blocks_n;       /* the visualiser's feed (caller's buffer) and what the last call made of it */
-    sdvp16::State16 *d_state;               /* [0] the stream's state, [1] its copy at the start of the running call */
+    rt::DevBuf<sdvp16::State16> d_state;               /* [0] the stream's state, [1] its copy at the start of the running call */
     bool state_valid;
-    sdvp16::Sub *d_rem, *d_rem_slots; size_t cap_rem_slots;       /* conv_queue's remainder: behind the last call (FRAME_SUBS entries) / behind every batch of the running call */
-    sdvp16::Ana16 *d_ana; sdvp16::Pick16 *d_pick; sdvp16::Choice16 *d_choice; sdvp16::Dec16 *d_dec; sdvp16::Ctrl16 *d_ctrl; sdvp16::Sub *d_fields; size_t cap_batch;
+    rt::DevBuf<sdvp16::Sub> d_rem, d_rem_slots;       /* conv_queue's remainder: behind the last call (FRAME_SUBS entries) / behind every batch of the running call */
+    rt::DevBuf<sdvp16::Ana16> d_ana; rt::DevBuf<sdvp16::Pick16> d_pick; rt::DevBuf<sdvp16::Choice16> d_choice; rt::DevBuf<sdvp16::Dec16> d_dec; rt::DevBuf<sdvp16::Ctrl16> d_ctrl; rt::DevBuf<sdvp16::Sub> d_fields;
     rt16::side_t side;              /* a second stream for the analysis kernels, which run ahead of the in-order decisions (product build only) */
 };
 #ifndef SDV_P16_ANA_BATCHES
@@ -67,7 +68,6 @@ static sdv_pcm16_stitcher *pcm16_get(sdv_engine *e)
 {
     if (e->pcm16) return e->pcm16;
     sdv_pcm16_stitcher *t = new sdv_pcm16_stitcher();
-    memset(t, 0, sizeof(*t));
     sdv_default_pcm16x0_stitch_settings(&t->st);
     e->pcm16 = t;
     return t;
@@ -76,11 +76,8 @@ static void pcm16_free(sdv_engine *e)
 {
     sdv_pcm16_stitcher *t = e->pcm16;
     if (!t) return;
-    void *ptrs[] = { t->d_carry, t->d_carry_spare, t->d_blk_count, t->d_blk_ofs, t->d_seg_end, t->d_marks, t->d_frasm_ofs, t->d_vblk_ofs, t->d_vline_ofs, t->d_field_src, t->d_pair_ofs, t->d_stat, t->d_svc,
-                     t->d_state, t->d_rem, t->d_rem_slots, t->d_ana, t->d_pick, t->d_choice, t->d_dec, t->d_ctrl, t->d_fields };
-    for (void *p : ptrs) if (p) rt::dfree(p);
 #ifndef SDV_EMU
-    rt16::side_free(t->side);
+    rt16::side_free(t->side);       /* (waits for the side streams: the buffers go after that) */
 #endif
     delete t;
     e->pcm16 = NULL;
@@ -152,8 +149,8 @@ int sdv_set_pcm16x0_stitch_state(sdv_engine *e, const void *in, size_t n)
     SDV_ON_DEVICE(e);
     sdv_pcm16_stitcher *t = pcm16_get(e);
     if (b->st.rem_n >= (uint32_t)sdvp16::FRAME_SUBS) { set_error(e, "not a PCM-16x0 stitch state"); return SDV_ERR_BAD_ARG; }
-    if (!t->d_state) RT_CHECK(rt::dmalloc((void **)&t->d_state, 2 * sizeof(sdvp16::State16)));
-    if (!t->d_rem) RT_CHECK(rt::dmalloc((void **)&t->d_rem, sdvp16::FRAME_SUBS * sizeof(sdvp16::Sub)));
+    RT_CHECK(t->d_state.reserve(2));
+    RT_CHECK(t->d_rem.reserve(sdvp16::FRAME_SUBS));
     RT_CHECK(rt::h2d(t->d_state, &b->st, sizeof(b->st), (rt::stream_t)0));
     RT_CHECK(rt::h2d(t->d_rem, b->rem, sizeof(b->rem), (rt::stream_t)0));
     RT_CHECK(rt::ssync((rt::stream_t)0));
@@ -209,10 +206,10 @@ int sdv_pcm16x0_stitch_frames(sdv_engine *e, const sdv_pcm16x0_bin_rec *lines, s
 
     /* 1. frame segments: positions of the END_FRAME records */
     const size_t nblk = (total + sdvp16::SEG_CHUNK16 - 1) / sdvp16::SEG_CHUNK16;
-    if (nblk > t->cap_blk) { ST_GROW(t->d_blk_count, uint32_t, nblk); ST_GROW(t->d_blk_ofs, uint32_t, nblk); t->cap_blk = nblk; }
-    if (!t->d_stat) RT_CHECK(rt::dmalloc((void **)&t->d_stat, 8 * sizeof(uint32_t)));
-    if (!t->d_state) { RT_CHECK(rt::dmalloc((void **)&t->d_state, 2 * sizeof(sdvp16::State16))); t->state_valid = false; }
-    if (!t->d_rem) RT_CHECK(rt::dmalloc((void **)&t->d_rem, sdvp16::FRAME_SUBS * sizeof(sdvp16::Sub)));
+    RT_CHECK(rt::reserve_all(nblk, nblk, t->d_blk_count, t->d_blk_ofs));
+    RT_CHECK(t->d_stat.reserve(8));
+    if (!t->d_state) { RT_CHECK(t->d_state.reserve(2)); t->state_valid = false; }
+    RT_CHECK(t->d_rem.reserve(sdvp16::FRAME_SUBS));
     if (!t->state_valid) {      /* resetState (:64-85) */
         sdvp16::State16 st0;
         p16_state_fresh(&st0);
@@ -220,7 +217,7 @@ int sdv_pcm16x0_stitch_frames(sdv_engine *e, const sdv_pcm16x0_bin_rec *lines, s
         RT_CHECK(rt::ssync(s));
         t->state_valid = true;
     }
-    if (total > t->cap_svc) { const size_t c = total + total / 4 + 4096; ST_GROW(t->d_svc, uint8_t, c); t->cap_svc = c; }
+    RT_CHECK(t->d_svc.reserve(total, total + total / 4 + 4096));
     sdvp16::SegArgs16 sa; sa.src = src; sa.n_recs = (uint32_t)total; sa.svc = t->d_svc; sa.block_count = t->d_blk_count; sa.block_ofs = t->d_blk_ofs;
     sa.seg_end = NULL; sa.n_seg = 0; sa.marks = NULL; sa.stat = t->d_stat; sa.write = 0;
     RT_LAUNCH64(sdv_k_pcm16_segments, nblk, sa, s);
@@ -230,11 +227,7 @@ int sdv_pcm16x0_stitch_frames(sdv_engine *e, const sdv_pcm16x0_bin_rec *lines, s
     for (size_t i = 0; i < nblk; i++) { uint32_t c = blk[i]; blk[i] = (uint32_t)n_seg; n_seg += c; }
     uint32_t last_end = 0;
     if (n_seg > 0) {
-        if (n_seg + 1 > t->cap_seg) {
-            const size_t c = n_seg + 1 + n_seg / 8 + 16;
-            ST_GROW(t->d_seg_end, uint32_t, c); ST_GROW(t->d_marks, uint32_t, c); ST_GROW(t->d_frasm_ofs, uint32_t, c); ST_GROW(t->d_vblk_ofs, uint32_t, c); ST_GROW(t->d_vline_ofs, uint32_t, c); ST_GROW(t->d_pair_ofs, uint64_t, c);
-            t->cap_seg = c;
-        }
+        RT_CHECK(rt::reserve_all(n_seg + 1, n_seg + 1 + n_seg / 8 + 16, t->d_seg_end, t->d_marks, t->d_frasm_ofs, t->d_vblk_ofs, t->d_vline_ofs, t->d_pair_ofs));
         RT_CHECK(rt::h2d(t->d_blk_ofs, blk.data(), nblk * sizeof(uint32_t), s));
         const uint32_t stat0[4] = { 0, 0xFFFFFFFFu, 0, 0 };
         RT_CHECK(rt::h2d(t->d_stat, stat0, sizeof(stat0), s));
@@ -260,22 +253,19 @@ int sdv_pcm16x0_stitch_frames(sdv_engine *e, const sdv_pcm16x0_bin_rec *lines, s
         /* 3. the frames, a batch at a time; the buffers hold every batch of the call so that the analysis can run ahead */
         const size_t batch = n_seg < (size_t)SDV_P16_STITCH_BATCH ? n_seg : (size_t)SDV_P16_STITCH_BATCH;
         const size_t n_batches = (n_seg + batch - 1) / batch;
-        if (n_seg > t->cap_batch) {
-            const size_t c = n_seg + n_seg / 8 + 16;
-            ST_GROW(t->d_ana, sdvp16::Ana16, c); ST_GROW(t->d_pick, sdvp16::Pick16, c); ST_GROW(t->d_choice, sdvp16::Choice16, c); ST_GROW(t->d_dec, sdvp16::Dec16, c); ST_GROW(t->d_ctrl, sdvp16::Ctrl16, c);
-            ST_GROW(t->d_fields, sdvp16::Sub, c * 2 * sdvp16::SUBLINES_PF);
-            t->cap_batch = c;
-        }
-        if (t->vis_lines && n_seg > t->cap_field_src) { const size_t c = n_seg + n_seg / 8 + 16; ST_GROW(t->d_field_src, uint32_t, c * 2 * sdvp16::SUBLINES_PF); t->cap_field_src = c; }
-        if (n_batches > t->cap_rem_slots) { ST_GROW(t->d_rem_slots, sdvp16::Sub, n_batches * sdvp16::FRAME_SUBS); t->cap_rem_slots = n_batches; }
+        const size_t c = n_seg + n_seg / 8 + 16, per_frame = 2 * sdvp16::SUBLINES_PF;
+        RT_CHECK(rt::reserve_all(n_seg, c, t->d_ana, t->d_pick, t->d_choice, t->d_dec, t->d_ctrl));
+        RT_CHECK(t->d_fields.reserve(n_seg * per_frame, c * per_frame));
+        if (t->vis_lines) RT_CHECK(t->d_field_src.reserve(n_seg * per_frame, c * per_frame));
+        RT_CHECK(t->d_rem_slots.reserve(n_batches * sdvp16::FRAME_SUBS));
         RT_CHECK(rt::d2d(t->d_state + 1, t->d_state, sizeof(sdvp16::State16), s));
         sdvp16::FrameArgs16s fa; fa.src = src; fa.seg_end = t->d_seg_end; fa.n_seg = (uint32_t)n_seg;
         fa.cfg.format = t->st.format; fa.cfg.field_order = t->st.field_order; fa.cfg.p_correction = t->st.p_correction; fa.cfg.ignore_crc = t->st.use_ecc == 0;
         fa.cfg.mask_seams = t->st.mask_seams; fa.cfg.broke_mask = t->st.broke_mask; fa.cfg.sample_rate_preset = t->st.sample_rate_preset;
         fa.marks = t->d_marks; fa.pair_ofs = t->d_pair_ofs; fa.frasm_ofs = t->d_frasm_ofs;
-        fa.vblk_ofs = t->vis_blocks ? t->d_vblk_ofs : NULL; fa.out_blocks = t->vis_blocks; fa.blocks_cap = t->vis_blocks_cap;
-        fa.vline_ofs = t->vis_lines ? t->d_vline_ofs : NULL; fa.out_lines = t->vis_lines; fa.lines_cap = t->vis_lines_cap; fa.field_src = NULL;
-        fa.state = t->d_state; fa.state_snap = hint_on ? t->d_state : NULL;      /* (the analysis reads the history as it stands while it runs: a hint, checked by what it is used for) */
+        fa.vblk_ofs = t->vis_blocks ? t->d_vblk_ofs.p : NULL; fa.out_blocks = t->vis_blocks; fa.blocks_cap = t->vis_blocks_cap;
+        fa.vline_ofs = t->vis_lines ? t->d_vline_ofs.p : NULL; fa.out_lines = t->vis_lines; fa.lines_cap = t->vis_lines_cap; fa.field_src = NULL;
+        fa.state = t->d_state; fa.state_snap = hint_on ? t->d_state.p : NULL;      /* (the analysis reads the history as it stands while it runs: a hint, checked by what it is used for) */
         fa.out_pairs = out_pairs; fa.pairs_cap = pairs_cap; fa.out_frames = out_frames; fa.frames_cap = (uint32_t)(frames_cap > 0xFFFFFFFFu ? 0xFFFFFFFFu : frames_cap);
         fa.stat = t->d_stat;
         auto point_at = [&](size_t b0) {
@@ -407,19 +397,13 @@ int sdv_pcm16x0_stitch_frames(sdv_engine *e, const sdv_pcm16x0_bin_rec *lines, s
     }
     const size_t keep_from = n_seg > 0 ? (size_t)last_end + 1 : 0, n_keep = total - keep_from;
     if (n_keep > 0) {
-        if (n_keep > t->cap_carry_spare) {
-            if (t->d_carry_spare) rt::dfree(t->d_carry_spare);
-            t->d_carry_spare = NULL; t->cap_carry_spare = 0;
-            const size_t cap = n_keep + n_keep / 2 + 1024;
-            RT_CHECK(rt::dmalloc((void **)&t->d_carry_spare, cap * sizeof(sdv_pcm16x0_bin_rec)));
-            t->cap_carry_spare = cap;
-        }
+        RT_CHECK(t->d_carry_spare.reserve(n_keep, n_keep + n_keep / 2 + 1024));
         size_t w = 0;
         if (keep_from < t->n_carry) { RT_CHECK(rt::d2d(t->d_carry_spare, t->d_carry + keep_from, (t->n_carry - keep_from) * sizeof(sdv_pcm16x0_bin_rec), s)); w = t->n_carry - keep_from; }
         const size_t from_lines = keep_from > t->n_carry ? keep_from - t->n_carry : 0;
         if (from_lines < n_lines) RT_CHECK(rt::d2d(t->d_carry_spare + w, lines + from_lines, (n_lines - from_lines) * sizeof(sdv_pcm16x0_bin_rec), s));
         RT_CHECK(rt::ssync(s));
-        std::swap(t->d_carry, t->d_carry_spare); std::swap(t->cap_carry, t->cap_carry_spare);
+        t->d_carry.swap(t->d_carry_spare);
     }
     t->n_carry = n_keep;
     return SDV_OK;

@@ -31,20 +31,9 @@ extern "C" int sdv_pcm16x0_binarize_frames(sdv_engine *e, const uint8_t *luma, s
     const int n = n_frames;
     int rc = ensure_capacity(e, (size_t)n, (size_t)height * 3);          /* coordinate lists: three sub-lines per line */
     if (rc != SDV_OK) return rc;
-    if ((size_t)n > e->cap_states16) {
-        if (e->d_states16_in) rt::dfree(e->d_states16_in);
-        if (e->d_states16_out) rt::dfree(e->d_states16_out);
-        e->d_states16_in = e->d_states16_out = NULL; e->cap_states16 = 0;
-        RT_CHECK(rt::dmalloc((void **)&e->d_states16_in, (size_t)n * sizeof(sdvp16f::State16)));
-        RT_CHECK(rt::dmalloc((void **)&e->d_states16_out, (size_t)n * sizeof(sdvp16f::State16)));
-        e->cap_states16 = (size_t)n;
-    }
-    if ((size_t)n > e->cap_prescan16) {
-        if (e->d_prescan16) rt::dfree(e->d_prescan16);
-        e->d_prescan16 = NULL; e->cap_prescan16 = 0;
-        RT_CHECK(rt::dmalloc((void **)&e->d_prescan16, (size_t)n * (2 * sdvp16f::COORD_CHECK_LINES * sizeof(sdvp1f::PrescanRes) + sizeof(uint2))));      /* two variants of every prescan line (pcm1_frames_device.h, PrescanRes) */
-        e->cap_prescan16 = (size_t)n;
-    }
+    RT_CHECK(rt::reserve_all((size_t)n, (size_t)n, e->d_states16_in, e->d_states16_out));
+    const size_t prescan_bytes = 2 * sdvp16f::COORD_CHECK_LINES * sizeof(sdvp1f::PrescanRes) + sizeof(uint2);     /* per frame: two variants of every prescan line (pcm1_frames_device.h, PrescanRes), a median */
+    RT_CHECK(e->d_prescan16.reserve((size_t)n * prescan_bytes));
 
     sdvp16f::FrameArgs16 a;
     memset(&a, 0, sizeof(a));
@@ -58,8 +47,8 @@ extern "C" int sdv_pcm16x0_binarize_frames(sdv_engine *e, const uint8_t *luma, s
     a.f.stats = out_stats; a.f.scratch = e->d_scratch; a.f.flag = e->d_flag; a.f.n_total = n;
     rc = take_frame_flags(e, (size_t)n, s, &a.f.frame_flags); if (rc != SDV_OK) return rc;
     a.states_in = e->d_states16_in; a.states_out = e->d_states16_out;
-    a.recs16 = out_lines; a.prescan = (sdvp1f::PrescanRes *)e->d_prescan16;
-    a.frame_med = (uint2 *)((sdvp1f::PrescanRes *)e->d_prescan16 + (size_t)e->cap_prescan16 * 2 * sdvp16f::COORD_CHECK_LINES);    /* behind the prescan results */
+    a.recs16 = out_lines; a.prescan = (sdvp1f::PrescanRes *)e->d_prescan16.p;
+    a.frame_med = (uint2 *)(a.prescan + e->d_prescan16.cap / prescan_bytes * 2 * sdvp16f::COORD_CHECK_LINES);    /* behind the prescan results of all the frames the buffer has room for */
 
     memset(&e->info, 0, sizeof(e->info));
     e->info.frames = (uint32_t)n;
@@ -141,12 +130,7 @@ extern "C" int sdv_pcm16x0_binarize_frames(sdv_engine *e, const uint8_t *luma, s
         head_of.insert(head_of.end(), others_head.begin(), others_head.end());
         sticky.assign(list.size(), 0);
         for (size_t i = (size_t)n_heads; i < list.size(); i++) sticky[i] = predicted_again[(size_t)list[i]] == 1;       /* the model has its say once */
-        if (list.size() > e->cap_sticky16) {
-            if (e->d_sticky16) rt::dfree(e->d_sticky16);
-            e->d_sticky16 = NULL; e->cap_sticky16 = 0;
-            RT_CHECK(rt::dmalloc((void **)&e->d_sticky16, (size_t)n));
-            e->cap_sticky16 = (size_t)n;
-        }
+        RT_CHECK(e->d_sticky16.reserve(list.size(), (size_t)n));
         RT_CHECK(rt::h2d(e->d_sticky16, sticky.data(), sticky.size(), s));
         RT_CHECK(rt::h2d(e->d_list_full, list.data(), list.size() * sizeof(int), s));
         RT_CHECK(rt::h2d(e->d_first_of, head_of.data(), head_of.size() * sizeof(int), s));

@@ -6,16 +6,17 @@
  */
 struct sdv_pcm1_stitcher {
     sdv_pcm1_stitch_settings st;
-    sdv_pcm1_line_rec *d_carry; size_t n_carry, cap_carry;
-    sdv_pcm1_line_rec *d_carry_spare; size_t cap_carry_spare;
-    uint32_t *d_blk_count, *d_blk_ofs; size_t cap_blk;
-    uint8_t *d_svc; size_t cap_svc;
-    uint32_t *d_seg_end, *d_marks, *d_frasm_ofs; uint64_t *d_pair_ofs; size_t cap_seg;
-    uint32_t *d_stat;
-    int *d_line_list; size_t cap_line_list;      /* PCM-1 line kernel: lines the lean kernel handed on, behind two counters */
-    void *d_prescan; size_t cap_prescan;         /* PCM-1 frame driver: prescan results, four per frame (pcm1_frames_device.h) */
+    /* (made by new sdv_pcm1_stitcher(): everything that is not a buffer starts as zero) */
+    rt::DevBuf<sdv_pcm1_line_rec> d_carry; size_t n_carry;
+    rt::DevBuf<sdv_pcm1_line_rec> d_carry_spare;
+    rt::DevBuf<uint32_t> d_blk_count, d_blk_ofs;
+    rt::DevBuf<uint8_t> d_svc;
+    rt::DevBuf<uint32_t> d_seg_end, d_marks, d_frasm_ofs; rt::DevBuf<uint64_t> d_pair_ofs;
+    rt::DevBuf<uint32_t> d_stat;
+    rt::DevBuf<int> d_line_list;                /* PCM-1 line kernel: lines the lean kernel handed on, behind two counters */
+    rt::DevBuf<uint8_t> d_prescan;              /* PCM-1 frame driver: prescan results, four per frame, a median per frame behind them (pcm1_frames_engine.inc) */
     /* manual line offsets: the field buffers outlive a frame (pcm1_stitch_device.h, FrameArgs1) */
-    uint32_t *d_cnt, *d_kept; size_t cap_cnt; void *d_hist; bool hist_ready;
+    rt::DevBuf<uint32_t> d_cnt, d_kept; rt::DevBuf<sdvp1::Line16> d_hist; bool hist_ready;
     /* the visualiser's feeds (caller's buffers) and what the last call made of them */
     sdv_pcm1_block_rec *vis_blocks; size_t vis_blocks_cap, vis_blocks_n; sdv_pcm1_asm_line_rec *vis_lines; size_t vis_lines_cap, vis_lines_n;
 };
@@ -25,7 +26,6 @@ static sdv_pcm1_stitcher *pcm1_get(sdv_engine *e)
 {
     if (e->pcm1) return e->pcm1;
     sdv_pcm1_stitcher *t = new sdv_pcm1_stitcher();
-    memset(t, 0, sizeof(*t));
     sdv_default_pcm1_stitch_settings(&t->st);
     e->pcm1 = t;
     return t;
@@ -34,8 +34,6 @@ static void pcm1_free(sdv_engine *e)
 {
     sdv_pcm1_stitcher *t = e->pcm1;
     if (!t) return;
-    void *ptrs[] = { t->d_carry, t->d_carry_spare, t->d_blk_count, t->d_blk_ofs, t->d_seg_end, t->d_marks, t->d_frasm_ofs, t->d_pair_ofs, t->d_stat, t->d_svc, t->d_line_list, t->d_prescan, t->d_cnt, t->d_kept, t->d_hist };
-    for (void *p : ptrs) if (p) rt::dfree(p);
     delete t;
     e->pcm1 = NULL;
 }
@@ -74,9 +72,9 @@ int sdv_pcm1_stitch_frames(sdv_engine *e, const sdv_pcm1_line_rec *lines, size_t
 
     /* 1. frame segments: positions of the END_FRAME records */
     const size_t nblk = (total + sdvp1::SEG_CHUNK1 - 1) / sdvp1::SEG_CHUNK1;
-    if (nblk > t->cap_blk) { ST_GROW(t->d_blk_count, uint32_t, nblk); ST_GROW(t->d_blk_ofs, uint32_t, nblk); t->cap_blk = nblk; }
-    if (!t->d_stat) RT_CHECK(rt::dmalloc((void **)&t->d_stat, 8 * sizeof(uint32_t)));
-    if (total > t->cap_svc) { const size_t c = total + total / 4 + 4096; ST_GROW(t->d_svc, uint8_t, c); t->cap_svc = c; }
+    RT_CHECK(rt::reserve_all(nblk, nblk, t->d_blk_count, t->d_blk_ofs));
+    RT_CHECK(t->d_stat.reserve(8));
+    RT_CHECK(t->d_svc.reserve(total, total + total / 4 + 4096));
     sdvp1::SegArgs1 sa; sa.src = src; sa.n_recs = (uint32_t)total; sa.svc = t->d_svc; sa.block_count = t->d_blk_count; sa.block_ofs = t->d_blk_ofs;
     sa.seg_end = NULL; sa.n_seg = 0; sa.marks = NULL; sa.stat = t->d_stat; sa.write = 0;
     RT_LAUNCH64(sdv_k_pcm1_segments, nblk, sa, s);
@@ -86,11 +84,7 @@ int sdv_pcm1_stitch_frames(sdv_engine *e, const sdv_pcm1_line_rec *lines, size_t
     for (size_t i = 0; i < nblk; i++) { uint32_t c = blk[i]; blk[i] = (uint32_t)n_seg; n_seg += c; }
     uint32_t last_end = 0;
     if (n_seg > 0) {
-        if (n_seg + 1 > t->cap_seg) {
-            const size_t c = n_seg + 1 + n_seg / 8 + 16;
-            ST_GROW(t->d_seg_end, uint32_t, c); ST_GROW(t->d_marks, uint32_t, c); ST_GROW(t->d_frasm_ofs, uint32_t, c); ST_GROW(t->d_pair_ofs, uint64_t, c);
-            t->cap_seg = c;
-        }
+        RT_CHECK(rt::reserve_all(n_seg + 1, n_seg + 1 + n_seg / 8 + 16, t->d_seg_end, t->d_marks, t->d_frasm_ofs, t->d_pair_ofs));
         RT_CHECK(rt::h2d(t->d_blk_ofs, blk.data(), nblk * sizeof(uint32_t), s));
         const uint32_t stat0[4] = { 0, 0xFFFFFFFFu, 0, 0 };
         RT_CHECK(rt::h2d(t->d_stat, stat0, sizeof(stat0), s));
@@ -110,20 +104,17 @@ int sdv_pcm1_stitch_frames(sdv_engine *e, const sdv_pcm1_line_rec *lines, size_t
         fa.marks = t->d_marks; fa.pair_ofs = t->d_pair_ofs; fa.frasm_ofs = t->d_frasm_ofs;
         fa.out_pairs = out_pairs; fa.pairs_cap = pairs_cap; fa.out_frames = out_frames; fa.frames_cap = (uint32_t)(frames_cap > 0xFFFFFFFFu ? 0xFFFFFFFFu : frames_cap);
         fa.stat = t->d_stat;
-        unsigned long long *d_timing = NULL;
-        if (dev_env("SDV_STITCH_TIMING")) { RT_CHECK(rt::dmalloc((void **)&d_timing, n_seg * 8 * sizeof(unsigned long long))); RT_CHECK(rt::dzero(d_timing, n_seg * 8 * sizeof(unsigned long long), s)); }
+        rt::DevBuf<unsigned long long> d_timing;
+        if (dev_env("SDV_STITCH_TIMING")) { RT_CHECK(d_timing.reserve(n_seg * 8)); RT_CHECK(rt::dzero(d_timing, n_seg * 8 * sizeof(unsigned long long), s)); }
         fa.timing = d_timing;
         fa.cnt_out = NULL; fa.kept_out = NULL; fa.cnt_in = NULL; fa.kept_in = NULL; fa.hist = NULL;
         fa.out_blocks = t->vis_blocks; fa.blocks_cap = t->vis_blocks_cap; fa.out_asm = t->vis_lines; fa.asm_cap = t->vis_lines_cap;
         if (!t->st.auto_offset) {
             /* manual line offsets: a first pass leaves what every frame writes into the field buffers, the frames then look up what they are told to
              * read beyond that (pcm1_stitch_device.h) */
-            if (n_seg > t->cap_cnt) {
-                const size_t c = n_seg + n_seg / 8 + 16;
-                ST_GROW(t->d_cnt, uint32_t, c); ST_GROW(t->d_kept, uint32_t, c * 2 * sdvp1::LINES_PF);
-                t->cap_cnt = c;
-            }
-            if (!t->d_hist) RT_CHECK(rt::dmalloc(&t->d_hist, 2 * sdvp1::LINES_PF * sizeof(sdvp1::Line16)));
+            const size_t c = n_seg + n_seg / 8 + 16;
+            RT_CHECK(t->d_cnt.reserve(n_seg, c)); RT_CHECK(t->d_kept.reserve(n_seg * 2 * sdvp1::LINES_PF, c * 2 * sdvp1::LINES_PF));
+            RT_CHECK(t->d_hist.reserve(2 * sdvp1::LINES_PF));
             if (!t->hist_ready) { sdv_p1_hist_clear_args ha; ha.hist = t->d_hist; RT_LAUNCH64(sdv_k_pcm1_hist_clear, 1, ha, s); t->hist_ready = true; }
             fa.cnt_out = t->d_cnt; fa.kept_out = t->d_kept;
             RT_LAUNCH64(sdv_k_pcm1_frames, n_seg, fa, s);
@@ -137,7 +128,6 @@ int sdv_pcm1_stitch_frames(sdv_engine *e, const sdv_pcm1_line_rec *lines, size_t
             double acc[8] = { 0 };
             for (size_t k = 0; k < n_seg; k++) for (int i = 1; i < 7; i++) acc[i] += (double)(tm[k * 8 + i] - tm[k * 8 + i - 1]);
             fprintf(stderr, "[pcm1 timing] cycles/frame: sweep1 %.0f marks %.0f trim %.0f sweep2 %.0f pad %.0f masks %.0f blocks+pairs %.0f\n", acc[1] / n_seg, 0.0, acc[2] / n_seg, acc[3] / n_seg, acc[4] / n_seg, acc[5] / n_seg, acc[6] / n_seg);
-            rt::dfree(d_timing);
         }
     }
 
@@ -179,19 +169,13 @@ int sdv_pcm1_stitch_frames(sdv_engine *e, const sdv_pcm1_line_rec *lines, size_t
     }
     const size_t keep_from = n_seg > 0 ? (size_t)last_end + 1 : 0, n_keep = total - keep_from;
     if (n_keep > 0) {
-        if (n_keep > t->cap_carry_spare) {
-            if (t->d_carry_spare) rt::dfree(t->d_carry_spare);
-            t->d_carry_spare = NULL; t->cap_carry_spare = 0;
-            const size_t cap = n_keep + n_keep / 2 + 1024;
-            RT_CHECK(rt::dmalloc((void **)&t->d_carry_spare, cap * sizeof(sdv_pcm1_line_rec)));
-            t->cap_carry_spare = cap;
-        }
+        RT_CHECK(t->d_carry_spare.reserve(n_keep, n_keep + n_keep / 2 + 1024));
         size_t w = 0;
         if (keep_from < t->n_carry) { RT_CHECK(rt::d2d(t->d_carry_spare, t->d_carry + keep_from, (t->n_carry - keep_from) * sizeof(sdv_pcm1_line_rec), s)); w = t->n_carry - keep_from; }
         const size_t from_lines = keep_from > t->n_carry ? keep_from - t->n_carry : 0;
         if (from_lines < n_lines) RT_CHECK(rt::d2d(t->d_carry_spare + w, lines + from_lines, (n_lines - from_lines) * sizeof(sdv_pcm1_line_rec), s));
         RT_CHECK(rt::ssync(s));
-        std::swap(t->d_carry, t->d_carry_spare); std::swap(t->cap_carry, t->cap_carry_spare);
+        t->d_carry.swap(t->d_carry_spare);
     }
     t->n_carry = n_keep;
     return SDV_OK;
@@ -253,12 +237,7 @@ extern "C" int sdv_pcm1_binarize_lines(sdv_engine *e, const uint8_t *luma, size_
     if (presets) {
         /* lines that decode from their presets go through the lean kernel; the others end up on a list the full kernel works off */
         sdv_pcm1_stitcher *t = pcm1_get(e);
-        if (n_lines + 4 > t->cap_line_list) {
-            if (t->d_line_list) rt::dfree(t->d_line_list);
-            t->d_line_list = NULL; t->cap_line_list = 0;
-            RT_CHECK(rt::dmalloc((void **)&t->d_line_list, (n_lines + n_lines / 4 + 1024) * sizeof(int)));
-            t->cap_line_list = n_lines + n_lines / 4 + 1024;
-        }
+        RT_CHECK(t->d_line_list.reserve(n_lines + 4, n_lines + n_lines / 4 + 1024));
         a.counters = t->d_line_list; a.list = t->d_line_list + 4;
         RT_CHECK(rt::dzero(a.counters, 4 * sizeof(int), s));
         RT_LAUNCH64(sdv_k_pcm1_lines_lean, n_lines, a, s);

@@ -37,12 +37,8 @@ extern "C" int sdv_pcm1_binarize_frames(sdv_engine *e, const uint8_t *luma, size
     int rc = ensure_capacity(e, (size_t)n, (size_t)height);
     if (rc != SDV_OK) return rc;
     sdv_pcm1_stitcher *t = pcm1_get(e);
-    if ((size_t)n > t->cap_prescan) {
-        if (t->d_prescan) rt::dfree(t->d_prescan);
-        t->d_prescan = NULL; t->cap_prescan = 0;
-        RT_CHECK(rt::dmalloc((void **)&t->d_prescan, (size_t)n * (2 * sdvp1f::COORD_CHECK_LINES * sizeof(sdvp1f::PrescanRes) + sizeof(uint2))));     /* two variants of every prescan line (pcm1_frames_device.h, PrescanRes) */
-        t->cap_prescan = (size_t)n;
-    }
+    const size_t prescan_bytes = 2 * sdvp1f::COORD_CHECK_LINES * sizeof(sdvp1f::PrescanRes) + sizeof(uint2);      /* per frame: two variants of every prescan line (pcm1_frames_device.h, PrescanRes), a median */
+    RT_CHECK(t->d_prescan.reserve((size_t)n * prescan_bytes));
 
     sdvp1f::FrameArgs1 a;
     memset(&a, 0, sizeof(a));
@@ -56,8 +52,8 @@ extern "C" int sdv_pcm1_binarize_frames(sdv_engine *e, const uint8_t *luma, size
     a.f.states_in = e->d_states_in; a.f.states_out = e->d_states_out;
     a.f.stats = out_stats; a.f.scratch = e->d_scratch; a.f.flag = e->d_flag; a.f.n_total = n;
     rc = take_frame_flags(e, (size_t)n, s, &a.f.frame_flags); if (rc != SDV_OK) return rc;
-    a.recs1 = out_lines; a.prescan = (sdvp1f::PrescanRes *)t->d_prescan;
-    a.frame_med = (uint2 *)((sdvp1f::PrescanRes *)t->d_prescan + (size_t)t->cap_prescan * 2 * sdvp1f::COORD_CHECK_LINES);       /* behind the prescan results */
+    a.recs1 = out_lines; a.prescan = (sdvp1f::PrescanRes *)t->d_prescan.p;
+    a.frame_med = (uint2 *)(a.prescan + t->d_prescan.cap / prescan_bytes * 2 * sdvp1f::COORD_CHECK_LINES);       /* behind the prescan results of all the frames the buffer has room for */
 
     memset(&e->info, 0, sizeof(e->info));
     e->info.frames = (uint32_t)n;
@@ -140,12 +136,7 @@ extern "C" int sdv_pcm1_binarize_frames(sdv_engine *e, const uint8_t *luma, size
             RT_CHECK(rt::h2d(e->d_first_of, head_of.data(), head_of.size() * sizeof(int), s));
             std::vector<uint8_t> sticky(others.size());
             for (size_t i = 0; i < others.size(); i++) sticky[i] = predicted_again[(size_t)others[i]] == 1;       /* the model has its say once */
-            if (others.size() > e->cap_sticky16) {
-                if (e->d_sticky16) rt::dfree(e->d_sticky16);
-                e->d_sticky16 = NULL; e->cap_sticky16 = 0;
-                RT_CHECK(rt::dmalloc((void **)&e->d_sticky16, (size_t)n));
-                e->cap_sticky16 = (size_t)n;
-            }
+            RT_CHECK(e->d_sticky16.reserve(others.size(), (size_t)n));
             RT_CHECK(rt::h2d(e->d_sticky16, sticky.data(), sticky.size(), s));
             sdvp1f::RepairArgs1 ra; ra.p = pa; ra.states_out = e->d_states_out; ra.list = e->d_list_lean; ra.head = e->d_first_of; ra.sticky = e->d_sticky16; ra.n = (int)others.size(); ra.frame_med = a.frame_med;
 #ifndef SDV_EMU

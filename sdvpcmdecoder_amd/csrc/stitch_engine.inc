@@ -58,36 +58,39 @@ struct Ring {
 struct sdv_stitcher {
     sdv_stitch_settings st;
     sdvs::Ring ring_order, ring_res;
-    sdv_line_rec *d_carry; size_t n_carry, cap_carry;
-    sdv_line_rec *d_carry_spare; size_t cap_carry_spare;      /* the next call's carry is built here, then the two swap: no allocation per call */
-    sdvs::StepChain *d_chain0;
-    sdvs::StepChain *d_chain0_spare;     /* a pipelined call of known layout writes the next call's state here ahead of its read-back; swapped in when the call went as assumed */
+    /* (made by new sdv_stitcher(): everything that is not a buffer starts as zero) */
+    rt::DevBuf<sdv_line_rec> d_carry; size_t n_carry;
+    rt::DevBuf<sdv_line_rec> d_carry_spare;     /* the next call's carry is built here, then the two swap: no allocation per call */
+    rt::DevBuf<sdvs::StepChain> d_chain0;
+    rt::DevBuf<sdvs::StepChain> d_chain0_spare; /* a pipelined call of known layout writes the next call's state here ahead of its read-back; swapped in when the call went as assumed */
     /* scratch, grown on demand */
-    uint32_t *d_blk_count, *d_blk_ofs, *d_seg_end, *d_work, *d_frasm_ofs; size_t cap_blk, cap_seg;
-    uint8_t *d_svc; size_t cap_svc;         /* service type of every record of the call (segment passes) */
-    uint64_t *d_pair_ofs;
-    sdvs::FrameLocal *d_fl; sdvs::FrameBrief *d_brief; sdvs::StepChain *d_chain[2];
-    uint8_t *d_prob_order, *d_prob_res; sdvs::StepInfo *d_info;
-    sdvs::SLine *d_ws; size_t cap_ws;
-    sdvs::SLine *d_fields;
+    rt::DevBuf<uint32_t> d_blk_count, d_blk_ofs, d_work, d_frasm_ofs;
+    size_t seg_slots;           /* segments every per-segment buffer has room for, and the layout of d_back / h_back (stitch_grow_seg; 0 while they do not agree) */
+    uint32_t *d_seg_end;
+    rt::DevBuf<uint8_t> d_svc;              /* service type of every record of the call (segment passes) */
+    rt::DevBuf<uint64_t> d_pair_ofs;
+    rt::DevBuf<sdvs::FrameLocal> d_fl; sdvs::FrameBrief *d_brief; rt::DevBuf<sdvs::StepChain> d_chain[2];
+    rt::DevBuf<uint8_t> d_prob_order, d_prob_res; sdvs::StepInfo *d_info;
+    rt::DevBuf<sdvs::SLine> d_ws;
+    rt::DevBuf<sdvs::SLine> d_fields;
     size_t resident_waves;      /* waves of the turn kernel the device holds at once (0: not asked yet) */
     uint32_t *d_next_work;
     uint32_t guess_pairs, guess_frasm;      /* what every turn of the last call emitted, if they all emitted the same (0: unknown) */
     bool steady;                /* the stream's last turn left usable paddings and field order: later turns can be predicted from it */
-    sdv_sample_pair *d_pairs; sdv_frame_asm *d_frasm;
+    rt::DevBuf<sdv_sample_pair> d_pairs; rt::DevBuf<sdv_frame_asm> d_frasm;
     sdv_stitch_info info;
     /* sdv_set_stitch_block_output: where the data blocks go (the caller's buffer), how many the last call had */
-    sdv_block_rec *block_out; size_t block_cap, n_blocks; uint32_t *d_block_ofs; size_t cap_block_ofs;
+    sdv_block_rec *block_out; size_t block_cap, n_blocks; rt::DevBuf<uint32_t> d_block_ofs;
     /* sdv_set_stitch_line_output: the assembled lines; how many every turn of the last call had (host copy) */
-    sdv_asm_line_rec *line_out; size_t line_cap, n_asm_lines; uint32_t *d_asm_cnt, *d_asm_ofs; size_t cap_asm; std::vector<uint32_t> *asm_per_turn;
+    sdv_asm_line_rec *line_out; size_t line_cap, n_asm_lines; rt::DevBuf<uint32_t> d_asm_cnt, d_asm_ofs; std::vector<uint32_t> *asm_per_turn;
     /* the pipelined call of a stream that plays (sdv_stitch_frames, "1p"): what the last call saw, which the next one assumes */
     /* what the host reads of a call - control words, frame briefs, turn infos, segment ends - lies in one block on the device (d_ctl, d_brief, d_info and
      * d_seg_end point into d_back) and has a page-locked mirror of the same layout: one copy brings all of it */
-    uint8_t *d_back, *h_back; size_t cap_back;
+    rt::DevBuf<uint8_t> d_back; rt::PinBuf<uint8_t> h_back;
     int carry_frames;           /* what waits in d_carry: 0 nothing, 1 exactly one frame (its END_FRAME is the last record), -1 not known */
     uint32_t *d_ctl; double pipe_rps; uint8_t pipe_res, pipe_order; uint32_t pipe_skip, pipe_backoff;
     /* the fused entry: frames the frame kernel put into d_fields itself (stitch_prepare_direct; valid for the one stitch call behind the binarize call) */
-    sdv::DirectFrame *d_direct; size_t cap_direct; bool direct_armed; uint32_t direct_ofs, direct_n;
+    rt::DevBuf<sdv::DirectFrame> d_direct; bool direct_armed; uint32_t direct_ofs, direct_n;
     bool ahead_direct;          /* a call whose device work was queued ahead (STITCH_QUEUE_AHEAD): what direct_armed was then */
     bool direct_count_owed;     /* sdv_stitch_info::direct_frames of the last call is still to be counted from d_direct */
 };
@@ -114,7 +117,6 @@ static sdv_stitcher *stitcher_get(sdv_engine *e)
 {
     if (e->stitch) return e->stitch;
     sdv_stitcher *t = new sdv_stitcher();
-    memset(t, 0, sizeof(*t));
     sdv_default_stitch_settings(&t->st);
     stitcher_reset_host(t);
     e->stitch = t;
@@ -124,11 +126,7 @@ static void stitcher_free(sdv_engine *e)
 {
     sdv_stitcher *t = e->stitch;
     if (!t) return;
-    void *ptrs[] = { t->d_carry, t->d_carry_spare, t->d_chain0, t->d_chain0_spare, t->d_blk_count, t->d_blk_ofs, t->d_back, t->d_work, t->d_frasm_ofs, t->d_pair_ofs, t->d_fl,
-                     t->d_chain[0], t->d_chain[1], t->d_prob_order, t->d_prob_res, t->d_ws, t->d_pairs, t->d_frasm, t->d_fields, t->d_svc, t->d_block_ofs, t->d_asm_cnt, t->d_asm_ofs, t->d_direct };
     delete t->asm_per_turn;
-    if (t->h_back) (void)rt::hunpin(t->h_back);
-    for (void *p : ptrs) if (p) rt::dfree(p);
     delete t;
     e->stitch = NULL;
 }
@@ -211,7 +209,7 @@ int sdv_set_stitch_state(sdv_engine *e, const void *in, size_t n)
     t->ring_order.clear(); t->ring_res.clear();
     for (int i = 0; i < 65; i++) { t->ring_order.push(b->ring_order[i]); t->ring_res.push(b->ring_res[i]); }
     t->steady = b->steady != 0; t->n_carry = 0; t->carry_frames = 0; t->guess_pairs = t->guess_frasm = 0;
-    if (!t->d_chain0) RT_CHECK(rt::dmalloc((void **)&t->d_chain0, sizeof(sdvs::StepChain)));
+    RT_CHECK(t->d_chain0.reserve(1));
     RT_CHECK(rt::h2d(t->d_chain0, &b->chain, sizeof(sdvs::StepChain), (rt::stream_t)0));
     RT_CHECK(rt::ssync((rt::stream_t)0));
     return SDV_OK;
@@ -228,8 +226,6 @@ int sdv_saturate_stitch_stats(sdv_engine *e)
     t->ring_order.fill(o); t->ring_res.fill(r);
     return SDV_OK;
 }
-
-#define ST_GROW(ptr, type, count) do { if (ptr) rt::dfree(ptr); ptr = NULL; RT_CHECK(rt::dmalloc((void **)&(ptr), (size_t)(count) * sizeof(type))); } while (0)
 
 int sdv_set_stitch_block_output(sdv_engine *e, sdv_block_rec *out_blocks, size_t blocks_cap)
 {
@@ -259,24 +255,19 @@ size_t sdv_stitch_line_counts(sdv_engine *e, uint32_t *per_turn, size_t cap)
 } // extern "C"
 
 /* room for n_seg_need frame segments in every per-segment buffer of the stitch stage */
+static inline size_t stitch_back_bytes(size_t c) { return 64 + ((c * sizeof(uint32_t) + 63) & ~(size_t)63) + c * (sizeof(sdvs::FrameBrief) + sizeof(sdvs::StepInfo)); }
 static int stitch_grow_seg(sdv_engine *e, sdv_stitcher *t, size_t n_seg_need)
 {
-        if (n_seg_need + 1 > t->cap_seg) {
-            const size_t c = n_seg_need + 1 + n_seg_need / 8 + 16;         /* head room: the next call of a stream usually brings one frame more (the carried one) */
-            ST_GROW(t->d_work, uint32_t, c); ST_GROW(t->d_frasm_ofs, uint32_t, c); ST_GROW(t->d_pair_ofs, uint64_t, c);
-            ST_GROW(t->d_fl, sdvs::FrameLocal, c); ST_GROW(t->d_fields, sdvs::SLine, c * 2 * sdvs::FIELD_PITCH);
-            ST_GROW(t->d_chain[0], sdvs::StepChain, c); ST_GROW(t->d_chain[1], sdvs::StepChain, c);
-            ST_GROW(t->d_prob_order, uint8_t, c); ST_GROW(t->d_prob_res, uint8_t, c);
-            ST_GROW(t->d_pairs, sdv_sample_pair, c * sdvs::PAIR_SLOT); ST_GROW(t->d_frasm, sdv_frame_asm, c * sdvs::FRASM_SLOT);
-            const size_t back = 64 + ((c * sizeof(uint32_t) + 63) & ~(size_t)63) + c * (sizeof(sdvs::FrameBrief) + sizeof(sdvs::StepInfo));
-            ST_GROW(t->d_back, uint8_t, back);
-            if (t->h_back) { RT_CHECK(rt::hunpin(t->h_back)); t->h_back = NULL; }
-            RT_CHECK(rt::hpin((void **)&t->h_back, back)); t->cap_back = back;
-            t->d_ctl = (uint32_t *)t->d_back; t->d_next_work = t->d_ctl + sdvs::CTL_NEXT; t->d_seg_end = (uint32_t *)(t->d_back + 64);
-            t->d_brief = (sdvs::FrameBrief *)(t->d_back + 64 + ((c * sizeof(uint32_t) + 63) & ~(size_t)63)); t->d_info = (sdvs::StepInfo *)(t->d_brief + c);
-            t->cap_seg = c;
-        }
-        return SDV_OK;
+    if (n_seg_need + 1 <= t->seg_slots) return SDV_OK;
+    const size_t c = n_seg_need + 1 + n_seg_need / 8 + 16;         /* head room: the next call of a stream usually brings one frame more (the carried one) */
+    t->seg_slots = 0;
+    RT_CHECK(rt::reserve_all(c, c, t->d_work, t->d_frasm_ofs, t->d_pair_ofs, t->d_fl, t->d_chain[0], t->d_chain[1], t->d_prob_order, t->d_prob_res));
+    RT_CHECK(t->d_fields.reserve(c * 2 * sdvs::FIELD_PITCH)); RT_CHECK(t->d_pairs.reserve(c * sdvs::PAIR_SLOT)); RT_CHECK(t->d_frasm.reserve(c * sdvs::FRASM_SLOT));
+    RT_CHECK(t->d_back.reserve(stitch_back_bytes(c))); RT_CHECK(t->h_back.reserve(stitch_back_bytes(c)));
+    t->d_ctl = (uint32_t *)t->d_back.p; t->d_next_work = t->d_ctl + sdvs::CTL_NEXT; t->d_seg_end = (uint32_t *)(t->d_back + 64);
+    t->d_brief = (sdvs::FrameBrief *)(t->d_back + 64 + ((c * sizeof(uint32_t) + 63) & ~(size_t)63)); t->d_info = (sdvs::StepInfo *)(t->d_brief + c);
+    t->seg_slots = c;
+    return SDV_OK;
 }
 
 /* The fused entry, ahead of its binarize call: may the frame kernel put the frames it captures whole straight into the field buffers?  Yes when the stitch
@@ -296,7 +287,7 @@ static int stitch_prepare_direct(sdv_engine *e, size_t n_frames, size_t recs_per
     if (est_seg < 3 || (uint64_t)(est_seg - 1) * t->guess_pairs > (uint64_t)pairs_cap || (uint64_t)(est_seg - 1) * t->guess_frasm > (uint64_t)frames_cap) return SDV_OK;
     if (recs_per_frame - 3 > 2 * (size_t)sdvs::BUF_FIELD) return SDV_OK;
     { int r = stitch_grow_seg(e, t, est_seg); if (r != SDV_OK) return r; }
-    if (n_frames > t->cap_direct) { const size_t c = n_frames + n_frames / 8 + 16; ST_GROW(t->d_direct, sdv::DirectFrame, c); t->cap_direct = c; }
+    RT_CHECK(t->d_direct.reserve(n_frames, n_frames + n_frames / 8 + 16));
     t->direct_armed = true; t->direct_ofs = (uint32_t)t->carry_frames; t->direct_n = (uint32_t)n_frames;
     *fields = t->d_fields; *direct = t->d_direct; *seg_ofs = t->carry_frames;
     return SDV_OK;
@@ -319,7 +310,7 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
     memset(&t->info, 0, sizeof(t->info));
     t->direct_count_owed = false;       /* (owed again only by a call that ends well, below: an error return leaves nothing to count) */
     if (!t->d_chain0) {
-        RT_CHECK(rt::dmalloc((void **)&t->d_chain0, sizeof(sdvs::StepChain)));
+        RT_CHECK(t->d_chain0.reserve(1));
         sdvs::StepChain c; cold_chain(&c);
         RT_CHECK(rt::h2d(t->d_chain0, &c, sizeof(c), s));
     }
@@ -352,14 +343,14 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
 #endif
     auto grow_seg = [&](size_t n_seg_need) -> int { return stitch_grow_seg(e, t, n_seg_need); };
     auto grow_ws = [&](size_t waves) -> int {
-        if (waves > t->cap_ws) { ST_GROW(t->d_ws, sdvs::SLine, waves * sdvs::QCAP); t->cap_ws = waves; }
+        RT_CHECK(t->d_ws.reserve(waves * sdvs::QCAP));
         return SDV_OK;
     };
 
     /* 1. frame segments: positions of the END_FRAME records */
     const size_t nblk = (total + sdvs::SEG_CHUNK - 1) / sdvs::SEG_CHUNK;
-    if (nblk > t->cap_blk) { ST_GROW(t->d_blk_count, uint32_t, nblk); ST_GROW(t->d_blk_ofs, uint32_t, nblk); t->cap_blk = nblk; }
-    if (total > t->cap_svc) { const size_t c = total + total / 4 + 4096; ST_GROW(t->d_svc, uint8_t, c); t->cap_svc = c; }
+    RT_CHECK(rt::reserve_all(nblk, nblk, t->d_blk_count, t->d_blk_ofs));
+    RT_CHECK(t->d_svc.reserve(total, total + total / 4 + 4096));
     sdvs::SegArgs sa; sa.src = src; sa.n_recs = (uint32_t)total; sa.svc = t->d_svc; sa.block_count = t->d_blk_count; sa.block_ofs = t->d_blk_ofs; sa.seg_end = NULL; sa.write = 0; sa.seg_cap = 0;
 
     std::chrono::steady_clock::time_point ht[8]; for (auto &x : ht) x = std::chrono::steady_clock::now();
@@ -369,8 +360,8 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
     /* the host's view of the read-back block (valid once grow_seg() has run for this call) */
     sdvs::FrameBrief *brief = NULL; uint32_t *seg_end = NULL, *ctl = NULL; sdvs::StepInfo *info = NULL;
     auto pin_back = [&]() {
-        ctl = (uint32_t *)t->h_back; seg_end = (uint32_t *)(t->h_back + 64);
-        brief = (sdvs::FrameBrief *)(t->h_back + 64 + ((t->cap_seg * sizeof(uint32_t) + 63) & ~(size_t)63)); info = (sdvs::StepInfo *)(brief + t->cap_seg);
+        ctl = (uint32_t *)t->h_back.p; seg_end = (uint32_t *)(t->h_back + 64);
+        brief = (sdvs::FrameBrief *)(t->h_back + 64 + ((t->seg_slots * sizeof(uint32_t) + 63) & ~(size_t)63)); info = (sdvs::StepInfo *)(brief + t->seg_slots);
     };
     sdvs::StepArgs sp; memset(&sp, 0, sizeof(sp));
     sp.cfg = cfg; sp.chain0 = t->d_chain0;
@@ -417,7 +408,7 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
         }
         sdvs::AnalyzeArgs aa; aa.src = src; aa.seg_end = t->d_seg_end; aa.n_seg = (uint32_t)est_seg; aa.ctl = t->d_ctl; aa.cfg = cfg; aa.fl = t->d_fl; aa.brief = t->d_brief; aa.fields = t->d_fields;
         aa.timing = NULL;
-        aa.direct = direct_now ? t->d_direct : NULL; aa.direct_ofs = t->direct_ofs; aa.direct_n = t->direct_n;
+        aa.direct = direct_now ? t->d_direct.p : NULL; aa.direct_ofs = t->direct_ofs; aa.direct_n = t->direct_n;
 #ifndef SDV_EMU
         if (e->profiling && queue_now) {
             if (!e->have_events) { RT_CHECK(hipEventCreate(&e->ev0)); RT_CHECK(hipEventCreate(&e->ev1)); e->have_events = true; }
@@ -441,15 +432,9 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
             /* what the next call inherits, ahead of the read-back: with the layout known so are the last turn (est_seg - 2, handed over in the second
              * buffers after one round) and the frame that waits for its successor (the last reg->recs_per_frame records).  Both go to spare buffers
              * and are swapped in at the end if the call went as assumed - then nothing is left to do behind the read-back. */
-            if (!t->d_chain0_spare) RT_CHECK(rt::dmalloc((void **)&t->d_chain0_spare, sizeof(sdvs::StepChain)));
+            RT_CHECK(t->d_chain0_spare.reserve(1));
             const size_t cnt = reg->recs_per_frame;
-            if (cnt > t->cap_carry_spare) {
-                if (t->d_carry_spare) rt::dfree(t->d_carry_spare);
-                t->d_carry_spare = NULL; t->cap_carry_spare = 0;
-                const size_t cap = cnt + cnt / 2 + 1024;
-                RT_CHECK(rt::dmalloc((void **)&t->d_carry_spare, cap * sizeof(sdv_line_rec)));
-                t->cap_carry_spare = cap;
-            }
+            RT_CHECK(t->d_carry_spare.reserve(cnt, cnt + cnt / 2 + 1024));
             if (queue_now) {
                 RT_CHECK(rt::d2d(t->d_chain0_spare, &t->d_chain[1][est_seg - 2], sizeof(sdvs::StepChain), s));
                 RT_CHECK(rt::d2d(t->d_carry_spare, lines + (n_lines - cnt), cnt * sizeof(sdv_line_rec), s));
@@ -457,9 +442,9 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
             tail_ahead = true;
         }
         /* control words, segment ends, briefs and infos in one copy */
-        if (step == STITCH_QUEUE_AHEAD) { RT_CHECK(rt::d2h_async(t->h_back, t->d_back, t->cap_back, s)); return SDV_STITCH_QUEUED_AHEAD; }
+        if (step == STITCH_QUEUE_AHEAD) { RT_CHECK(rt::d2h_async(t->h_back, t->d_back, stitch_back_bytes(t->seg_slots), s)); return SDV_STITCH_QUEUED_AHEAD; }
         if (step == STITCH_TAKE_UP) RT_CHECK(rt::ssync(s));
-        else RT_CHECK(rt::d2h_pinned(t->h_back, t->d_back, t->cap_back, s));
+        else RT_CHECK(rt::d2h_pinned(t->h_back, t->d_back, stitch_back_bytes(t->seg_slots), s));
         if (ctl[sdvs::CTL_NSEG] >= 2 && ctl[sdvs::CTL_NSEG] <= est_seg) {
             piped = true; n_seg = ctl[sdvs::CTL_NSEG];
             piped_round = ctl[sdvs::CTL_ABORT] == 0;
@@ -467,14 +452,12 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
     }
     auto keep_all = [&]() -> int {      /* nothing to do yet: the records wait for the next call, like lines in the reference's input queue */
         if (n_lines == 0) return SDV_OK;
-        if (total > t->cap_carry) {
-            sdv_line_rec *nc = NULL;
-            size_t cap = total + total / 2 + 1024;
-            RT_CHECK(rt::dmalloc((void **)&nc, cap * sizeof(sdv_line_rec)));
+        if (total > t->d_carry.cap) {       /* (grows with what it holds) */
+            rt::DevBuf<sdv_line_rec> nc;
+            RT_CHECK(nc.reserve(total + total / 2 + 1024));
             if (t->n_carry) RT_CHECK(rt::d2d(nc, t->d_carry, t->n_carry * sizeof(sdv_line_rec), s));
             RT_CHECK(rt::ssync(s));
-            if (t->d_carry) rt::dfree(t->d_carry);
-            t->d_carry = nc; t->cap_carry = cap;
+            t->d_carry.swap(nc);
         }
         RT_CHECK(rt::d2d(t->d_carry + t->n_carry, lines, n_lines * sizeof(sdv_line_rec), s));
         RT_CHECK(rt::ssync(s));
@@ -504,7 +487,8 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
         }
 #endif
         aa.timing = NULL;
-        if (dev_env("SDV_STITCH_TIMING")) { RT_CHECK(rt::dmalloc((void **)&aa.timing, n_seg * 8 * sizeof(unsigned long long))); RT_CHECK(rt::dzero(aa.timing, n_seg * 8 * sizeof(unsigned long long), s)); }
+        rt::DevBuf<unsigned long long> d_atiming;
+        if (dev_env("SDV_STITCH_TIMING")) { RT_CHECK(d_atiming.reserve(n_seg * 8)); RT_CHECK(rt::dzero(d_atiming, n_seg * 8 * sizeof(unsigned long long), s)); aa.timing = d_atiming; }
         RT_LAUNCH64(sdv_k_stitch_analyze, n_seg, aa, s);
         if (aa.timing) {        /* developer aid: mean cycles per phase of the analysis of a frame */
             std::vector<unsigned long long> tm(n_seg * 8);
@@ -515,7 +499,6 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
             for (size_t k = 0; k < n_seg; k++) { st += (double)(tm[k * 8 + 5] - tm[k * 8 + 3]); lp += (double)(tm[k * 8 + 6] - tm[k * 8 + 5]); sc += (double)tm[k * 8 + 7]; }
             fprintf(stderr, "[analyze timing] cycles/frame: read + stage %.0f  trim %.0f  split + field buffers %.0f  resolution %.0f (first field: staging %.0f, trials %.0f, %.2f steps with a block through processBlock)\n",
                     ph[0] / n_seg, ph[1] / n_seg, ph[2] / n_seg, ph[3] / n_seg, st / n_seg, lp / n_seg, sc / n_seg);
-            rt::dfree(aa.timing);
         }
         pin_back();
         RT_CHECK(rt::d2h_async(brief, t->d_brief, n_seg * sizeof(sdvs::FrameBrief), s));
@@ -559,8 +542,8 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
     try_direct = t->steady && t->guess_pairs > 0 && t->guess_frasm > 0 &&
                  (uint64_t)n_steps * t->guess_pairs <= (uint64_t)pairs_cap && (uint64_t)n_steps * t->guess_frasm <= (uint64_t)frames_cap;
     sp.direct_pairs = try_direct ? out_pairs : NULL; sp.direct_frasm = try_direct ? out_frames : NULL;
-    unsigned long long *d_timing = NULL;
-    if (dev_env("SDV_STITCH_TIMING")) { RT_CHECK(rt::dmalloc((void **)&d_timing, n_steps * 8 * sizeof(unsigned long long))); RT_CHECK(rt::dzero(d_timing, n_steps * 8 * sizeof(unsigned long long), s)); }
+    rt::DevBuf<unsigned long long> d_timing;
+    if (dev_env("SDV_STITCH_TIMING")) { RT_CHECK(d_timing.reserve(n_steps * 8)); RT_CHECK(rt::dzero(d_timing, n_steps * 8 * sizeof(unsigned long long), s)); }
     sp.timing = d_timing;
     HT(3);
     bool plain = false;     /* every frame and every turn of the call like those of the last one: the two histories stay what they are, no replay needed */
@@ -661,7 +644,6 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
         for (size_t k = 0; k < n_steps; k++) for (int i = 0; i < 6; i++) ph[i] += (double)(tm[k * 8 + i + 1] - tm[k * 8 + i]);
         fprintf(stderr, "[stitch timing] cycles/turn: load %.0f  stitching %.0f  fill %.0f  cwd %.0f  deinterleave %.0f  handover %.0f\n",
                 ph[0] / n_steps, ph[1] / n_steps, ph[2] / n_steps, ph[3] / n_steps, ph[4] / n_steps, ph[5] / n_steps);
-        rt::dfree(d_timing);
     }
     HT(4);
     /* 4. the outputs: already in place when the guess held for every turn, else packed from the per-turn slots */
@@ -709,7 +691,7 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
         sp.n_work = (uint32_t)n_steps; sp.first_round = 0; sp.timing = NULL;
         std::vector<uint32_t> aofs(n_steps), acnt(n_steps);
         if (t->line_out) {
-            if (n_steps > t->cap_asm) { const size_t c = n_steps + n_steps / 4 + 16; ST_GROW(t->d_asm_cnt, uint32_t, c); ST_GROW(t->d_asm_ofs, uint32_t, c); t->cap_asm = c; }
+            RT_CHECK(rt::reserve_all(n_steps, n_steps + n_steps / 4 + 16, t->d_asm_cnt, t->d_asm_ofs));
             RT_CHECK(rt::dzero(t->d_next_work, sizeof(uint32_t), s));
             sp.asm_cnt = t->d_asm_cnt; sp.asm_lines = NULL; sp.asm_ofs = NULL; sp.blocks = NULL; sp.block_ofs = NULL;
             RT_LAUNCH64(sdv_k_stitch_step, std::min(n_steps, waves_cap), sp, s);
@@ -729,7 +711,7 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
             for (size_t k = 0; k < n_steps; k++) { bofs[k] = (uint32_t)nb; nb += info[k].n_pairs / 3u; }
             t->n_blocks = (size_t)nb;
             if (nb > t->block_cap) { set_error(e, "block buffer too small: " + std::to_string((unsigned long long)nb) + " data blocks are needed"); *n_pairs = (size_t)np; *n_frames = nf; return SDV_ERR_BAD_ARG; }
-            if (n_steps > t->cap_block_ofs) { ST_GROW(t->d_block_ofs, uint32_t, n_steps + n_steps / 4 + 16); t->cap_block_ofs = n_steps + n_steps / 4 + 16; }
+            RT_CHECK(t->d_block_ofs.reserve(n_steps, n_steps + n_steps / 4 + 16));
             RT_CHECK(rt::h2d(t->d_block_ofs, bofs.data(), n_steps * sizeof(uint32_t), s));
             sp.blocks = t->block_out; sp.block_ofs = t->d_block_ofs;
         }
@@ -767,8 +749,8 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
             if (memcmp(ahead.data(), now.data(), now.size()) != 0) { set_error(e, "internal: the stitch state copied ahead of the read-back is not the last turn's"); return SDV_ERR_HIP; }
         }
 #endif
-        std::swap(t->d_chain0, t->d_chain0_spare);
-        std::swap(t->d_carry, t->d_carry_spare); std::swap(t->cap_carry, t->cap_carry_spare);
+        t->d_chain0.swap(t->d_chain0_spare);
+        t->d_carry.swap(t->d_carry_spare);
         t->n_carry = reg->recs_per_frame; t->carry_frames = 1;
     } else {
     RT_CHECK(rt::d2d(t->d_chain0, &t->d_chain[which[n_steps - 1]][n_steps - 1], sizeof(sdvs::StepChain), s));
@@ -776,20 +758,14 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
     else {
         /* the last frame has no successor yet: it (and any records behind its END_FRAME) waits for the next call */
         const size_t from = (size_t)seg_end[n_seg - 2] + 1, cnt = total - from;
-        if (cnt > t->cap_carry_spare) {
-            if (t->d_carry_spare) rt::dfree(t->d_carry_spare);
-            t->d_carry_spare = NULL; t->cap_carry_spare = 0;
-            const size_t cap = cnt + cnt / 2 + 1024;
-            RT_CHECK(rt::dmalloc((void **)&t->d_carry_spare, cap * sizeof(sdv_line_rec)));
-            t->cap_carry_spare = cap;
-        }
+        RT_CHECK(t->d_carry_spare.reserve(cnt, cnt + cnt / 2 + 1024));
         sdv_line_rec *nc = t->d_carry_spare;
         size_t done = 0;
         if (from < t->n_carry) { done = t->n_carry - from; RT_CHECK(rt::d2d(nc, t->d_carry + from, done * sizeof(sdv_line_rec), s)); }
         const size_t lfrom = from + done - t->n_carry;
         RT_CHECK(rt::d2d(nc + done, lines + lfrom, (cnt - done) * sizeof(sdv_line_rec), s));
         RT_CHECK(rt::ssync(s));                       /* the caller may reuse `lines` as soon as the call returns */
-        std::swap(t->d_carry, t->d_carry_spare); std::swap(t->cap_carry, t->cap_carry_spare);
+        t->d_carry.swap(t->d_carry_spare);
         t->n_carry = cnt; t->carry_frames = (size_t)seg_end[n_seg - 1] + 1 == total ? 1 : -1;
     }
     }

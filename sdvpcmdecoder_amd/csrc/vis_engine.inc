@@ -5,18 +5,17 @@
  * many frames there are), the frames' first rows, the lines, and the two passes that carry over what a frame did not draw.
  */
 struct sdv_vis {
-    uint32_t *d_canvas[10];             /* per kind: the canvas as the last frame of the last call left it (RenderPCM::img_data) */
-    uint32_t *d_cnt, *d_base_end, *d_base_adv; size_t cap_chunks;
-    uint32_t *d_frame_adv0, *d_wmask; size_t cap_frames, cap_wmask;
-    uint32_t *d_frame_ofs; size_t cap_frame_ofs;
-    int32_t *d_last; size_t cap_last;
+    rt::DevBuf<uint32_t> d_canvas[10];  /* per kind: the canvas as the last frame of the last call left it (RenderPCM::img_data) */
+    rt::DevBuf<uint32_t> d_cnt, d_base_end, d_base_adv;
+    rt::DevBuf<uint32_t> d_frame_adv0, d_wmask;
+    rt::DevBuf<uint32_t> d_frame_ofs;
+    rt::DevBuf<int32_t> d_last;
 };
 
 static sdv_vis *vis_get(sdv_engine *e)
 {
     if (e->vis) return e->vis;
     sdv_vis *t = new sdv_vis();
-    memset(t, 0, sizeof(*t));
     e->vis = t;
     return t;
 }
@@ -24,8 +23,6 @@ static void vis_free(sdv_engine *e)
 {
     sdv_vis *t = e->vis;
     if (!t) return;
-    void *ptrs[] = { t->d_canvas[0], t->d_canvas[1], t->d_canvas[2], t->d_canvas[3], t->d_canvas[4], t->d_canvas[5], t->d_canvas[6], t->d_canvas[7], t->d_canvas[8], t->d_canvas[9], t->d_frame_ofs, t->d_cnt, t->d_base_end, t->d_base_adv, t->d_frame_adv0, t->d_wmask, t->d_last };
-    for (void *p : ptrs) if (p) rt::dfree(p);
     delete t;
     e->vis = NULL;
 }
@@ -34,7 +31,7 @@ static int vis_blank(sdv_engine *e, sdv_vis *t, int kind, rt::stream_t s)
 {
     const sdvvis::Geometry g = sdvvis::geometry(kind);
     const size_t n_px = (size_t)g.w * g.h;
-    if (!t->d_canvas[kind]) RT_CHECK(rt::dmalloc((void **)&t->d_canvas[kind], n_px * sizeof(uint32_t)));
+    RT_CHECK(t->d_canvas[kind].reserve(n_px));
     sdvvis::BlankArgs b; b.canvas = t->d_canvas[kind]; b.n_px = (uint32_t)n_px;
     RT_LAUNCH64(sdv_k_vis_blank, (n_px + 63) / 64, b, s);
     return SDV_OK;
@@ -75,11 +72,7 @@ int sdv_vis_render_lines(sdv_engine *e, int kind, const void *recs, size_t n_rec
     if (!t->d_canvas[kind]) { const int rc = vis_blank(e, t, kind, s); if (rc != SDV_OK) return rc; }
 
     const size_t n_chunks = (n_recs + 63) / 64;
-    if (n_chunks > t->cap_chunks) {
-        const size_t c = n_chunks + n_chunks / 4 + 64;
-        ST_GROW(t->d_cnt, uint32_t, c); ST_GROW(t->d_base_end, uint32_t, c); ST_GROW(t->d_base_adv, uint32_t, c);
-        t->cap_chunks = c;
-    }
+    RT_CHECK(rt::reserve_all(n_chunks, n_chunks + n_chunks / 4 + 64, t->d_cnt, t->d_base_end, t->d_base_adv));
     sdvvis::VisArgs a;
     memset(&a, 0, sizeof(a));
     a.recs = recs; a.n_recs = (uint32_t)n_recs; a.kind = kind; a.cnt = t->d_cnt; a.base_end = t->d_base_end; a.base_adv = t->d_base_adv;
@@ -101,14 +94,14 @@ int sdv_vis_render_lines(sdv_engine *e, int kind, const void *recs, size_t n_rec
     RT_CHECK(rt::h2d(t->d_base_adv, ba.data(), n_chunks * sizeof(uint32_t), s));
     RT_CHECK(rt::ssync(s));             /* the host vectors go out of scope with the call */
     const size_t n_cells = (size_t)g.h * g.cells_per_row, stride = (n_cells + 31) / 32;
-    if ((size_t)ends + 1 > t->cap_frames) { const size_t c = (size_t)ends + 1 + ends / 4; ST_GROW(t->d_frame_adv0, uint32_t, c); t->cap_frames = c; }
-    if ((size_t)ends * stride > t->cap_wmask) { const size_t c = (size_t)ends * stride + (size_t)ends * stride / 4; ST_GROW(t->d_wmask, uint32_t, c); t->cap_wmask = c; }
+    RT_CHECK(t->d_frame_adv0.reserve((size_t)ends + 1, (size_t)ends + 1 + ends / 4));
+    RT_CHECK(t->d_wmask.reserve((size_t)ends * stride, (size_t)ends * stride + (size_t)ends * stride / 4));
     RT_CHECK(rt::dzero(t->d_wmask, (size_t)ends * stride * sizeof(uint32_t), s));
     a.frame_adv0 = t->d_frame_adv0; a.n_frames = ends; a.out = out_canvases; a.wmask = t->d_wmask; a.wmask_stride = (uint32_t)stride; a.canvas = t->d_canvas[kind];
     VIS_LAUNCH(index, n_chunks);
     VIS_LAUNCH(draw, n_chunks);
 #undef VIS_LAUNCH
-    if (n_cells * (size_t)ends > t->cap_last) { const size_t c = n_cells * ((size_t)ends + ends / 4 + 1); ST_GROW(t->d_last, int32_t, c); t->cap_last = c; }
+    RT_CHECK(t->d_last.reserve(n_cells * (size_t)ends, n_cells * ((size_t)ends + ends / 4 + 1)));
     a.last_drawn = t->d_last; a.n_cells = (uint32_t)n_cells;
     RT_LAUNCH64(sdv_k_vis_last, n_cells, a, s);
     RT_LAUNCH64(sdv_k_vis_fill, (size_t)ends * ((n_cells + 63) / 64), a, s);
@@ -138,9 +131,9 @@ static int vis_render_rows(sdv_engine *e, int kind, bool asm_lines, const void *
     const sdvvis::Geometry g = sdvvis::geometry(kind);
     const size_t n_cells = g.h, stride = (n_cells + 31) / 32, chunks = (g.h + 63) / 64;
     if (at * (kind == SDV_VIS_PCM1_BLOCKS ? (uint64_t)sdvvis::P1BK_ROWS : 1u) >= 0xFFFFFFFFu) { set_error(e, "too many blocks in one call"); return SDV_ERR_BAD_ARG; }
-    if (n_frames + 1 > t->cap_frame_ofs) { const size_t c = n_frames + 1 + n_frames / 4; ST_GROW(t->d_frame_ofs, uint32_t, c); t->cap_frame_ofs = c; }
-    if (n_frames * stride > t->cap_wmask) { const size_t c = n_frames * stride + n_frames * stride / 4; ST_GROW(t->d_wmask, uint32_t, c); t->cap_wmask = c; }
-    if (n_cells * n_frames > t->cap_last) { const size_t c = n_cells * (n_frames + n_frames / 4 + 1); ST_GROW(t->d_last, int32_t, c); t->cap_last = c; }
+    RT_CHECK(t->d_frame_ofs.reserve(n_frames + 1, n_frames + 1 + n_frames / 4));
+    RT_CHECK(t->d_wmask.reserve(n_frames * stride, n_frames * stride + n_frames * stride / 4));
+    RT_CHECK(t->d_last.reserve(n_cells * n_frames, n_cells * (n_frames + n_frames / 4 + 1)));
     RT_CHECK(rt::h2d(t->d_frame_ofs, ofs.data(), (n_frames + 1) * sizeof(uint32_t), s));
     RT_CHECK(rt::ssync(s));             /* the host vector goes out of scope with the call */
     RT_CHECK(rt::dzero(t->d_wmask, n_frames * stride * sizeof(uint32_t), s));

@@ -30,6 +30,10 @@ struct uint2 { uint32_t x, y; };
 #include "../../sdvpcmdecoder_amd/csrc/audio_engine.inc"
 #include "../../sdvpcmdecoder_amd/csrc/vis_engine.inc"
 
+/* Test hook: the nth allocation (rt::dmalloc or rt::hpin) from now fails, once; 0 disarms.  Returns what was left of the last countdown, so
+ * that a test can count the allocations of a call: arm with a large nth, make the call, ask what is left. */
+extern "C" int sdv_emu_fail_alloc(int nth) { const int left = rt::fail_alloc_in; rt::fail_alloc_in = nth > 0 ? nth : 0; return left; }
+
 /* ---- test hooks (emulator build only) -------------------------------------------------------------------------------------------- */
 /* bursts_word (64 blocks per call, mask arithmetic) against bursts_block (one block per call) on random flag sequences: returns the number of
  * sequences on which the two disagree.  Flags per block are independent bits with the given densities (per mille), in runs of random length so
