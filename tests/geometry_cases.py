@@ -1,0 +1,338 @@
+"""Awkward buffer geometry for the two marker-less formats (PCM-1, PCM-16x0): the shape tables, the helper that places frames in a larger
+buffer - padded rows, gaps between frames (or none at all: the last row of a frame touching the first of the next), a start that is not 16-byte aligned -
+the oracle's records of the same frames held contiguously, and host-memory callers of the entry points that pass the strides and hand over outputs with
+guard records behind what the call may write.  Shared by the emulator and the GPU twins of tests/test_markerless_geometry.py.
+
+Why these shapes: stage_row (pcm1_bin_device.h) copies 16 bytes per lane when row pointer and width are multiples of 16 and byte by byte otherwise, the
+lean frame kernels gather single bytes at 2 * idx + field rows of row_stride, fields are (h + 1) / 2 and h / 2 lines, and the prescan only runs on
+frames of more than COORD_CHECK_PARTS buffer lines."""
+import ctypes as C
+import functools
+
+import numpy as np
+
+import engine_api as ea
+import libs
+import pcm1_api as p1
+import pcm16_api as p16
+import pcm1_frames_api as p1f
+import pcm16_frames_api as p16f
+import pcm1_front_api as p1l
+import pcm16_front_api as p16l
+from sdvpcmdecoder_amd import synth
+
+PX_BYTES = 2048             # SDV_PX_BYTES (stc007_device.h): the widest line the marker-less entry points take, the LDS row of stage_row
+BAD_ARG = -1                # SDV_ERR_BAD_ARG
+GUARD = 0xA5                # what the records behind the ones a call may write are filled with
+PCM1, PCM16X0, STC007 = 0, 1, 2
+N_FRAMES = 3
+TIGHT = "tight"             # gap: frame_stride = (h - 1) * row_stride + w, the smallest the entry points take (= -pad)
+
+# (w, h, pad, shift, gap, mode): row_stride = w + pad, frame_stride = h * row_stride + gap, the first pixel `shift` bytes behind a 16-byte boundary
+FRAME_SHAPES = [
+    (720, 24, 13, 0, 0, 2),         # padded rows: rows leave 16-byte alignment (every 16th keeps it) - byte path and vector path within one frame
+    (720, 24, 0, 5, 0, 2),          # misaligned base: every row on the byte path
+    (721, 24, 0, 0, 0, 2),          # width not a multiple of 16
+    (717, 25, 3, 1, 7, 1),          # everything at once, odd height
+    (720, 25, 16, 16, 720, 2),      # all aligned again but padded, odd height: stays on the vector path and must still skip the pad
+    (720, 23, 0, 0, 0, 0),          # odd height in MODE_DRAFT: no prescan
+    (720, 24, 8, 0, TIGHT, 2),      # the last row of a frame touches the first row of the next
+    (2048, 12, 0, 0, 0, 1),         # SDV_PX_BYTES exactly: the last byte of the LDS row
+    (1930, 11, 5, 3, 0, 2),         # wide, byte path, the second trip round stage_row's loop
+    (720, 9, 8, 0, 0, 2),           # short frame: the prescan lines one or two rows apart
+    (720, 3, 0, 0, 0, 2),           # frame_buf_lines == COORD_CHECK_PARTS: the prescan does not run
+    (720, 2, 0, 0, 0, 2),           # the smallest frame the entry points take
+    # pad == w, the pad filled with the rows of another tape (place(beside=...)): every second row of a picture twice as wide.  The lean frame kernels
+    # take runs of lines with byte gathers of their own (batch1, batch16) and fall back to staging line by line where a run does not read: wrong row
+    # arithmetic there only shows where the wrong row reads as well.
+    (720, 24, 720, 0, 0, 2),
+]
+STREAM_SHAPE = 3                    # the 717 x 25 row, as a stream of 12 damaged frames in calls of ...
+STREAM_CALLS = (1, 7, 4)
+STREAM_FRAMES = sum(STREAM_CALLS)
+
+# (w, pad, shift, how, mode).  how: "rows" = independent lines, one per row of the buffer; "field" = every second row of a frame (row_stride = 2 * w)
+LINE_SHAPES = [(721, 0, 0, "rows", 2), (720, 13, 0, "rows", 2), (2048, 0, 0, "rows", 1), (1930, 5, 3, "rows", 2), (720, 0, 0, "field", 2)]
+N_LINES = 12
+
+# sdv_decode_frames: one padded, misaligned case per format (pad, shift as below, three frames, NEW_FILE and END_FILE)
+FUSED_PAD, FUSED_SHIFT = 13, 5
+FUSED_HEIGHT = {STC007: 25, PCM1: 25, PCM16X0: 24}
+
+
+def lean_build_alone(shape):
+    """Frames that play and whose prescan runs (every mode but DRAFT, more than COORD_CHECK_PARTS = 6 lines in the frame buffer: h + 3 of them) are
+    decoded by the lean build of the frame kernel alone - the one that gathers bytes at row_stride and frame_stride itself; it hands a frame to the
+    full build only when a line does not read from what it inherits (pcm1_frames_engine.inc), and the lines of the tables read
+    (test_the_frames_of_the_tables_read).  A lean build that looks at the wrong rows gives every frame up; the records then still come out right,
+    from the full build, and only sdv_run_info.frames_general tells."""
+    _w, h, _pad, _shift, _gap, mode = shape
+    return mode != 0 and h + 3 > 6
+
+
+def shape_id(s):
+    return "x".join(str(v) for v in s[:2]) + "".join("_%s" % v for v in s[2:])
+
+
+class Format:
+    def __init__(self, name, pcm_type, frames_api, lines_api, gen_frames, gen_lines, rec_dtype, recs_per_line, line_prefix, count_fn):
+        self.name, self.pcm_type, self.frames_api, self.lines_api = name, pcm_type, frames_api, lines_api
+        self.gen_frames, self.gen_lines, self.rec_dtype, self.recs_per_line = gen_frames, gen_lines, rec_dtype, recs_per_line
+        self.line_prefix, self.count_fn = line_prefix, count_fn
+        self.frames_entry, self.lines_entry = "sdv_%s_binarize_frames" % name, "sdv_%s_binarize_lines" % name
+
+
+FORMATS = {
+    "pcm1": Format("pcm1", PCM1, p1f, p1l, synth.pcm1_frames, synth.pcm1_random_lines, p1f.BIN1_DTYPE, 1, "orc_bin1_", "sdv_binarize_records"),
+    "pcm16x0": Format("pcm16x0", PCM16X0, p16f, p16l, synth.pcm16x0_frames, synth.pcm16x0_random_lines, p16f.BIN16_DTYPE, 3, "orc_bin16_",
+                      "sdv_pcm16x0_binarize_records"),
+}
+
+
+# ---- the pixels ------------------------------------------------------------------------------------------------------------------------------
+def _window(w):
+    """x0 / x1 of the generators (4 and w - 4 at 720 px) scaled to the width, so that the lines read at every width of the tables"""
+    x0 = max(1, (4 * w + 360) // 720)
+    return dict(x0=x0, x1=w - x0)
+
+
+def make_frames(fmt, w, h, n=N_FRAMES, seed=0, **kw):
+    """Frames of an even height cut to h rows: an odd h leaves fields of (h + 1) / 2 and h / 2 lines."""
+    luma, _ = fmt.gen_frames(n, seed=seed, width=w, height=h + (h & 1), noise_sigma=3.0, **_window(w), **kw)
+    return np.ascontiguousarray(luma[:, :h])
+
+
+def make_lines(fmt, w, seed=0):
+    kw = dict(control="random") if fmt.name == "pcm16x0" else {}
+    luma, _ = fmt.gen_lines(N_LINES, seed=seed, width=w, noise_sigma=3.0, **_window(w), **kw)
+    return np.ascontiguousarray(luma)
+
+
+class Placed:
+    """(n, h, w) frames inside `buf`: buf[0] sits on a 16-byte boundary, the first pixel at buf[start], pixel (f, r, x) at
+    buf[start + f * frame_stride + r * row_stride + x].  Every other byte of buf is seeded noise."""
+
+    def __init__(self, buf, start, row_stride, frame_stride, shape):
+        self.buf, self.start, self.row_stride, self.frame_stride, self.shape = buf, start, row_stride, frame_stride, shape
+
+    def view(self):
+        n, h, w = self.shape
+        return np.lib.stride_tricks.as_strided(self.buf[self.start:], shape=(n, h, w), strides=(self.frame_stride, self.row_stride, 1))
+
+    def ptr(self, first_frame=0):
+        return self.buf.ctypes.data + self.start + first_frame * self.frame_stride
+
+    def torch_view(self, torch, first_frame=0, n=None):
+        """The same bytes on the GPU and the (n, h, w) view of them that Engine takes (strides in bytes = elements)."""
+        if not hasattr(self, "_dev"):
+            self._dev = torch.from_numpy(self.buf).to("cuda:0")
+            assert self._dev.data_ptr() % 16 == 0
+        _, h, w = self.shape
+        n = self.shape[0] - first_frame if n is None else n
+        return torch.as_strided(self._dev, (n, h, w), (self.frame_stride, self.row_stride, 1), self.start + first_frame * self.frame_stride)
+
+
+def place(frames, pad=0, shift=0, gap=0, seed=0, beside=None):
+    """The generalisation of engine_api.emu_binarize's padded, shifted buffer: row_stride = w + pad, frame_stride = h * row_stride + gap (gap may be
+    negative down to -pad, TIGHT), the first pixel `shift` bytes behind a 16-byte boundary.  The bytes between, before and behind the frames come from a
+    seeded generator, not a constant: a kernel that takes pad bytes for pixels decodes something else.  `beside` (pad == w): frames of another tape whose
+    rows fill the pad, so that the frames are every second row of a picture whose other rows read just as well."""
+    n, h, w = frames.shape
+    rs = w + pad
+    fs = (h - 1) * rs + w if gap == TIGHT else h * rs + gap
+    assert fs >= (h - 1) * rs + w, "frames would overlap"
+    span = (n - 1) * fs + (h - 1) * rs + w + (w if beside is not None else 0)
+    start = 16 + shift
+    total = start + span + 64
+    raw = np.empty(total + 15, dtype=np.uint8)
+    a = (-raw.ctypes.data) % 16
+    buf = raw[a:a + total]
+    buf[:] = np.random.default_rng(seed).integers(0, 256, size=total, dtype=np.uint8)
+    assert buf.ctypes.data % 16 == 0
+    p = Placed(buf, start, rs, fs, (n, h, w))
+    if beside is not None:
+        assert pad == w and gap == 0 and beside.shape == frames.shape
+        np.lib.stride_tricks.as_strided(buf[start + w:], shape=(n, h, w), strides=(fs, rs, 1))[...] = beside
+    p.view()[...] = frames
+    assert np.array_equal(p.view(), frames)
+    return p
+
+
+# ---- what the oracle makes of the same pixels held contiguously: computed once per case, shared by the twins, read-only ------------------------
+def _frozen(*arrays):
+    for a in arrays:
+        a.setflags(write=False)
+    return arrays
+
+
+@functools.lru_cache(maxsize=None)
+def frames_case(fmt_name, idx):
+    """-> (frames (n, h, w) contiguous, the oracle's records, the oracle's frame descriptors) of row idx of FRAME_SHAPES"""
+    fmt = FORMATS[fmt_name]
+    w, h, _pad, _shift, _gap, mode = FRAME_SHAPES[idx]
+    frames = make_frames(fmt, w, h, seed=900 + idx)
+    recs, stats = fmt.frames_api.run_cpu(libs.load_oracle(), "orc_", frames, mode, {})
+    return _frozen(frames, recs, stats)
+
+
+@functools.lru_cache(maxsize=None)
+def stream_case(fmt_name):
+    """The 717 x 25 shape as a damaged tape of 12 frames (jitter, lost lines): one sequential oracle run over all of them, NEW_FILE in front."""
+    fmt = FORMATS[fmt_name]
+    w, h, _pad, _shift, _gap, mode = FRAME_SHAPES[STREAM_SHAPE]
+    frames = make_frames(fmt, w, h, n=STREAM_FRAMES, seed=950, jitter=2, p_dropout=0.05)
+    recs, stats = fmt.frames_api.run_cpu(libs.load_oracle(), "orc_", frames, mode, dict(new_file=True))
+    return _frozen(frames, recs, stats)
+
+
+def cold_states(n):
+    st = np.zeros(n, dtype=p1l.STATE_DTYPE)
+    st["start"], st["stop"] = -32768, 32767
+    return st
+
+
+def _oracle_lines(fmt, rows, states, mode):
+    """-> (records, scan_done behind each pass or None)"""
+    out = fmt.lines_api.run_lines_with_states(libs.load_oracle(), fmt.line_prefix, rows, states, mode=mode)
+    return out if isinstance(out, tuple) else (out, None)
+
+
+@functools.lru_cache(maxsize=None)
+def lines_case(fmt_name, idx):
+    """-> (what is placed: (1, n_rows, w), which rows of it are lines (step), [(states, records, scan_done)] cold and preset from the decoded neighbour)"""
+    fmt = FORMATS[fmt_name]
+    w, _pad, _shift, how, mode = LINE_SHAPES[idx]
+    if how == "field":
+        block = make_frames(fmt, w, 2 * N_LINES, n=1, seed=970 + idx)
+        step = 2
+    else:
+        block = make_lines(fmt, w, seed=970 + idx)[None]
+        step = 1
+    rows = np.ascontiguousarray(block[0, ::step])
+    cold = cold_states(fmt.recs_per_line * len(rows))
+    recs, scans = _oracle_lines(fmt, rows, cold, mode)
+    warm = fmt.lines_api.states_from_records(recs, mode)            # before every line (pass): what the last one that read left behind
+    recs2, scans2 = _oracle_lines(fmt, rows, warm, mode)
+    for a in (block, cold, recs, warm, recs2) + tuple(s for s in (scans, scans2) if s is not None):
+        a.setflags(write=False)
+    return block, step, ((cold, recs, scans), (warm, recs2, scans2))
+
+
+def fused_frames(pcm_type):
+    h = FUSED_HEIGHT[pcm_type]
+    if pcm_type == STC007:
+        even = h + (h & 1)
+        # (40 lines per field, the last 13 of them in the picture: the interleaved stream of the generator needs 112 lines)
+        luma = synth.stc007_frames(N_FRAMES, seed=990, width=720, height=even, lines_per_field=40, noise_sigma=3.0)[0]
+        return np.ascontiguousarray(luma[:, :h])
+    return make_frames(FORMATS["pcm1" if pcm_type == PCM1 else "pcm16x0"], 720, h, seed=990 + pcm_type)
+
+
+@functools.lru_cache(maxsize=None)
+def fused_case(pcm_type):
+    """-> (frames, pairs, frame descriptors, frame statistics): the oracle's two workers over the contiguous frames, NEW_FILE and END_FILE - for STC-007
+    the helper of test_decode_frames.py, for the marker-less formats the same chain of their oracle halves."""
+    orc = libs.load_oracle()
+    frames = fused_frames(pcm_type)
+    if pcm_type == STC007:
+        from test_decode_frames import _oracle_chain
+        pairs, fr, stats = _oracle_chain(orc, frames)
+    elif pcm_type == PCM1:
+        from test_pcm1 import bin_to_line_recs
+        recs, stats = p1f.run_cpu(orc, "orc_", frames, 2, dict(new_file=True, end_file=True))
+        pairs, fr = p1.run_cpu(orc, "orc_", bin_to_line_recs(recs), p1.default_settings())
+    else:
+        recs, stats = p16f.run_cpu(orc, "orc_", frames, 2, dict(new_file=True, end_file=True))
+        pairs, fr = p16.run_cpu(orc, "orc_", recs, p16.default_settings())
+    return _frozen(frames, pairs, fr, np.ascontiguousarray(stats).view(np.uint8).reshape(-1, 32))
+
+
+# ---- outputs with guard records -------------------------------------------------------------------------------------------------------------
+def guarded(count, dtype):
+    """`count` records of `dtype`, every byte GUARD"""
+    dtype = np.dtype(dtype)
+    return np.full(count * dtype.itemsize, GUARD, dtype=np.uint8).view(dtype)
+
+
+def guards_intact(arr, count):
+    """Everything behind the first `count` records still holds the pattern."""
+    tail = np.ascontiguousarray(arr).view(np.uint8).reshape(len(arr), -1)[count:]
+    return bool((tail == GUARD).all())
+
+
+def first_difference(got, want):
+    if len(got) != len(want):
+        return "lengths %d / %d" % (len(got), len(want))
+    for i in range(len(got)):
+        if got[i].tobytes() != want[i].tobytes():
+            return "record %d:\n  got  %s\n  want %s" % (i, got[i], want[i])
+    return "equal"
+
+
+# ---- the entry points on host memory (the emulator build), strides passed through ---------------------------------------------------------------
+_FRAMES_ARGS = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                C.c_void_p]
+_LINES_ARGS = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint16, C.c_uint16, C.c_uint, C.c_int, C.c_void_p, C.c_size_t]
+_DECODE_ARGS = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint,
+                C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t,
+                C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.c_void_p]
+
+
+def bind(lib):
+    for fmt in FORMATS.values():
+        f = getattr(lib, fmt.frames_entry); f.restype = C.c_int; f.argtypes = _FRAMES_ARGS
+        f = getattr(lib, fmt.lines_entry); f.restype = C.c_int
+        f.argtypes = _LINES_ARGS + ([C.c_void_p] if fmt.recs_per_line == 1 else [C.c_void_p, C.c_void_p])
+        f = getattr(lib, fmt.count_fn); f.restype = C.c_size_t; f.argtypes = [C.c_int, C.c_int, C.c_uint]
+    lib.sdv_decode_frames.restype = C.c_int
+    lib.sdv_decode_frames.argtypes = _DECODE_ARGS
+    lib.sdv_set_pcm_type.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.sdv_set_pcm16x0_stitch_settings.argtypes = [C.c_void_p, C.c_void_p]
+    return ea.bind(lib)
+
+
+def emu_configure(lib, eng, mode):
+    lib.sdv_set_mode(eng, mode)
+    lib.sdv_set_bin_preset(eng, C.byref(libs.default_preset()))
+    lib.sdv_set_check_line_dup(eng, 1)
+
+
+def emu_frames_raw(lib, eng, fmt, ptr, row_stride, frame_stride, w, h, n, first_frame_no=1, new_file=False):
+    """One frame call on host memory.  The outputs hold two records and one descriptor more than the call needs, lines_cap and stats_cap say what it
+    needs.  -> (rc, all the records, all the descriptors, the count of records the call may write)"""
+    flags = 1 if new_file else 0
+    nrec = int(getattr(lib, fmt.count_fn)(h, n, flags))
+    recs, stats = guarded(nrec + 2, fmt.rec_dtype), guarded(n + 1, ea.STATS_DTYPE)
+    rc = getattr(lib, fmt.frames_entry)(eng, ptr, row_stride, frame_stride, w, h, n, first_frame_no, flags, recs.ctypes.data, nrec, stats.ctypes.data, n, None)
+    return rc, recs, stats, nrec
+
+
+def emu_frames(lib, eng, fmt, placed, first_frame=0, n=None, first_frame_no=1, new_file=False):
+    _, h, w = placed.shape
+    n = placed.shape[0] - first_frame if n is None else n
+    return emu_frames_raw(lib, eng, fmt, placed.ptr(first_frame), placed.row_stride, placed.frame_stride, w, h, n, first_frame_no, new_file)
+
+
+def emu_lines_raw(lib, eng, fmt, ptr, row_stride, w, n_lines, states):
+    """-> (rc, records with two guards behind them, scan_done marks with two guards behind them or None)"""
+    k = fmt.recs_per_line
+    recs = guarded(k * n_lines + 2, fmt.rec_dtype)
+    scans = guarded(k * n_lines + 2, np.uint8) if k == 3 else None
+    st = None if states is None else np.ascontiguousarray(states)
+    args = [eng, ptr, row_stride, w, n_lines, None if st is None else st.ctypes.data, 1, 1, 1, 0, 1, recs.ctypes.data, k * n_lines]
+    args += [scans.ctypes.data, None] if k == 3 else [None]
+    return getattr(lib, fmt.lines_entry)(*args), recs, scans
+
+
+def emu_decode(lib, eng, pcm_type, placed):
+    """sdv_decode_frames(NEW_FILE | END_FILE) on host memory, the caller's three outputs with guards behind their capacities.
+    -> (rc, pairs, n_pairs, descriptors, n_descriptors, statistics (rows of 32 bytes), n_statistics)"""
+    import stitch_api as sa
+    from test_decode_frames import FRASM
+    n, h, w = placed.shape
+    cap, fcap, nst = (n + 2) * 1800 + 8192, n + 16, n + 1
+    pairs, frames, stats = guarded(cap + 2, sa.PAIR_DTYPE), guarded(fcap + 1, FRASM[pcm_type]), guarded(nst + 1, ea.STATS_DTYPE)
+    npairs, nfr, npur, nm = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_uint64(0)
+    rc = lib.sdv_decode_frames(eng, pcm_type, placed.ptr(), placed.row_stride, placed.frame_stride, w, h, n, 1, 1 | 4, pairs.ctypes.data, cap, C.byref(npairs),
+                               frames.ctypes.data, fcap, C.byref(nfr), stats.ctypes.data, nst, 0, 0, None, 0, C.byref(npur), C.byref(nm), None)
+    return rc, pairs, npairs.value, frames, nfr.value, stats.view(np.uint8).reshape(-1, 32), nst
