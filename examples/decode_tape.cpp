@@ -11,10 +11,12 @@
  *       8-bit luma frames of a PCM-1600/1610/1630 tape -> sdv_pcm16x0_binarize_frames (VideoToDigital with TYPE_PCM16X0) ->
  *       sdv_pcm16x0_stitch_frames (the PCM16X0DataStitcher worker's body); the sub-line records never leave the device
  *
- *   decode_tape wav <luma.raw> <width> <height> <n_frames> <out.wav> [<mask mode 0..6>]
+ *   decode_tape wav <luma.raw> <width> <height> <n_frames> <out.wav> [<mask mode 0..6>] [auto|force]
  *       the whole chain of the application for an STC-007 file: sdv_binarize_frames -> sdv_stitch_frames -> sdv_audio_process (the
  *       AudioProcessor worker's loop, linear interpolation of dropouts by default) -> sdv_wav_pack + sdv_wav_header: the file SamplesToWAV
- *       writes, byte for byte; nothing but the luma goes to the device and nothing but the 16-bit PCM comes back
+ *       writes, byte for byte; nothing but the luma goes to the device and nothing but the 16-bit PCM comes back.  With `auto` or `force`
+ *       the 50/15 us de-emphasis network (sdv_audio_deemphasis) runs on the file's pairs in front of sdv_wav_pack - `force` is the one for
+ *       an STC-007 tape recorded with emphasis, whose pairs never carry the flag `auto` goes by; the reference leaves this to an audio editor
  *
  * Build (host code only, any C++ compiler): g++ -std=c++17 -O2 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude examples/decode_tape.cpp
  *        -Lsdvpcmdecoder_amd -lsdvpcm_hip -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$ORIGIN/../sdvpcmdecoder_amd' (build.py: build_example).
@@ -65,6 +67,9 @@ int main(int argc, char **argv)
     sdv_sample_pair *d_pairs = NULL;
     size_t n_pairs = 0, n_frames = 0;
     int rc = 0;
+    /* wav: the optional last word */
+    const std::string last_arg = argv[argc - 1];
+    const int deemph = last_arg == "auto" ? SDV_DEEMPH_AUTO : last_arg == "force" ? SDV_DEEMPH_FORCE : SDV_DEEMPH_OFF, wav_tail = deemph != SDV_DEEMPH_OFF ? 1 : 0;
     if (mode == "stc007" && argc == 8) {
         const int width = atoi(argv[3]), height = atoi(argv[4]), n = atoi(argv[5]);
         if (!read_file(argv[2], in) || in.size() != (size_t)width * height * n) { fprintf(stderr, "cannot read %s\n", argv[2]); return 1; }
@@ -89,9 +94,9 @@ int main(int argc, char **argv)
         sdv_run_info info; sdv_get_run_info(eng, &info);
         printf("stc007: %d frames -> %zu line records -> %zu sample pairs, %zu frame descriptors (binarize rounds %u)\n", n, n_lines, n_pairs, n_frames, info.rounds);
         (void)hipFree(d_luma); (void)hipFree(d_lines); (void)hipFree(d_stats); (void)hipFree(d_frames);
-    } else if (mode == "wav" && (argc == 7 || argc == 8)) {
+    } else if (mode == "wav" && (argc - wav_tail == 7 || argc - wav_tail == 8)) {
         const int width = atoi(argv[3]), height = atoi(argv[4]), n = atoi(argv[5]);
-        const int mask_mode = argc == 8 ? atoi(argv[7]) : SDV_DROP_INTER_LIN_WORD;
+        const int mask_mode = argc - wav_tail == 8 ? atoi(argv[7]) : SDV_DROP_INTER_LIN_WORD;
         if (!read_file(argv[2], in) || in.size() != (size_t)width * height * n) { fprintf(stderr, "cannot read %s\n", argv[2]); return 1; }
         uint8_t *d_luma = NULL; sdv_line_rec *d_lines = NULL; sdv_frame_stats *d_stats = NULL; sdv_frame_asm *d_frames = NULL;
         sdv_sample_pair *d_audio = NULL; sdv_audio_purge *d_purges = NULL; int16_t *d_pcm = NULL;
@@ -123,6 +128,10 @@ int main(int argc, char **argv)
         for (size_t k = 0; k < n_purges && !found; k++) if (purges[k].kind == SDV_AP_PURGE_NEW_FILE) { a = (size_t)purges[k].first_pair; b = k + 1 < n_purges ? (size_t)purges[k + 1].first_pair : n_audio; found = true; }
         if (!found || b <= a) { fprintf(stderr, "no audio came out\n"); rc = 5; }
         else {
+            if (deemph != SDV_DEEMPH_OFF) {         /* in place, on what goes into the file */
+                SDV_OKAY(sdv_set_deemphasis(eng, deemph));
+                SDV_OKAY(sdv_audio_deemphasis(eng, d_audio + a, b - a, d_audio + a, NULL));
+            }
             SDV_OKAY(sdv_wav_pack(eng, d_audio + a, b - a, d_pcm, NULL));
             HIP_OK(hipDeviceSynchronize());
             sdv_sample_pair last;

@@ -20,10 +20,11 @@
 extern "C" {
 #endif
 
-#define SDV_ABI_VERSION 5   /* 2: output capacities on sdv_binarize_frames / sdv_pcm1_binarize_lines; 3: sdv_audio_process, sdv_wav_pack, sdv_wav_header, sdv_decode_frames (additions only);
+#define SDV_ABI_VERSION 6   /* 2: output capacities on sdv_binarize_frames / sdv_pcm1_binarize_lines; 3: sdv_audio_process, sdv_wav_pack, sdv_wav_header, sdv_decode_frames (additions only);
                              * 4: sdv_pcm16x0_binarize_lines, sdv_audio_stalled, sdv_set_frame_flags, sdv_double_width, sdv_vis_render_lines (additions); the calls that used to refuse PCM-16x0 frames of the wrong size and the
                              * AudioProcessor's dead ends now follow the reference; the PCM-16x0 stitch state blob grew by conv_queue's remainder;
-                             * 5: sdv_run_info grew by frames_met (at its end), sdv_binarize_lines (addition) */
+                             * 5: sdv_run_info grew by frames_met (at its end), sdv_binarize_lines (addition);
+                             * 6: sdv_deemphasis_coeffs, sdv_set_deemphasis, sdv_reset_deemphasis, sdv_audio_deemphasis (additions only) */
 
 /* ---- status codes ---------------------------------------------------------------------------
  * 0..4 mirror Binarizer::LB_RET_* (binarizer.h:268-275); 16.. mirror STC007Deinterleaver::DI_RET_*
@@ -773,6 +774,38 @@ int sdv_wav_pack(sdv_engine *e, const sdv_sample_pair *pairs, size_t n, int16_t 
  * Host memory. */
 void sdv_wav_header(uint8_t hdr[44], uint64_t n_pairs, uint16_t last_sample_rate);
 
+/* ---- de-emphasis: the 50/15 us network on the pair stream (no reference equivalent: the reference leaves it to the user) ---- */
+/* H(s) = (1 + s T2) / (1 + s T1), T1 = 50 us, T2 = 15 us, by the bilinear transform without pre-warping (K = 2 fs):
+ *   b0 = (1 + K T2) / (1 + K T1), b1 = (1 - K T2) / (1 + K T1), a1 = (1 - K T1) / (1 + K T1)
+ * (gain 1 at DC, T2 / T1 at fs / 2).  fs is 44056 for a pair whose sample_rate is 44056, else 44100 - the rule of sdv_wav_header.
+ * Per channel the stream is walked in order with a state that is idle or running (fs, x_prev, y_prev), all arithmetic in double:
+ *   - SDV_DEEMPH_OFF: the call copies its input byte for byte; the state becomes idle;
+ *   - a service pair (service_type != 0), and a pair that is not selected, is copied unchanged; the state becomes idle.  A pair is selected
+ *     always with SDV_DEEMPH_FORCE, and where its emphasis field is not 0 with SDV_DEEMPH_AUTO.  The STC-007 chain never sets the field
+ *     (the reference does not either, stc007datastitcher.cpp:6719), so SDV_DEEMPH_FORCE is how the user of an STC-007 tape recorded
+ *     with emphasis asks for the network;
+ *   - a selected pair that finds the state idle, or running at another fs, starts a segment: x_prev = y_prev = x, the word stays (no click);
+ *   - any other selected pair: y = b0 x + b1 x_prev - a1 y_prev, x_prev = x, y_prev = y (unrounded), audio_word = y rounded to the nearest
+ *     integer (halves to even) and clamped to -32768 .. 32767;
+ *   - a selected pair leaves with emphasis = 0 - the stream is flat now, a second SDV_DEEMPH_AUTO pass changes nothing - and its other
+ *     fields as they came.
+ * The state lives in the engine, on the device, from one call of a stream to the next (calls of one stream go to one HIP stream);
+ * sdv_engine_create and sdv_reset_deemphasis leave it idle.  On the device the stream is worked on in tiles whose states come from the
+ * 128 pairs in front of them (what a state owes to older pairs is below the rounding of a double): a word differs from the walk above
+ * only where y lies within about 1e-11 of a half. */
+enum { SDV_DEEMPH_OFF = 0, SDV_DEEMPH_AUTO = 1, SDV_DEEMPH_FORCE = 2 };
+#define SDV_DEEMPH_TILE 1024        /* pairs per tile of the device's work (the tiles of a call start at its first pair) */
+#define SDV_DEEMPH_WARMUP 128       /* pairs in front of a tile its state is taken from */
+/* b0, b1, a1 for a pair of this sample_rate.  Host memory, no engine. */
+void sdv_deemphasis_coeffs(uint16_t sample_rate, double c[3]);
+/* The mode (SDV_DEEMPH_OFF when the engine is made); anything else: SDV_ERR_BAD_ARG.  The state stays as it is. */
+int sdv_set_deemphasis(sdv_engine *e, int mode);
+int sdv_reset_deemphasis(sdv_engine *e);
+/* n pairs from `pairs` to `out_pairs` (device pointers; asynchronous on `stream`, nothing is read back).  out_pairs may be `pairs` itself;
+ * any other overlap of the two is refused (SDV_ERR_BAD_ARG) and leaves the state untouched.  With a mode other than SDV_DEEMPH_OFF,
+ * sdv_decode_frames (with_audio != 0) makes this call on its out_pairs, in place, behind the AudioProcessor. */
+int sdv_audio_deemphasis(sdv_engine *e, const sdv_sample_pair *pairs, size_t n, sdv_sample_pair *out_pairs, void *stream);
+
 /* ---- the workers back to back: video frames -> PCMSamplePair (-> masked PCMSamplePair) in one call ------------------- */
 /* SURVEY 8b's "sdv_decode_frames": the format's VideoToDigital worker, its data stitcher and - on request - the AudioProcessor, one
  * after the other on `stream`, with the line records (and the raw pair stream) in buffers the engine owns, so that only the luma
@@ -787,7 +820,8 @@ void sdv_wav_header(uint8_t hdr[44], uint64_t n_pairs, uint16_t last_sample_rate
  * in the engine exactly as if the separate entry points had been called.  out_stats (n_frames records, + 1 with SDV_FLAG_END_FILE) may
  * be NULL.  with_audio != 0: the pair stream goes through sdv_audio_process (stop = audio_stop) before it is handed out; out_purges /
  * n_purges / n_masked then receive what that call reports (NULL otherwise).  The result is what the separate calls give - the parity
- * tests compare the two.  A failure of a later stage leaves the earlier stages' stream state advanced (the frames were binarized):
+ * tests compare the two.  With a de-emphasis mode other than SDV_DEEMPH_OFF (sdv_set_deemphasis) and with_audio != 0, sdv_audio_deemphasis
+ * runs on out_pairs behind that.  A failure of a later stage leaves the earlier stages' stream state advanced (the frames were binarized):
  * after an error other than SDV_ERR_BAD_ARG for a too small buffer of the last stage, reset the streams. */
 int sdv_decode_frames(sdv_engine *e, int pcm_type, const uint8_t *luma, size_t row_stride, size_t frame_stride, int width, int height,
                       int n_frames, uint32_t first_frame_no, unsigned flags,

@@ -688,3 +688,5 @@ __global__ void __launch_bounds__(64) sdv_k_ap_windows(sdva::ExecArgs a)
 }
 __global__ void __launch_bounds__(64) sdv_k_ap_emit(sdva::EmitArgs a) { sdva::emit_body(a, blockIdx.x, (int)threadIdx.x); }
 __global__ void __launch_bounds__(64) sdv_k_wav_pack(sdva::WavArgs a) { sdva::wav_body(a, (size_t)blockIdx.x * 64u + threadIdx.x); }
+
+#include "audio_deemph_device.h"      /* sdv_audio_deemphasis: the de-emphasis network behind the AudioProcessor */

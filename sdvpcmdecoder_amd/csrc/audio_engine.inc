@@ -6,8 +6,8 @@
  * stretches that each start from a purged window), prepare (work array + bitmaps) and the bitmap summary, the plan (one wave per
  * stretch, bitmaps only), a read-back of the per-stretch results, the sample work of the listed windows, a second read-back (mask
  * counts, the plan check), and - unless the caller's buffer was the work array - emit.  The stream state - what waits in the window,
- * the masking mode, the running sample index - is replaced only when the call succeeds.  sdv_decode_frames (the workers of a format
- * back to back) lives here too, being the last include of both builds.
+ * the masking mode, the running sample index - is replaced only when the call succeeds.  sdv_audio_deemphasis (two launches,
+ * nothing read back) and sdv_decode_frames (the workers of a format back to back) live here too, this being the last include of both builds.
  */
 #include <algorithm>
 
@@ -25,6 +25,9 @@ struct sdv_audio {
     rt::DevBuf<sdva::WinRec> d_wins; rt::DevBuf<uint32_t> d_win_base;
     /* sdv_decode_frames: what passes from stage to stage */
     rt::DevBuf<uint8_t> d_chain_recs; rt::DevBuf<sdv_frame_stats> d_chain_stats; rt::DevBuf<sdv_sample_pair> d_chain_pairs;
+    /* sdv_audio_deemphasis: the mode, the filter between two calls (on the device; de_idle: not looked at, the next call starts idle), a record per tile */
+    int de_mode; bool de_idle;
+    rt::DevBuf<sdva::DeState> d_de_state, d_de_tiles;
 };
 
 static sdv_audio *audio_get(sdv_engine *e)
@@ -32,6 +35,7 @@ static sdv_audio *audio_get(sdv_engine *e)
     if (e->audio) return e->audio;
     sdv_audio *t = new sdv_audio();
     t->mask_mode = SDV_DROP_IGNORE;     /* the constructor's DROP_IGNORE (audioprocessor.cpp:15) */
+    t->de_mode = SDV_DEEMPH_OFF; t->de_idle = true;
     e->audio = t;
     return t;
 }
@@ -353,6 +357,63 @@ void sdv_wav_header(uint8_t hdr[44], uint64_t n_pairs, uint16_t last_sample_rate
 }
 
 
+/* ---- de-emphasis (no reference equivalent: the definition is in include/sdvpcm.h) ------------------------------------------ */
+void sdv_deemphasis_coeffs(uint16_t sample_rate, double c[3])
+{
+    const double fs = sample_rate == 44056 ? 44056.0 : 44100.0, K = 2.0 * fs, T1 = 50e-6, T2 = 15e-6;
+    c[0] = (1.0 + K * T2) / (1.0 + K * T1);
+    c[1] = (1.0 - K * T2) / (1.0 + K * T1);
+    c[2] = (1.0 - K * T1) / (1.0 + K * T1);
+}
+
+int sdv_set_deemphasis(sdv_engine *e, int mode)
+{
+    if (!e) return SDV_ERR_BAD_ARG;
+    if (mode != SDV_DEEMPH_OFF && mode != SDV_DEEMPH_AUTO && mode != SDV_DEEMPH_FORCE) { set_error(e, "no such de-emphasis mode"); return SDV_ERR_BAD_ARG; }
+    audio_get(e)->de_mode = mode;
+    return SDV_OK;
+}
+
+int sdv_reset_deemphasis(sdv_engine *e)
+{
+    if (!e) return SDV_ERR_BAD_ARG;
+    audio_get(e)->de_idle = true;
+    return SDV_OK;
+}
+
+int sdv_audio_deemphasis(sdv_engine *e, const sdv_sample_pair *pairs, size_t n, sdv_sample_pair *out_pairs, void *stream)
+{
+    if (!e) return SDV_ERR_BAD_ARG;
+    sdv_audio *t = audio_get(e);
+    if (n == 0) { if (t->de_mode == SDV_DEEMPH_OFF) t->de_idle = true; return SDV_OK; }
+    if (!pairs) { set_error(e, "null sample pair buffer"); return SDV_ERR_NULL_LINES; }
+    if (!out_pairs) { set_error(e, "null output buffer"); return SDV_ERR_NULL_BLOCK; }
+    if (n >= 0x7FFF0000u) { set_error(e, "too many sample pairs in one call"); return SDV_ERR_BAD_ARG; }
+    if (out_pairs != pairs && (const char *)pairs < (const char *)(out_pairs + n) && (const char *)out_pairs < (const char *)(pairs + n)) {
+        set_error(e, "the output overlaps the input without being the input"); return SDV_ERR_BAD_ARG;
+    }
+    SDV_ON_DEVICE(e);
+    rt::stream_t s = (rt::stream_t)stream;
+    if (t->de_mode == SDV_DEEMPH_OFF) {
+        if (out_pairs != pairs) RT_CHECK(rt::d2d(out_pairs, pairs, n * sizeof(sdv_sample_pair), s));
+        t->de_idle = true;
+        return SDV_OK;
+    }
+    const size_t n_tiles = (n + sdva::DE_TILE - 1) / sdva::DE_TILE;
+    RT_CHECK(t->d_de_state.reserve(1));
+    RT_CHECK(t->d_de_tiles.reserve(n_tiles, n_tiles + n_tiles / 8 + 64));
+    sdva::DeArgs a; memset(&a, 0, sizeof(a));
+    a.in = pairs; a.out = out_pairs; a.n = n; a.tiles = t->d_de_tiles; a.state = t->d_de_state;
+    sdv_deemphasis_coeffs(44056, a.c[0]); sdv_deemphasis_coeffs(44100, a.c[1]);
+    a.force = t->de_mode == SDV_DEEMPH_FORCE ? 1 : 0; a.head_idle = t->de_idle ? 1 : 0;
+    /* the state in front of every tile from the input alone, then the tiles: the second pass reads nothing another tile writes (a call in place) */
+    RT_LAUNCH64(sdv_k_deemph_warm, n_tiles, a, s);
+    RT_LAUNCH64(sdv_k_deemph, n_tiles, a, s);
+    t->de_idle = false;
+    return SDV_OK;
+}
+
+
 /* The chains of the three formats, stage after stage (see include/sdvpcm.h).  Intermediate records live in buffers of the engine. */
 int sdv_decode_frames(sdv_engine *e, int pcm_type, const uint8_t *luma, size_t row_stride, size_t frame_stride, int width, int height,
                       int n_frames, uint32_t first_frame_no, unsigned flags,
@@ -458,7 +519,9 @@ int sdv_decode_frames(sdv_engine *e, int pcm_type, const uint8_t *luma, size_t r
     *n_frames_out = got_frames;
     if (rc != SDV_OK) { *n_pairs = got_pairs; return rc; }
     if (!with_audio) { *n_pairs = got_pairs; return SDV_OK; }
-    return sdv_audio_process(e, raw, got_pairs, audio_stop, out_pairs, pairs_cap, n_pairs, out_purges, purges_cap, n_purges, n_masked, stream);
+    rc = sdv_audio_process(e, raw, got_pairs, audio_stop, out_pairs, pairs_cap, n_pairs, out_purges, purges_cap, n_purges, n_masked, stream);
+    if (rc != SDV_OK || t->de_mode == SDV_DEEMPH_OFF) return rc;
+    return sdv_audio_deemphasis(e, out_pairs, *n_pairs, out_pairs, stream);         /* behind the AudioProcessor, where the pairs lie */
 }
 
 } // extern "C"

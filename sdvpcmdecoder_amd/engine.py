@@ -34,6 +34,7 @@ PCM_PCM1, PCM_PCM16X0, PCM_STC007 = 0, 1, 2
 TYPE_M2 = 3                      # VideoToDigital::TYPE_M2 (videotodigital.h:77)
 MODE_DRAFT, MODE_FAST, MODE_NORMAL, MODE_INSANE = 0, 1, 2, 3
 FLAG_NEW_FILE, FLAG_DOUBLED, FLAG_END_FILE = 1, 2, 4
+DEEMPH_OFF, DEEMPH_AUTO, DEEMPH_FORCE = 0, 1, 2       # sdv_set_deemphasis
 FRAME_EMPTY = 1                 # sdv_set_frame_flags: SDV_FRAME_EMPTY
 VIS_STC007_LINES, VIS_PCM1_LINES, VIS_PCM16X0_LINES, VIS_STC007_BLOCKS_NTSC, VIS_STC007_BLOCKS_PAL, VIS_STC007_ASM_NTSC, VIS_STC007_ASM_PAL = 0, 1, 2, 3, 4, 5, 6   # SDV_VIS_*
 
@@ -224,6 +225,12 @@ def load_library(path: str | None = None):
     lib.sdv_wav_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     lib.sdv_wav_header.argtypes = [C.c_void_p, C.c_uint64, C.c_uint16]
     lib.sdv_wav_header.restype = None
+    lib.sdv_deemphasis_coeffs.argtypes = [C.c_uint16, C.POINTER(C.c_double)]
+    lib.sdv_deemphasis_coeffs.restype = None
+    lib.sdv_set_deemphasis.argtypes = [C.c_void_p, C.c_int]
+    lib.sdv_reset_deemphasis.argtypes = [C.c_void_p]
+    lib.sdv_audio_deemphasis.restype = C.c_int
+    lib.sdv_audio_deemphasis.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     lib.sdv_decode_frames.restype = C.c_int
     lib.sdv_decode_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint,
                                       C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t,
@@ -860,6 +867,36 @@ class Engine:
         hdr = C.create_string_buffer(44)
         self.lib.sdv_wav_header(hdr, int(n_pairs), int(last_sample_rate))
         return hdr.raw
+
+    # ---- de-emphasis (50/15 us) of the pair stream: beyond the reference, which leaves it to the user --------------------
+    def set_deemphasis(self, mode: int):
+        """DEEMPH_OFF (the default) / DEEMPH_AUTO (pairs whose emphasis field is set) / DEEMPH_FORCE (every pair: what an STC-007 tape
+        needs, whose chain never sets the field).  Also switches the stage on behind the AudioProcessor of decode_frames(with_audio=True)."""
+        self._check(self.lib.sdv_set_deemphasis(self._h, int(mode)))
+
+    def reset_deemphasis(self):
+        """The filter forgets the stream it was on: the next selected pair starts a segment (no click)."""
+        self._check(self.lib.sdv_reset_deemphasis(self._h))
+
+    def audio_deemphasis(self, pairs, out=None, stream=None):
+        """The de-emphasis network over one burst of the stream: (n, 12) sdv_sample_pair -> (n, 12) on the device, asynchronous on the
+        stream.  out may be `pairs` itself (in place); the filter state stays in the engine from call to call."""
+        import torch
+        _check_out(pairs, 12, pairs.device, "pairs")
+        n = pairs.shape[0]
+        if out is None:
+            out = torch.empty((n, 12), dtype=torch.uint8, device=pairs.device)
+        _check_out(out, 12, pairs.device, "out")
+        assert out.shape[0] >= n
+        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else C.c_void_p(torch.cuda.current_stream(pairs.device).cuda_stream)
+        self._check(self.lib.sdv_audio_deemphasis(self._h, C.c_void_p(pairs.data_ptr()) if n else None, n, C.c_void_p(out.data_ptr()) if n else None, sptr))
+        return out[:n]
+
+    def deemphasis_coeffs(self, rate: int):
+        """(b0, b1, a1) of the network at the rate of a pair (44056, anything else reads 44100)."""
+        c = (C.c_double * 3)()
+        self.lib.sdv_deemphasis_coeffs(int(rate), c)
+        return tuple(c)
 
     def wav_files(self, out_pairs, purges):
         """The files SamplesToWAV leaves for an output stream of audio_process (one per NEW_FILE purge that is followed by at least one
