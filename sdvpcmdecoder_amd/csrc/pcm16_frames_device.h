@@ -703,140 +703,6 @@ __device__ inline void frame_body16(const FrameArgs16 &a16, Lds16 &lds, int f)
 #endif
 }
 
-/* ---- prediction of the incoming states (the PCM-1 model, pcm1_frames_device.h, with the longer window) ------------------------ */
-struct PredictArgs16 { State16 *states; const PrescanRes *prescan; int first, hi; FrameArgs f; };
-
-/* the median of a state's window of last valid coordinates (videotodigital.cpp:348-371), or false when it is empty */
-__device__ inline bool last_valid_median16(const State16 &s0, sdv_coord *out)
-{
-    const int n = s0.s.n_last_valid > LV16 ? LV16 : s0.s.n_last_valid;
-    if (n == 0 || s0.s.reset_stats) return false;
-    uint32_t keys[LV16];
-    for (int i = 0; i < n; i++) { const sdv_coord cc = i < COORD_HISTORY_DEPTH ? s0.s.last_valid[i] : s0.more[i - COORD_HISTORY_DEPTH]; keys[i] = coords_key(cc.data_start, cc.data_stop); }
-    for (int i = 1; i < n; i++) { const uint32_t x = keys[i]; int j = i; while (j > 0 && keys[j - 1] > x) { keys[j] = keys[j - 1]; j--; } keys[j] = x; }
-    out->data_start = key_start(keys[n / 2]); out->data_stop = key_stop(keys[n / 2]);
-    return true;
-}
-/* sticky = the frames in between are taken to decode with the coordinates the stream already carries (the median of the window of
- * last valid coordinates) instead of the ones their own prescan finds: what happens when the first line of a field is marked bad
- * (no Header in this format, :1193-1211) and the worker falls back on its history for the lines behind it (:1431-1451) */
-__device__ inline State16 predict_state16(const PredictArgs16 &a, int k, int base, bool sticky = false)
-{
-    const State16 s0 = a.states[base];
-    State16 p = s0;
-    sdv_coord carried; carried.data_start = 0; carried.data_stop = 0;
-    const bool use_carried = sticky && last_valid_median16(s0, &carried);
-    const uint8_t dbl = a.f.doubled;
-    int n_long = s0.s.reset_stats ? 0 : s0.s.n_long_valid;
-    sdv_coord lg[COORD_LONG_HISTORY];
-    for (int i = 0; i < COORD_LONG_HISTORY; i++) lg[i] = s0.s.long_valid[i];
-    bool touched = false;
-    sdv_coord last; last.data_start = 0; last.data_stop = 0;
-    uint8_t pref = prescan_ref_of(s0.s);
-    int j0 = base; if (k - j0 > COORD_LONG_HISTORY + 1) j0 = k - (COORD_LONG_HISTORY + 1);
-    for (int j = j0; j < k; j++) {
-        if (!prescan_runs(a.f, j)) continue;
-        uint32_t keys[COORD_CHECK_LINES]; uint8_t refs[COORD_CHECK_LINES]; int n = 0;
-        for (int q = 0; q < COORD_CHECK_LINES; q++) {
-            const PrescanRes r = a.prescan[(size_t)j * COORD_CHECK_LINES + q];
-            if (r.valid) { keys[n] = coords_key(r.start, r.stop); refs[n] = r.ref; n++; }
-            if (r.pad[1]) p.s.do_ref_lvl_sweep = a.f.mode == SDV_MODE_INSANE ? 1 : 0;
-        }
-        if (n == 0) continue;
-        for (int i = 1; i < n; i++)
-            for (int q = i; q > 0; q--) {
-                if (keys[q - 1] > keys[q]) { const uint32_t t = keys[q]; keys[q] = keys[q - 1]; keys[q - 1] = t; }
-                if (refs[q - 1] > refs[q]) { const uint8_t t = refs[q]; refs[q] = refs[q - 1]; refs[q - 1] = t; }
-            }
-        last.data_start = key_start(keys[n / 2]); last.data_stop = key_stop(keys[n / 2]);
-        if (use_carried) last = carried;
-        pref = refs[n / 2];
-        touched = true;
-        if (n_long == COORD_LONG_HISTORY) { for (int i = 0; i + 1 < COORD_LONG_HISTORY; i++) lg[i] = lg[i + 1]; n_long--; }
-        lg[n_long++] = last;
-    }
-    if (touched) {
-        p.s.reset_stats = 0;
-        p.s.n_last_valid = LV16;
-        for (int i = 0; i < COORD_HISTORY_DEPTH; i++) p.s.last_valid[i] = last;
-        for (int i = 0; i < LV16 - COORD_HISTORY_DEPTH; i++) p.more[i] = last;
-        p.s.n_long_valid = (uint8_t)n_long;
-        for (int i = 0; i < COORD_LONG_HISTORY; i++) { if (i < n_long) p.s.long_valid[i] = lg[i]; else { p.s.long_valid[i].data_start = 0; p.s.long_valid[i].data_stop = 0; } }
-        const uint16_t lm = dbl ? (uint16_t)((1u << COORD_HISTORY_DEPTH) - 1u) : 0, gm = dbl ? (uint16_t)((1u << n_long) - 1u) : 0;
-        p.s.last_valid_doubled_mask_lo = (uint8_t)(lm & 0xFF); p.s.last_valid_doubled_mask_hi = (uint8_t)(lm >> 8);
-        p.s.long_valid_doubled_mask = gm;
-        p.s._pad[1] = (uint8_t)(pref ^ 128);
-        p.s.bin.in_def_start = last.data_start; p.s.bin.in_def_stop = last.data_stop; p.s.bin.in_def_from_doubled = dbl;
-    } else if (!s0.s.reset_stats && a.f.mode == SDV_MODE_DRAFT) {
-        const int16_t cs = s0.s.bin.in_def_start, ce = s0.s.bin.in_def_stop;
-        if (s0.s.bin.in_def_reference >= a.f.preset.min_ref_lvl && (cs != NO_COORD_LEFT && ce != NO_COORD_RIGHT && cs < ce)) {
-            const int m = k - base;
-            p.s.bin.in_def_from_doubled = dbl;
-            p.s.n_last_valid = LV16;
-            for (int i = 0; i < COORD_HISTORY_DEPTH; i++) { p.s.last_valid[i].data_start = cs; p.s.last_valid[i].data_stop = ce; }
-            for (int i = 0; i < LV16 - COORD_HISTORY_DEPTH; i++) { p.more[i].data_start = cs; p.more[i].data_stop = ce; }
-            const int total = (int)s0.s.n_long_valid + m;
-            const int keep = total > COORD_LONG_HISTORY ? COORD_LONG_HISTORY : total, drop = total - keep;
-            for (int i = 0; i < COORD_LONG_HISTORY; i++) {
-                const int src = i + drop;
-                if (i >= keep) { p.s.long_valid[i].data_start = 0; p.s.long_valid[i].data_stop = 0; }
-                else if (src < (int)s0.s.n_long_valid) p.s.long_valid[i] = s0.s.long_valid[src];
-                else { p.s.long_valid[i].data_start = cs; p.s.long_valid[i].data_stop = ce; }
-            }
-            p.s.n_long_valid = (uint8_t)keep;
-            const uint16_t lm = dbl ? (uint16_t)((1u << COORD_HISTORY_DEPTH) - 1u) : 0, gm = dbl ? (uint16_t)((1u << keep) - 1u) : 0;
-            p.s.last_valid_doubled_mask_lo = (uint8_t)(lm & 0xFF); p.s.last_valid_doubled_mask_hi = (uint8_t)(lm >> 8);
-            p.s.long_valid_doubled_mask = gm;
-        }
-    }
-    return p;
-}
-struct RepairArgs16 { PredictArgs16 p; const State16 *states_out; const int *list, *head; const uint8_t *sticky; int n; const uint2 *frame_med; };
-/* Repair of a run of broken links (pcm16_frames_engine.inc).  Heads (head[i] == list[i]) take their predecessor's real outcome; they
- * come first in the list and are written by an earlier launch than the others read them.  A frame further into the run:
- *   DRAFT mode (the whole tuning is handed on): predicted again from its run's head - or, when that tells nothing new, its own
- *   predecessor's outcome;
- *   the other modes, first attempt (sticky[i]): predicted again from the head with the coordinates the stream carries (predict_state16);
- *   later attempts: its own predecessor's outcome (what a frame hands on depends little on what it was handed), except for the
- *   multi-frame history, which only passes through the frames - that is rebuilt from the head's true state and what the frames
- *   since then have pushed themselves, so that one wrong median does not need sixteen rounds to leave the chain. */
-__device__ inline void repair_body16(const RepairArgs16 &a, int i)
-{
-    const int k = a.list[i], h = a.head[i];
-    if (h == k) { a.p.states[k] = a.states_out[k - 1]; return; }
-    if (a.p.f.mode == SDV_MODE_DRAFT || a.sticky[i]) {
-        State16 p = predict_state16(a.p, k, h, a.p.f.mode != SDV_MODE_DRAFT);
-        const State16 cur = a.p.states[k];
-        uint32_t x[sizeof(State16) / 4], y[sizeof(State16) / 4];
-        __builtin_memcpy(x, &p, sizeof(p));
-        __builtin_memcpy(y, &cur, sizeof(cur));
-        bool same = true;
-        for (unsigned q = 0; q < sizeof(State16) / 4; q++) same = same && (x[q] == y[q]);
-        a.p.states[k] = same ? a.states_out[k - 1] : p;
-        return;
-    }
-    State16 p = a.states_out[k - 1];
-    const State16 h_in = a.p.states[h];
-    int n_long = h_in.s.reset_stats ? 0 : h_in.s.n_long_valid;
-    sdv_coord lg[COORD_LONG_HISTORY];
-    for (int q = 0; q < COORD_LONG_HISTORY; q++) lg[q] = h_in.s.long_valid[q];
-    for (int j = h; j < k; j++) {
-        const uint2 m = a.frame_med[j];
-        if (!m.y) continue;
-        if (n_long == COORD_LONG_HISTORY) { for (int q = 0; q + 1 < COORD_LONG_HISTORY; q++) lg[q] = lg[q + 1]; n_long--; }
-        lg[n_long].data_start = key_start(m.x); lg[n_long].data_stop = key_stop(m.x); n_long++;
-    }
-    p.s.n_long_valid = (uint8_t)n_long;
-    for (int q = 0; q < COORD_LONG_HISTORY; q++) { if (q < n_long) p.s.long_valid[q] = lg[q]; else { p.s.long_valid[q].data_start = 0; p.s.long_valid[q].data_stop = 0; } }
-    p.s.long_valid_doubled_mask = a.p.f.doubled ? (uint16_t)((1u << n_long) - 1u) : 0;
-    a.p.states[k] = p;
-}
-struct VerifyArgs16 { FrameArgs f; const State16 *states_in, *states_out; };
-__device__ inline void verify_body16(const VerifyArgs16 &a, int k)
-{
-    a.f.flag[k] = link_holds16(a.f, k, a.states_out[k], a.states_in[k + 1]) ? VF_OK : VF_BREAK;
-}
-
 } // namespace sdvp16f
 
 #ifndef SDV_P16_WAVES_PER_EU
@@ -868,20 +734,3 @@ __global__ void __launch_bounds__(64, SDV_P16F_LEAN_WAVES_PER_EU) sdv_k_pcm16_fr
     const int f = a.f.frame_list ? a.f.frame_list[blockIdx.x] : a.f.frame_lo + (int)blockIdx.x;
     sdvp16f::frame_body16<false, true>(a, lds, f);
 }
-#ifndef SDV_EMU
-__global__ void sdv_k_pcm16_predict(sdvp16f::PredictArgs16 a)
-{
-    const int k = a.first + 1 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (k < a.hi) a.states[k] = sdvp16f::predict_state16(a, k, a.first, true);
-}
-__global__ void sdv_k_pcm16_repair(sdvp16f::RepairArgs16 a, int lo, int hi)
-{
-    const int i = lo + (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (i < hi) sdvp16f::repair_body16(a, i);
-}
-__global__ void sdv_k_pcm16_verify(sdvp16f::VerifyArgs16 a)
-{
-    const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (k + 1 < a.f.n_total) sdvp16f::verify_body16(a, k);
-}
-#endif

@@ -12,7 +12,8 @@
  *                        Binarizer (setGoodParameters / setDataCoordinates / setBWLevels), with the per-line bookkeeping of the
  *                        worker (Header lines, duplicate-line detection, coordinate damper, statistics).  Frames run in parallel
  *                        from predicted incoming states; every frame checks the link to its successor itself (stc007_device.h,
- *                        v2d_store_state) and the host repeats the frames behind broken links (pcm1_frames_engine.inc).
+ *                        v2d_store_state) and the host repeats the frames behind broken links (markerless_frames_engine.inc;
+ *                        the model of the states: markerless_chain_device.h).
  */
 #pragma once
 #include "pcm1_bin_device.h"
@@ -642,150 +643,6 @@ __device__ inline void frame_body1(const FrameArgs1 &a1, P1Lds &lds, int f)
     v2d1_store_state(w, lds.w, &a.states_out[f], a);
 }
 
-/* ---- prediction of the incoming states ------------------------------------------------------------------------------------ */
-/* states[k] for the frames behind an anchor (first_of as for STC-007, engine.inc): what the worker carries from frame to frame is the
- * coordinate history - the last nine valid lines, the medians of the last sixteen frames - and prescan_ref.  On a tape that plays
- * every line of a frame reads with the coordinates its prescan found, so all of that follows from the prescan results, which are
- * known before any frame is decoded.  DRAFT mode has no prescan: there the state is handed on as it is, like for STC-007. */
-struct PredictArgs1 { sdv_v2d_state *states; const PrescanRes *prescan; int first, hi; const int *first_of; FrameArgs f; };
-
-/* the median of a state's window of last valid coordinates (videotodigital.cpp:348-371), or false when it is empty */
-__device__ inline bool last_valid_median1(const sdv_v2d_state &s0, sdv_coord *out)
-{
-    const int n = s0.n_last_valid > COORD_HISTORY_DEPTH ? COORD_HISTORY_DEPTH : s0.n_last_valid;
-    if (n == 0 || s0.reset_stats) return false;
-    uint32_t keys[COORD_HISTORY_DEPTH];
-    for (int i = 0; i < n; i++) keys[i] = coords_key(s0.last_valid[i].data_start, s0.last_valid[i].data_stop);
-    for (int i = 1; i < n; i++) { const uint32_t x = keys[i]; int j = i; while (j > 0 && keys[j - 1] > x) { keys[j] = keys[j - 1]; j--; } keys[j] = x; }
-    out->data_start = key_start(keys[n / 2]); out->data_stop = key_stop(keys[n / 2]);
-    return true;
-}
-/* sticky = the frames in between are taken to decode with the coordinates the stream already carries (the median of the window of
- * last valid coordinates) instead of the ones their own prescan finds: what happens on a tape without Header lines, where the first
- * line of a field is marked bad (:1193-1211) and the worker falls back on its history for the lines behind it (:1431-1451) */
-__device__ inline sdv_v2d_state predict_state1(const PredictArgs1 &a, int k, int base, bool sticky = false)
-{
-    const sdv_v2d_state s0 = a.states[base];
-    sdv_v2d_state p = s0;
-    sdv_coord carried; carried.data_start = 0; carried.data_stop = 0;
-    const bool use_carried = sticky && last_valid_median1(s0, &carried);
-    const uint8_t dbl = a.f.doubled;
-    int n_long = s0.reset_stats ? 0 : s0.n_long_valid;       /* a worker that starts over clears its histories first (:778-790) */
-    sdv_coord lg[COORD_LONG_HISTORY];
-    for (int i = 0; i < COORD_LONG_HISTORY; i++) lg[i] = s0.long_valid[i];
-    bool touched = false;
-    sdv_coord last; last.data_start = 0; last.data_stop = 0;
-    uint8_t pref = prescan_ref_of(s0);
-    /* only the last sixteen frames in between can still be seen in the history */
-    int j0 = base; if (k - j0 > COORD_LONG_HISTORY + 1) j0 = k - (COORD_LONG_HISTORY + 1);
-    for (int j = j0; j < k; j++) {
-        if (!prescan_runs(a.f, j)) continue;
-        uint32_t keys[COORD_CHECK_LINES]; uint8_t refs[COORD_CHECK_LINES]; int n = 0;
-        for (int q = 0; q < COORD_CHECK_LINES; q++) {
-            const PrescanRes r = a.prescan[(size_t)j * COORD_CHECK_LINES + q];
-            if (r.valid) { keys[n] = coords_key(r.start, r.stop); refs[n] = r.ref; n++; }
-            if (r.pad[1]) p.do_ref_lvl_sweep = a.f.mode == SDV_MODE_INSANE ? 1 : 0;
-        }
-        if (n == 0) continue;
-        for (int i = 1; i < n; i++)
-            for (int q = i; q > 0; q--) {
-                if (keys[q - 1] > keys[q]) { const uint32_t t = keys[q]; keys[q] = keys[q - 1]; keys[q - 1] = t; }
-                if (refs[q - 1] > refs[q]) { const uint8_t t = refs[q]; refs[q] = refs[q - 1]; refs[q - 1] = t; }
-            }
-        last.data_start = key_start(keys[n / 2]); last.data_stop = key_stop(keys[n / 2]);
-        if (use_carried) last = carried;
-        pref = refs[n / 2];
-        touched = true;
-        if (n_long == COORD_LONG_HISTORY) { for (int i = 0; i + 1 < COORD_LONG_HISTORY; i++) lg[i] = lg[i + 1]; n_long--; }
-        lg[n_long++] = last;
-    }
-    if (touched) {
-        p.reset_stats = 0;
-        p.n_last_valid = COORD_HISTORY_DEPTH;
-        for (int i = 0; i < COORD_HISTORY_DEPTH; i++) p.last_valid[i] = last;
-        p.n_long_valid = (uint8_t)n_long;
-        for (int i = 0; i < COORD_LONG_HISTORY; i++) { if (i < n_long) p.long_valid[i] = lg[i]; else { p.long_valid[i].data_start = 0; p.long_valid[i].data_stop = 0; } }
-        const uint16_t lm = dbl ? (uint16_t)((1u << COORD_HISTORY_DEPTH) - 1u) : 0, gm = dbl ? (uint16_t)((1u << n_long) - 1u) : 0;
-        p.last_valid_doubled_mask_lo = (uint8_t)(lm & 0xFF); p.last_valid_doubled_mask_hi = (uint8_t)(lm >> 8);
-        p.long_valid_doubled_mask = gm;
-        p._pad[1] = (uint8_t)(pref ^ 128);
-        p.bin.in_def_start = last.data_start; p.bin.in_def_stop = last.data_stop; p.bin.in_def_from_doubled = dbl;
-    } else if (!touched && !s0.reset_stats && a.f.mode == SDV_MODE_DRAFT) {
-        /* DRAFT: the tuning is handed on; a frame that plays fills the histories with the pair it inherited (the STC-007 model) */
-        const int16_t cs = s0.bin.in_def_start, ce = s0.bin.in_def_stop;
-        if (s0.bin.in_def_reference >= a.f.preset.min_ref_lvl && (cs != NO_COORD_LEFT && ce != NO_COORD_RIGHT && cs < ce)) {
-            const int m = k - base;
-            p.bin.in_def_from_doubled = dbl;
-            p.n_last_valid = COORD_HISTORY_DEPTH;
-            for (int i = 0; i < COORD_HISTORY_DEPTH; i++) { p.last_valid[i].data_start = cs; p.last_valid[i].data_stop = ce; }
-            const int total = (int)s0.n_long_valid + m;
-            const int keep = total > COORD_LONG_HISTORY ? COORD_LONG_HISTORY : total, drop = total - keep;
-            for (int i = 0; i < COORD_LONG_HISTORY; i++) {
-                const int src = i + drop;
-                if (i >= keep) { p.long_valid[i].data_start = 0; p.long_valid[i].data_stop = 0; }
-                else if (src < (int)s0.n_long_valid) p.long_valid[i] = s0.long_valid[src];
-                else { p.long_valid[i].data_start = cs; p.long_valid[i].data_stop = ce; }
-            }
-            p.n_long_valid = (uint8_t)keep;
-            const uint16_t lm = dbl ? (uint16_t)((1u << COORD_HISTORY_DEPTH) - 1u) : 0, gm = dbl ? (uint16_t)((1u << keep) - 1u) : 0;
-            p.last_valid_doubled_mask_lo = (uint8_t)(lm & 0xFF); p.last_valid_doubled_mask_hi = (uint8_t)(lm >> 8);
-            p.long_valid_doubled_mask = gm;
-        }
-    }
-    return p;
-}
-__device__ inline void predict_body1(const PredictArgs1 &a, int k)
-{
-    const int base = a.first_of ? a.first_of[k - a.first] : a.first;
-    if (base != k) a.states[k] = predict_state1(a, k, base);
-}
-
-/* Repair of a run of broken links (pcm1_frames_engine.inc): the frame behind the first link of the run has been given what its
- * predecessor really handed on (sdv_k_anchor).  A frame list[i] further into the run, whose run starts at frame head[i]:
- *   DRAFT mode (the whole tuning is handed on): predicted again from its run's head - or, when that tells nothing new, its own
- *   predecessor's outcome;
- *   the other modes, first attempt (sticky[i]): predicted again from the head with the coordinates the stream carries (predict_state1);
- *   later attempts: its own predecessor's outcome (what a frame hands on depends little on what it was handed), except for the
- *   multi-frame history, which only passes through the frames - that is rebuilt from the head's true state and what the frames
- *   since then have pushed themselves, so that one wrong median does not need sixteen rounds to leave the chain. */
-struct RepairArgs1 { PredictArgs1 p; const sdv_v2d_state *states_out; const int *list, *head; const uint8_t *sticky; int n; const uint2 *frame_med; };
-__device__ inline void repair_body1(const RepairArgs1 &a, int i)
-{
-    const int k = a.list[i], h = a.head[i];
-    if (a.p.f.mode == SDV_MODE_DRAFT || a.sticky[i]) {
-        sdv_v2d_state p = predict_state1(a.p, k, h, a.p.f.mode != SDV_MODE_DRAFT);
-        const sdv_v2d_state cur = a.p.states[k];
-        uint32_t x[sizeof(sdv_v2d_state) / 4], y[sizeof(sdv_v2d_state) / 4];
-        __builtin_memcpy(x, &p, sizeof(p));
-        __builtin_memcpy(y, &cur, sizeof(cur));
-        bool same = true;
-        for (unsigned q = 0; q < sizeof(sdv_v2d_state) / 4; q++) same = same && (x[q] == y[q]);
-        a.p.states[k] = same ? a.states_out[k - 1] : p;
-        return;
-    }
-    sdv_v2d_state p = a.states_out[k - 1];
-    const sdv_v2d_state h_in = a.p.states[h];
-    int n_long = h_in.reset_stats ? 0 : h_in.n_long_valid;
-    sdv_coord lg[COORD_LONG_HISTORY];
-    for (int q = 0; q < COORD_LONG_HISTORY; q++) lg[q] = h_in.long_valid[q];
-    for (int j = h; j < k; j++) {
-        const uint2 m = a.frame_med[j];
-        if (!m.y) continue;
-        if (n_long == COORD_LONG_HISTORY) { for (int q = 0; q + 1 < COORD_LONG_HISTORY; q++) lg[q] = lg[q + 1]; n_long--; }
-        lg[n_long].data_start = key_start(m.x); lg[n_long].data_stop = key_stop(m.x); n_long++;
-    }
-    p.n_long_valid = (uint8_t)n_long;
-    for (int q = 0; q < COORD_LONG_HISTORY; q++) { if (q < n_long) p.long_valid[q] = lg[q]; else { p.long_valid[q].data_start = 0; p.long_valid[q].data_stop = 0; } }
-    p.long_valid_doubled_mask = a.p.f.doubled ? (uint16_t)((1u << n_long) - 1u) : 0;
-    a.p.states[k] = p;
-}
-/* the links of the chain after a round: flag[k] for k in [0, n - 1) */
-struct VerifyArgs1 { FrameArgs f; };
-__device__ inline void verify_body1(const VerifyArgs1 &a, int k)
-{
-    a.f.flag[k] = link_holds1(a.f, k, a.f.states_out[k], a.f.states_in[k + 1]) ? VF_OK : VF_BREAK;
-}
-
 } // namespace sdvp1f
 
 /* two builds of the two kernels: MODE_INSANE (with the reference level sweep) and every other mode (process_line_p1) */
@@ -817,20 +674,3 @@ __global__ void __launch_bounds__(64, SDV_P1F_LEAN_WAVES_PER_EU) sdv_k_pcm1_fram
     const int f = a.f.frame_list ? a.f.frame_list[blockIdx.x] : a.f.frame_lo + (int)blockIdx.x;
     sdvp1f::frame_body1<false, true>(a, lds, f);
 }
-#ifndef SDV_EMU
-__global__ void sdv_k_pcm1_predict(sdvp1f::PredictArgs1 a)
-{
-    const int k = a.first + (a.first_of ? 0 : 1) + (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (k < a.hi) sdvp1f::predict_body1(a, k);
-}
-__global__ void sdv_k_pcm1_repair(sdvp1f::RepairArgs1 a)
-{
-    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (i < a.n) sdvp1f::repair_body1(a, i);
-}
-__global__ void sdv_k_pcm1_verify(sdvp1f::VerifyArgs1 a)
-{
-    const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (k + 1 < a.f.n_total) sdvp1f::verify_body1(a, k);
-}
-#endif

@@ -63,7 +63,7 @@ FUSED_HEIGHT = {STC007: 25, PCM1: 25, PCM16X0: 24}
 def lean_build_alone(shape):
     """Frames that play and whose prescan runs (every mode but DRAFT, more than COORD_CHECK_PARTS = 6 lines in the frame buffer: h + 3 of them) are
     decoded by the lean build of the frame kernel alone - the one that gathers bytes at row_stride and frame_stride itself; it hands a frame to the
-    full build only when a line does not read from what it inherits (pcm1_frames_engine.inc), and the lines of the tables read
+    full build only when a line does not read from what it inherits (markerless_frames_engine.inc), and the lines of the tables read
     (test_the_frames_of_the_tables_read).  A lean build that looks at the wrong rows gives every frame up; the records then still come out right,
     from the full build, and only sdv_run_info.frames_general tells."""
     _w, h, _pad, _shift, _gap, mode = shape

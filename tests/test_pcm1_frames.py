@@ -88,6 +88,11 @@ def test_emu_matches_oracle(name, emu_lib, oracle_lib):
         assert info.rounds == 1, "a tape that plays is decoded in one round (every frame's incoming state follows from the prescans)"
 
 
+# (rounds, frames_launched) of the two calls of test_emu_stream_in_two_calls, by (mode, seed): the schedule as measured before the two drivers' schedulers
+# became one (profiles/markerless_scheduler_notes.md).  Equal output does not pin the schedule - any schedule that settles gives the sequential result.
+TWO_CALLS_SCHEDULE = {(2, 503): ((3, 50), (3, 50)), (0, 502): ((3, 61), (3, 61)), (0, 505): ((2, 47), (1, 16)), (1, 504): ((1, 32), (1, 32))}
+
+
 @pytest.mark.parametrize("mode,kw", [(2, dict(seed=503, jitter=3, noise_sigma=4.0)), (0, dict(seed=502, p_dropout=0.1, noise_sigma=5.0)),
                                      (0, dict(seed=505)), (1, dict(seed=504, p_dropout=0.15, noise_sigma=5.0))])
 def test_emu_stream_in_two_calls(mode, kw, emu_lib, oracle_lib):
@@ -102,10 +107,12 @@ def test_emu_stream_in_two_calls(mode, kw, emu_lib, oracle_lib):
     rc1, g1, t1 = pf.run_engine(emu_lib, eng, luma, mode, {})
     i1 = _info(emu_lib, eng)
     rc2, g2, t2 = pf.run_engine(emu_lib, eng, luma, mode, {}, first_frame_no=17, configure=False)
+    i2 = _info(emu_lib, eng)
     emu_lib.sdv_engine_destroy(eng)
     assert rc1 == 0 and g1.tobytes() == w1.tobytes() and t1.tobytes() == s1.tobytes(), _diff(g1, w1, t1, s1)
     assert rc2 == 0 and g2.tobytes() == w2.tobytes() and t2.tobytes() == s2.tobytes(), _diff(g2, w2, t2, s2)
-    assert i1.rounds <= 5
+    assert i1.rounds <= 5 and i2.rounds <= 5
+    assert ((i1.rounds, i1.frames_launched), (i2.rounds, i2.frames_launched)) == TWO_CALLS_SCHEDULE[mode, kw["seed"]]
 
 
 def test_emu_bad_arguments(emu_lib):
