@@ -334,8 +334,8 @@ size_t sdv_binarize_records(int height, int n_frames, unsigned flags);
  *  out_stats    device pointer to stats_cap rows, one FrameBinDescriptor per frame (signal guiUpdFrameBin); one more row with
  *               SDV_FLAG_END_FILE (the worker reports the filler frame too).
  *  frame_stride at least (height-1)*row_stride + width when n_frames > 1 (frames do not overlap), else SDV_ERR_BAD_ARG.
- *  stream       hipStream_t (NULL = default stream).  The call returns after the device work of the
- *               batch has been validated (it synchronises `stream` at least once).
+ *  stream       hipStream_t (NULL = default stream).  All device work goes to it.  The call returns when the outputs are
+ *               complete: behind the read-back of the last round, which validates the batch (it synchronises `stream` in every round).
  * Returns SDV_OK or an SDV_ERR_* code; invalid input is refused up front like the reference's early
  * returns (binarizer.cpp:465-478, 582-589). */
 int sdv_binarize_frames(sdv_engine *e, const uint8_t *luma, size_t row_stride, size_t frame_stride, int width, int height,
@@ -384,7 +384,10 @@ int sdv_get_stitch_info(const sdv_engine *e, sdv_stitch_info *out);
  * checkpointing, and handing a tape over to the engine of the next GPU when one stream is sharded across GPUs (the "field
  * seam" that travels by all-gather).  sdv_set_stitch_state drops lines that still wait for a successor
  * frame.  sdv_saturate_stitch_stats fills the two statistics rings with their current majority - for an engine that joined
- * the stream after a short warm-up and is about to compare its state with the true one. */
+ * the stream after a short warm-up and is about to compare its state with the true one.
+ * These entries, sdv_reset_stitcher and their PCM-16x0 twins take no stream: their small copies go to the NULL stream of the engine's device and are
+ * complete when the call returns, so a stitch call on any stream may follow at once.  Like every call of an engine they are made while no other call of
+ * that engine runs; the stitch entries return when their outputs are complete, so nothing of the engine is in flight then. */
 size_t sdv_stitch_state_size(void);
 int sdv_get_stitch_state(sdv_engine *e, void *out, size_t cap);
 int sdv_set_stitch_state(sdv_engine *e, const void *in, size_t n);
@@ -479,7 +482,8 @@ typedef struct sdv_pcm16x0_bin_rec {
  * VideoLine::scan_done mark like in the reference (a line whose coordinate search has run is not searched again, binarizer.cpp:5819-6042),
  * which starts cleared.  out_lines takes three records per line (lines_cap >= 3 n_lines), out_scan_done (or NULL) the mark behind each pass.
  * Mode, fine settings, coord_search, flags, service / empty lines, SDV_MODE_INSANE and errors as for sdv_pcm1_binarize_lines;
- * SDV_ERR_SHORT_LINE under 193 px.  The twin of sdv_pcm1_binarize_lines for callers that keep VideoToDigital's frame loop. */
+ * SDV_ERR_SHORT_LINE under 193 px.  The twin of sdv_pcm1_binarize_lines for callers that keep VideoToDigital's frame loop.
+ * Device pointers; asynchronous on `stream` (one launch, nothing is read back). */
 int sdv_pcm16x0_binarize_lines(sdv_engine *e, const uint8_t *luma, size_t row_stride, int width, size_t n_lines,
                                const sdv_bin_state *presets, uint32_t frame_number, uint16_t first_line, uint16_t line_step,
                                unsigned flags, int coord_search, sdv_pcm16x0_bin_rec *out_lines, size_t lines_cap, uint8_t *out_scan_done, void *stream);
@@ -822,7 +826,10 @@ int sdv_audio_deemphasis(sdv_engine *e, const sdv_sample_pair *pairs, size_t n, 
  * n_purges / n_masked then receive what that call reports (NULL otherwise).  The result is what the separate calls give - the parity
  * tests compare the two.  With a de-emphasis mode other than SDV_DEEMPH_OFF (sdv_set_deemphasis) and with_audio != 0, sdv_audio_deemphasis
  * runs on out_pairs behind that.  A failure of a later stage leaves the earlier stages' stream state advanced (the frames were binarized):
- * after an error other than SDV_ERR_BAD_ARG for a too small buffer of the last stage, reset the streams. */
+ * after an error other than SDV_ERR_BAD_ARG for a too small buffer of the last stage, reset the streams.
+ * All device work goes to `stream`.  The call returns when the outputs are complete (its last stage is sdv_*_stitch_frames or sdv_audio_process, which
+ * do) - except with a de-emphasis mode other than SDV_DEEMPH_OFF and with_audio != 0: the pass over out_pairs is then left running on `stream`
+ * (sdv_audio_deemphasis is asynchronous), the other outputs are complete. */
 int sdv_decode_frames(sdv_engine *e, int pcm_type, const uint8_t *luma, size_t row_stride, size_t frame_stride, int width, int height,
                       int n_frames, uint32_t first_frame_no, unsigned flags,
                       sdv_sample_pair *out_pairs, size_t pairs_cap, size_t *n_pairs, void *out_frames, size_t frames_cap, size_t *n_frames_out,
@@ -877,7 +884,7 @@ size_t sdv_stitch_line_counts(sdv_engine *e, uint32_t *per_turn, size_t cap);
  * keeps the last canvas per kind for the next call like RenderPCM keeps its QImage; a canvas nothing was drawn on yet is 0xFF000000 (the
  * reference leaves those rows uninitialised).  Records behind the last END_FRAME are not drawn: pass whole frames.  *n_frames = frames in
  * `recs`; more than canvases_cap: SDV_ERR_BAD_ARG, nothing drawn.  Device pointers; the call reads one small array back (the frame count)
- * and leaves the drawing running on `stream`.  sdv_vis_reset: a new canvas (RenderPCM::startNewFrame).
+ * and leaves the drawing running on `stream`.  sdv_vis_reset: a new canvas (RenderPCM::startNewFrame), asynchronous on `stream`.
  *   SDV_VIS_PCM1_ASM         sdv_pcm1_asm_line_rec     624 x 490   (startPCM1SubFrame: the assembled-lines window of PCM-1, renderNewLine(PCM1SubLine),
  *                                                                   renderpcm.cpp:626-741, on what sdv_set_pcm1_stitch_line_output wrote: 1470 records are a
  *                                                                   frame - no END_FRAME records here -, records marked SDV_P1S_SKIP are not drawn)

@@ -168,6 +168,7 @@ int sdv_get_stitch_info(const sdv_engine *ce, sdv_stitch_info *out)
 int sdv_reset_stitcher(sdv_engine *e)
 {
     if (!e) return SDV_ERR_BAD_ARG;
+    SDV_ON_DEVICE(e);
     sdv_stitcher *t = stitcher_get(e);
     stitcher_reset_host(t);
     t->n_carry = 0; t->carry_frames = 0; t->steady = false; t->guess_pairs = t->guess_frasm = 0;
@@ -187,6 +188,7 @@ size_t sdv_stitch_state_size(void) { return sizeof(sdv_stitch_state_blob); }
 int sdv_get_stitch_state(sdv_engine *e, void *out, size_t cap)
 {
     if (!e || !out || cap < sizeof(sdv_stitch_state_blob)) return SDV_ERR_BAD_ARG;
+    SDV_ON_DEVICE(e);
     sdv_stitcher *t = stitcher_get(e);
     sdv_stitch_state_blob *b = (sdv_stitch_state_blob *)out;
     memset(b, 0, sizeof(*b));
@@ -205,6 +207,7 @@ int sdv_set_stitch_state(sdv_engine *e, const void *in, size_t n)
     if (!e || !in || n < sizeof(sdv_stitch_state_blob)) return SDV_ERR_BAD_ARG;
     const sdv_stitch_state_blob *b = (const sdv_stitch_state_blob *)in;
     if (b->magic != 0x53445653u) { set_error(e, "not a stitch state"); return SDV_ERR_BAD_ARG; }
+    SDV_ON_DEVICE(e);           /* (the hand-over chain is allocated here when the stitcher is fresh: on the engine's device, not the caller's) */
     sdv_stitcher *t = stitcher_get(e);
     t->ring_order.clear(); t->ring_res.clear();
     for (int i = 0; i < 65; i++) { t->ring_order.push(b->ring_order[i]); t->ring_res.push(b->ring_res[i]); }
