@@ -191,7 +191,14 @@ int main(int argc, char **argv)
     const int width = atoi(argv[2]), height = atoi(argv[3]), n_frames = atoi(argv[4]);
     const std::string prefix = argv[5], comm_arg = argc > 6 ? argv[6] : "rccl";
     const int warmup = argc > 7 ? atoi(argv[7]) : 20, stitch_warmup = argc > 8 ? atoi(argv[8]) : 4;
-    if (rank < 0 || rank >= world || n_frames < world || width <= 0 || height <= 0) { fprintf(stderr, "bad arguments\n"); return 1; }
+    if (rank < 0 || rank >= world || width <= 0 || height <= 0) { fprintf(stderr, "bad arguments\n"); return 1; }
+    /* Every rank needs a frame of its own.  Every rank works out every rank's bounds, so all of them refuse together, before the first collective
+     * (a rank that gave up alone would leave the others waiting for it in the all-gather). */
+    for (int r = 0; r < world; r++)
+        if ((long long)n_frames * r / world == (long long)n_frames * (r + 1) / world) {
+            fprintf(stderr, "rank %d: a tape of %d frame(s) does not shard over %d rank(s): rank %d would own no frame\n", rank, n_frames, world, r);
+            return 1;
+        }
 #ifndef SDV_EXAMPLE_HOST_MEMORY
     HIP_OK(hipSetDevice(local));
 #endif
@@ -289,16 +296,20 @@ int main(int argc, char **argv)
                 start = k0;
             } else if (s_lead) {
                 /* warm-up turns lo - s_lead .. lo - 1 (output discarded); frame lo then waits inside the engine for its successor */
-                const unsigned fl = (last && n_own == 1) ? SDV_FLAG_END_FILE : 0u;
-                const size_t n_first = sdv_binarize_records(height, 1, fl), n_cat = (size_t)s_lead * rpf + n_first;
-                sdv_line_rec *d_cat = (sdv_line_rec *)dev_alloc(n_cat * sizeof(sdv_line_rec));
+                const bool ends_here = last && n_own == 1;
+                const unsigned fl = ends_here ? SDV_FLAG_END_FILE : 0u;
+                const size_t n_first = sdv_binarize_records(height, 1, fl), n_cat = (size_t)s_lead * rpf + rpf;
+                sdv_line_rec *d_cat = (sdv_line_rec *)dev_alloc(((size_t)s_lead * rpf + n_first) * sizeof(sdv_line_rec));
                 d2d(d_cat, d_warm + (size_t)(lead - s_lead) * rpf, (size_t)s_lead * rpf * sizeof(sdv_line_rec));
                 SDV_OKAY(sdv_binarize_frames(eng, d_luma + (size_t)lead * frame_bytes, (size_t)width, frame_bytes, width, height, 1, (uint32_t)(1 + lo), fl,
                                              d_cat + (size_t)s_lead * rpf, n_first, d_stats, n_in + 2, NULL));
                 size_t np = 0, nf = 0;
                 SDV_OKAY(sdv_stitch_frames(eng, d_cat, n_cat, d_pairs, pairs_cap, &np, d_frames, frames_cap, &nf, NULL));
                 SDV_OKAY(sdv_saturate_stitch_stats(eng));
-                SDV_OKAY(sdv_get_stitch_state(eng, s_pred.data(), state_n));
+                SDV_OKAY(sdv_get_stitch_state(eng, s_pred.data(), state_n));    /* (before END_FILE: what the predecessor has behind its successor frame, this same frame lo) */
+                /* a range of the tape's last frame alone: its successor is the filler frame that closes the file, behind frame lo in d_cat - that turn is
+                 * all this rank puts out */
+                if (ends_here) SDV_OKAY(sdv_stitch_frames(eng, d_cat + n_cat, n_first - rpf, d_pairs, pairs_cap, &n_pairs, d_frames, frames_cap, &n_fr, NULL));
                 dev_free(d_cat);
                 start = 1;
             }

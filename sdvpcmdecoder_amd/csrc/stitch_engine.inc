@@ -196,6 +196,9 @@ int sdv_get_stitch_state(sdv_engine *e, void *out, size_t cap)
     for (int i = 0; i < 65; i++) { b->ring_order[i] = t->ring_order.data[(i + t->ring_order.tail_i) % 65]; b->ring_res[i] = t->ring_res.data[(i + t->ring_res.tail_i) % 65]; }
     if (t->d_chain0) RT_CHECK(rt::d2h(&b->chain, t->d_chain0, sizeof(sdvs::StepChain), (rt::stream_t)0));
     else cold_chain(&b->chain);
+    /* the bytes between the counters and the 16-byte aligned lines (_pad and what the compiler adds behind it) are nobody's: whatever the turn that
+     * wrote the chain left there must not make two equal states compare unequal - a rank of a sharded tape would decode its range again for it */
+    memset((uint8_t *)&b->chain + offsetof(sdvs::StepChain, _pad), 0, offsetof(sdvs::StepChain, tail) - offsetof(sdvs::StepChain, _pad));
     /* only the lines in use are part of the state */
     for (int i = b->chain.tail_n; i < sdvs::MIN_DEINT; i++) memset(&b->chain.tail[i], 0, sizeof(sdvs::SLine));
     return SDV_OK;

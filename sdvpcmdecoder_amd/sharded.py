@@ -28,6 +28,14 @@ def shard_bounds(n_frames: int, rank: int, world: int):
     return n_frames * rank // world, n_frames * (rank + 1) // world
 
 
+def check_ranges(n_frames: int, world: int):
+    """Every rank needs a frame of its own.  Every rank can work out every rank's bounds, so all of them refuse together and before the
+    first collective: a rank that gave up alone would leave the others waiting in the all-gather for a peer that has gone."""
+    empty = [r for r in range(world) if shard_bounds(n_frames, r, world)[0] == shard_bounds(n_frames, r, world)[1]]
+    if empty:
+        raise ValueError(f"a tape of {n_frames} frame(s) does not shard over {world} rank(s): rank(s) {empty} would own no frame")
+
+
 class ShardedDecoder:
     """`eng`: an engine with the methods of sdvpcmdecoder_amd.Engine (binarize_frames, stitch_frames, reset_stream,
     reset_stitcher, get/set_chain_state, get/set_stitch_state, saturate_stitch_stats).
@@ -55,7 +63,8 @@ class ShardedDecoder:
         f0, f1 = self.frames_needed(n_frames)
         lead, look, n_own = lo - f0, f1 - hi, hi - lo
         last = rank == world - 1
-        assert luma.shape[0] == f1 - f0 and n_own > 0
+        check_ranges(n_frames, world)
+        assert luma.shape[0] == f1 - f0
 
         # ---- binarize stage ------------------------------------------------------------------------------------------
         eng.reset_stream()
@@ -104,10 +113,16 @@ class ShardedDecoder:
                     start = head.shape[0] // rpf
                 elif s_lead:
                     # warm-up turns lo-s_lead .. lo-1 (output discarded); frame lo then waits inside the engine for its successor
-                    first, _ = eng.binarize_frames(luma[lead:lead + 1], first_frame_no=first_frame_no + lo, new_file=False, end_file=(last and n_own == 1))
-                    eng.stitch_frames(_cat(warm[(lead - s_lead) * rpf:], first))
+                    ends_here = last and n_own == 1
+                    first, _ = eng.binarize_frames(luma[lead:lead + 1], first_frame_no=first_frame_no + lo, new_file=False, end_file=ends_here)
+                    eng.stitch_frames(_cat(warm[(lead - s_lead) * rpf:], first[:rpf]))
                     eng.saturate_stitch_stats()
-                    s_pred = eng.get_stitch_state()
+                    s_pred = eng.get_stitch_state()     # (before END_FILE: what the predecessor has behind its successor frame, this same frame lo)
+                    if ends_here:
+                        # a range of the tape's last frame alone: its successor is the filler frame that closes the file, behind frame lo in
+                        # `first` - that turn is all this rank puts out
+                        p, f = eng.stitch_frames(first[rpf:])
+                        out_p.append(p); out_f.append(f)
                     start = 1
             if start < n_own:
                 kw = dict(first_frame_no=first_frame_no + lo + start, new_file=(rank == 0 and start == 0), end_file=last)
@@ -199,7 +214,8 @@ class ShardedPcmDecoder:
         lo, hi = shard_bounds(n_frames, rank, world)
         f0, _ = self.frames_needed(n_frames)
         lead, n_own, last = lo - f0, hi - lo, rank == world - 1
-        assert luma.shape[0] == hi - f0 and n_own > 0
+        check_ranges(n_frames, world)
+        assert luma.shape[0] == hi - f0
         # ---- binarize stage: as ShardedDecoder ------------------------------------------------------------------------
         eng.reset_stream()
         predicted, warm = None, None
