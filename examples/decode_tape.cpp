@@ -11,12 +11,14 @@
  *       8-bit luma frames of a PCM-1600/1610/1630 tape -> sdv_pcm16x0_binarize_frames (VideoToDigital with TYPE_PCM16X0) ->
  *       sdv_pcm16x0_stitch_frames (the PCM16X0DataStitcher worker's body); the sub-line records never leave the device
  *
- *   decode_tape wav <luma.raw> <width> <height> <n_frames> <out.wav> [<mask mode 0..6>] [auto|force]
+ *   decode_tape wav <luma.raw> <width> <height> <n_frames> <out.wav> [<mask mode 0..6>] [auto|force] [44100]
  *       the whole chain of the application for an STC-007 file: sdv_binarize_frames -> sdv_stitch_frames -> sdv_audio_process (the
  *       AudioProcessor worker's loop, linear interpolation of dropouts by default) -> sdv_wav_pack + sdv_wav_header: the file SamplesToWAV
  *       writes, byte for byte; nothing but the luma goes to the device and nothing but the 16-bit PCM comes back.  With `auto` or `force`
  *       the 50/15 us de-emphasis network (sdv_audio_deemphasis) runs on the file's pairs in front of sdv_wav_pack - `force` is the one for
- *       an STC-007 tape recorded with emphasis, whose pairs never carry the flag `auto` goes by; the reference leaves this to an audio editor
+ *       an STC-007 tape recorded with emphasis, whose pairs never carry the flag `auto` goes by; the reference leaves this to an audio editor.
+ *       With `44100` the file's pairs - an NTSC tape runs at 44 056 Hz - are resampled to 44 100 Hz (sdv_audio_resample, flush = 1) behind the
+ *       de-emphasis, and the header says 44 100 Hz
  *
  * Build (host code only, any C++ compiler): g++ -std=c++17 -O2 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude examples/decode_tape.cpp
  *        -Lsdvpcmdecoder_amd -lsdvpcm_hip -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$ORIGIN/../sdvpcmdecoder_amd' (build.py: build_example).
@@ -67,9 +69,11 @@ int main(int argc, char **argv)
     sdv_sample_pair *d_pairs = NULL;
     size_t n_pairs = 0, n_frames = 0;
     int rc = 0;
-    /* wav: the optional last word */
-    const std::string last_arg = argv[argc - 1];
-    const int deemph = last_arg == "auto" ? SDV_DEEMPH_AUTO : last_arg == "force" ? SDV_DEEMPH_FORCE : SDV_DEEMPH_OFF, wav_tail = deemph != SDV_DEEMPH_OFF ? 1 : 0;
+    /* wav: the optional last words, `auto|force` and behind it `44100` */
+    const bool wav = mode == "wav";
+    const int resample = wav && std::string(argv[argc - 1]) == "44100" ? 1 : 0;
+    const std::string last_arg = wav ? argv[argc - 1 - resample] : "";
+    const int deemph = last_arg == "auto" ? SDV_DEEMPH_AUTO : last_arg == "force" ? SDV_DEEMPH_FORCE : SDV_DEEMPH_OFF, wav_tail = (deemph != SDV_DEEMPH_OFF ? 1 : 0) + resample;
     if (mode == "stc007" && argc == 8) {
         const int width = atoi(argv[3]), height = atoi(argv[4]), n = atoi(argv[5]);
         if (!read_file(argv[2], in) || in.size() != (size_t)width * height * n) { fprintf(stderr, "cannot read %s\n", argv[2]); return 1; }
@@ -94,12 +98,12 @@ int main(int argc, char **argv)
         sdv_run_info info; sdv_get_run_info(eng, &info);
         printf("stc007: %d frames -> %zu line records -> %zu sample pairs, %zu frame descriptors (binarize rounds %u)\n", n, n_lines, n_pairs, n_frames, info.rounds);
         (void)hipFree(d_luma); (void)hipFree(d_lines); (void)hipFree(d_stats); (void)hipFree(d_frames);
-    } else if (mode == "wav" && (argc - wav_tail == 7 || argc - wav_tail == 8)) {
+    } else if (wav && (argc - wav_tail == 7 || argc - wav_tail == 8)) {
         const int width = atoi(argv[3]), height = atoi(argv[4]), n = atoi(argv[5]);
         const int mask_mode = argc - wav_tail == 8 ? atoi(argv[7]) : SDV_DROP_INTER_LIN_WORD;
         if (!read_file(argv[2], in) || in.size() != (size_t)width * height * n) { fprintf(stderr, "cannot read %s\n", argv[2]); return 1; }
         uint8_t *d_luma = NULL; sdv_line_rec *d_lines = NULL; sdv_frame_stats *d_stats = NULL; sdv_frame_asm *d_frames = NULL;
-        sdv_sample_pair *d_audio = NULL; sdv_audio_purge *d_purges = NULL; int16_t *d_pcm = NULL;
+        sdv_sample_pair *d_audio = NULL, *d_resampled = NULL; sdv_audio_purge *d_purges = NULL; int16_t *d_pcm = NULL;
         const size_t n_lines = sdv_binarize_records(height, n, SDV_FLAG_NEW_FILE | SDV_FLAG_END_FILE);
         const size_t pairs_cap = n_lines * 4 + 8192, frames_cap = (size_t)n + 16, purges_cap = 8;
         HIP_OK(hipMalloc((void **)&d_luma, in.size()));
@@ -109,7 +113,11 @@ int main(int argc, char **argv)
         HIP_OK(hipMalloc((void **)&d_frames, frames_cap * sizeof(sdv_frame_asm)));
         HIP_OK(hipMalloc((void **)&d_audio, (pairs_cap + 1024) * sizeof(sdv_sample_pair)));
         HIP_OK(hipMalloc((void **)&d_purges, purges_cap * sizeof(sdv_audio_purge)));
-        HIP_OK(hipMalloc((void **)&d_pcm, (pairs_cap + 1024) * 2 * sizeof(int16_t)));
+        /* with `44100`: room for every pair of the audio stage resampled (the bound grows with the pairs of the call) */
+        if (resample) SDV_OKAY(sdv_set_resample(eng, SDV_RESAMPLE_TO_44100));
+        const size_t res_cap = sdv_audio_resample_room(eng, pairs_cap + 1024);
+        if (resample) HIP_OK(hipMalloc((void **)&d_resampled, res_cap * sizeof(sdv_sample_pair)));
+        HIP_OK(hipMalloc((void **)&d_pcm, res_cap * 2 * sizeof(int16_t)));
         HIP_OK(hipMemcpy(d_luma, in.data(), in.size(), hipMemcpyHostToDevice));
         SDV_OKAY(sdv_set_mode(eng, SDV_MODE_NORMAL));
         SDV_OKAY(sdv_binarize_frames(eng, d_luma, (size_t)width, (size_t)width * height, width, height, n, 1,
@@ -132,18 +140,24 @@ int main(int argc, char **argv)
                 SDV_OKAY(sdv_set_deemphasis(eng, deemph));
                 SDV_OKAY(sdv_audio_deemphasis(eng, d_audio + a, b - a, d_audio + a, NULL));
             }
-            SDV_OKAY(sdv_wav_pack(eng, d_audio + a, b - a, d_pcm, NULL));
+            const sdv_sample_pair *d_file = d_audio + a; size_t n_file = b - a;
+            if (resample) {                         /* the file's range, closed behind its last pair */
+                size_t n_res = 0;
+                SDV_OKAY(sdv_audio_resample(eng, d_file, n_file, 1, d_resampled, res_cap, &n_res, NULL));
+                d_file = d_resampled; n_file = n_res;
+            }
+            SDV_OKAY(sdv_wav_pack(eng, d_file, n_file, d_pcm, NULL));
             HIP_OK(hipDeviceSynchronize());
             sdv_sample_pair last;
-            HIP_OK(hipMemcpy(&last, d_audio + (b - 1), sizeof(last), hipMemcpyDeviceToHost));
-            std::vector<uint8_t> file(44 + 4 * (b - a));
-            sdv_wav_header(file.data(), b - a, last.sample_rate);
-            HIP_OK(hipMemcpy(file.data() + 44, d_pcm, 4 * (b - a), hipMemcpyDeviceToHost));
+            HIP_OK(hipMemcpy(&last, d_file + (n_file - 1), sizeof(last), hipMemcpyDeviceToHost));
+            std::vector<uint8_t> file(44 + 4 * n_file);
+            sdv_wav_header(file.data(), n_file, last.sample_rate);
+            HIP_OK(hipMemcpy(file.data() + 44, d_pcm, 4 * n_file, hipMemcpyDeviceToHost));
             rc = write_file(argv[6], file.data(), file.size()) ? 0 : 4;
             printf("wav: %d frames -> %zu sample pairs -> %zu after the audio stage (%llu samples masked, %zu purges) -> %zu bytes at %u Hz\n", n, n_pairs, n_audio,
                    (unsigned long long)n_masked, n_purges, file.size(), last.sample_rate == 44056 ? 44056u : 44100u);
         }
-        (void)hipFree(d_luma); (void)hipFree(d_lines); (void)hipFree(d_stats); (void)hipFree(d_frames); (void)hipFree(d_audio); (void)hipFree(d_purges); (void)hipFree(d_pcm);
+        (void)hipFree(d_luma); (void)hipFree(d_lines); (void)hipFree(d_stats); (void)hipFree(d_frames); (void)hipFree(d_audio); (void)hipFree(d_purges); (void)hipFree(d_pcm); (void)hipFree(d_resampled);
     } else if (mode == "pcm1" && argc == 5) {
         if (!read_file(argv[2], in) || in.size() % sizeof(sdv_pcm1_line_rec)) { fprintf(stderr, "cannot read %s\n", argv[2]); return 1; }
         const size_t n_lines = in.size() / sizeof(sdv_pcm1_line_rec);

@@ -20,11 +20,12 @@
 extern "C" {
 #endif
 
-#define SDV_ABI_VERSION 6   /* 2: output capacities on sdv_binarize_frames / sdv_pcm1_binarize_lines; 3: sdv_audio_process, sdv_wav_pack, sdv_wav_header, sdv_decode_frames (additions only);
+#define SDV_ABI_VERSION 7   /* 2: output capacities on sdv_binarize_frames / sdv_pcm1_binarize_lines; 3: sdv_audio_process, sdv_wav_pack, sdv_wav_header, sdv_decode_frames (additions only);
                              * 4: sdv_pcm16x0_binarize_lines, sdv_audio_stalled, sdv_set_frame_flags, sdv_double_width, sdv_vis_render_lines (additions); the calls that used to refuse PCM-16x0 frames of the wrong size and the
                              * AudioProcessor's dead ends now follow the reference; the PCM-16x0 stitch state blob grew by conv_queue's remainder;
                              * 5: sdv_run_info grew by frames_met (at its end), sdv_binarize_lines (addition);
-                             * 6: sdv_deemphasis_coeffs, sdv_set_deemphasis, sdv_reset_deemphasis, sdv_audio_deemphasis (additions only) */
+                             * 6: sdv_deemphasis_coeffs, sdv_set_deemphasis, sdv_reset_deemphasis, sdv_audio_deemphasis (additions only);
+                             * 7: sdv_resample_taps, sdv_set_resample, sdv_reset_resample, sdv_audio_resample_pending, sdv_audio_resample_room, sdv_audio_resample (additions only) */
 
 /* ---- status codes ---------------------------------------------------------------------------
  * 0..4 mirror Binarizer::LB_RET_* (binarizer.h:268-275); 16.. mirror STC007Deinterleaver::DI_RET_*
@@ -809,6 +810,48 @@ int sdv_reset_deemphasis(sdv_engine *e);
  * any other overlap of the two is refused (SDV_ERR_BAD_ARG) and leaves the state untouched.  With a mode other than SDV_DEEMPH_OFF,
  * sdv_decode_frames (with_audio != 0) makes this call on its out_pairs, in place, behind the AudioProcessor. */
 int sdv_audio_deemphasis(sdv_engine *e, const sdv_sample_pair *pairs, size_t n, sdv_sample_pair *out_pairs, void *stream);
+
+/* ---- resampling: 44 056 Hz pair streams to 44 100 Hz (no reference equivalent: the reference writes the NTSC rate into the WAV header) ---- */
+/* STC-007 / PCM-F1 on NTSC video and PCM-1 run at 44 100 / 1.001 Hz; the ratio to 44 100 Hz is the exact rational SDV_RESAMPLE_L / SDV_RESAMPLE_M.
+ * The filter is a Kaiser-windowed sinc (beta = 12.0), SDV_RESAMPLE_HALF taps on each side, one row of 2 * SDV_RESAMPLE_HALF = 128 taps per
+ * phase p = 0 .. 1000.  For k = 0 .. 127, all in double:
+ *   d = (k - 63) - p / 1001,  w(d) = I0(beta sqrt(1 - (d / 64)^2)) / I0(beta),  g[p][k] = sinc(d) w(d) with sinc(x) = sin(pi x) / (pi x),
+ *   h[p][k] = g[p][k] / sum_k g[p][k]
+ * so every phase has gain 1 at DC; h[p][k] = h[1001 - p][127 - k] for p >= 1.  (Passband ripple 1e-5 dB up to 20 kHz, images beyond 24.056 kHz
+ * at or below -121 dB, sum |h| <= 3.15: outputs clamp.)
+ * Segments.  A call's pairs are walked in order.  A service pair (service_type != 0) and a pair whose sample_rate is not 44056 are copied
+ * through unchanged at their place and end an open segment; a maximal run of other pairs is a segment.  A segment may continue across the
+ * calls of one stream; it ends at a pair that is copied through, or at the end of a call made with flush != 0.
+ * A finished segment of n pairs x[0 .. n-1] yields n_out = floor((n - 1) 1001 / 1000) + 1 pairs.  For m = 0 .. n_out - 1:
+ *   i0 = floor(m 1000 / 1001), p = (m 1000) mod 1001, per channel y = sum_k h[p][k] x[clamp(i0 - 63 + k, 0, n - 1)]  (edge hold: no click
+ *   at the ends, DC passes exactly); audio_word = y rounded to the nearest integer (halves to even), clamped to -32768 .. 32767; every other
+ *   field of the output pair is that of x[i0], except sample_rate = 44100.
+ * Latency.  Without flush a call emits only those outputs of the open segment whose i0 + 64 is below the number of pairs the segment has seen
+ * so far; the rest wait in the engine (the segment's last 127 pairs, on the device).  The concatenated output of any split of a stream into
+ * calls equals the output of one call, when the last call has flush != 0 or the stream's last pair is one that is copied through.
+ * The sums run in double in the order of k: a word differs from a sequential float64 evaluation in another order only where y lies within about
+ * 1e-9 of a half. */
+#define SDV_RESAMPLE_L 1001
+#define SDV_RESAMPLE_M 1000
+#define SDV_RESAMPLE_HALF 64        /* taps on each side of an output: 128 per phase */
+enum { SDV_RESAMPLE_OFF = 0, SDV_RESAMPLE_TO_44100 = 1 };
+/* h[phase][0 .. 127] (phase 0 .. 1000; anything else: zeros).  Host memory, no engine. */
+void sdv_resample_taps(int phase, double taps[128]);
+/* The mode (SDV_RESAMPLE_OFF when the engine is made); anything else: SDV_ERR_BAD_ARG.  The state stays as it is. */
+int sdv_set_resample(sdv_engine *e, int mode);
+/* No open segment, nothing pending. */
+int sdv_reset_resample(sdv_engine *e);
+/* Pairs of the open segment that still owe outputs (at most SDV_RESAMPLE_HALF; 0 behind a flush). */
+size_t sdv_audio_resample_pending(const sdv_engine *e);
+/* An upper bound of *n_out for the next call with n_pairs pairs, whatever they hold and with or without flush. */
+size_t sdv_audio_resample_room(const sdv_engine *e, size_t n_pairs);
+/* n_pairs pairs from `pairs` to `out_pairs` (device pointers, all device work on `stream`); *n_out receives the count.  The call returns when
+ * the outputs are complete (the count is read back).  With SDV_RESAMPLE_OFF the call is a byte copy, *n_out = n_pairs and the state becomes
+ * empty.  Refused before any launch, with the state untouched (SDV_ERR_BAD_ARG, sdv_last_error says why): out_cap below
+ * sdv_audio_resample_room(e, n_pairs), any overlap of out_pairs with pairs, and - with n_pairs != 0 - null buffers (SDV_ERR_NULL_LINES /
+ * SDV_ERR_NULL_BLOCK).  n_pairs == 0 with flush != 0 closes the open segment and emits its tail. */
+int sdv_audio_resample(sdv_engine *e, const sdv_sample_pair *pairs, size_t n_pairs, int flush,
+                       sdv_sample_pair *out_pairs, size_t out_cap, size_t *n_out, void *stream);
 
 /* ---- the workers back to back: video frames -> PCMSamplePair (-> masked PCMSamplePair) in one call ------------------- */
 /* SURVEY 8b's "sdv_decode_frames": the format's VideoToDigital worker, its data stitcher and - on request - the AudioProcessor, one

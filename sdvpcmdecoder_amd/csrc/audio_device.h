@@ -690,3 +690,4 @@ __global__ void __launch_bounds__(64) sdv_k_ap_emit(sdva::EmitArgs a) { sdva::em
 __global__ void __launch_bounds__(64) sdv_k_wav_pack(sdva::WavArgs a) { sdva::wav_body(a, (size_t)blockIdx.x * 64u + threadIdx.x); }
 
 #include "audio_deemph_device.h"      /* sdv_audio_deemphasis: the de-emphasis network behind the AudioProcessor */
+#include "audio_resample_device.h"    /* sdv_audio_resample: 44 056 Hz segments of the stream to 44 100 Hz */

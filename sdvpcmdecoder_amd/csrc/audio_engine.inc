@@ -7,7 +7,8 @@
  * stretch, bitmaps only), a read-back of the per-stretch results, the sample work of the listed windows, a second read-back (mask
  * counts, the plan check), and - unless the caller's buffer was the work array - emit.  The stream state - what waits in the window,
  * the masking mode, the running sample index - is replaced only when the call succeeds.  sdv_audio_deemphasis (two launches,
- * nothing read back) and sdv_decode_frames (the workers of a format back to back) live here too, this being the last include of both builds.
+ * nothing read back), sdv_audio_resample (three launches, the count read back) and sdv_decode_frames (the workers of a format back to back)
+ * live here too, this being the last include of both builds.
  */
 #include <algorithm>
 
@@ -28,6 +29,12 @@ struct sdv_audio {
     /* sdv_audio_deemphasis: the mode, the filter between two calls (on the device; de_idle: not looked at, the next call starts idle), a record per tile */
     int de_mode; bool de_idle;
     rt::DevBuf<sdva::DeState> d_de_state, d_de_tiles;
+    /* sdv_audio_resample: the mode; the open segment between two calls - pairs seen, outputs emitted, its last RS_HIST pairs (on the device) -;
+     * the tap table ([k][phase], made on first use), a summary and a start per tile, the call's result */
+    int rs_mode; uint64_t rs_seen, rs_emitted; bool rs_taps_ready;
+    rt::DevBuf<sdv_sample_pair> d_rs_hist, d_rs_hist_spare;
+    rt::DevBuf<double> d_rs_taps;
+    rt::DevBuf<sdva::RsSum> d_rs_sums; rt::DevBuf<sdva::RsStart> d_rs_starts; rt::DevBuf<sdva::RsResult> d_rs_result;
 };
 
 static sdv_audio *audio_get(sdv_engine *e)
@@ -36,6 +43,7 @@ static sdv_audio *audio_get(sdv_engine *e)
     sdv_audio *t = new sdv_audio();
     t->mask_mode = SDV_DROP_IGNORE;     /* the constructor's DROP_IGNORE (audioprocessor.cpp:15) */
     t->de_mode = SDV_DEEMPH_OFF; t->de_idle = true;
+    t->rs_mode = SDV_RESAMPLE_OFF;
     e->audio = t;
     return t;
 }
@@ -410,6 +418,125 @@ int sdv_audio_deemphasis(sdv_engine *e, const sdv_sample_pair *pairs, size_t n, 
     RT_LAUNCH64(sdv_k_deemph_warm, n_tiles, a, s);
     RT_LAUNCH64(sdv_k_deemph, n_tiles, a, s);
     t->de_idle = false;
+    return SDV_OK;
+}
+
+
+/* ---- resampling 44 056 Hz -> 44 100 Hz (no reference equivalent: the definition is in include/sdvpcm.h) --------------------- */
+static double rs_bessel_i0(double x)
+{
+    const double q = x * x / 4.0;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 500; k++) { term *= q / ((double)k * (double)k); sum += term; if (term < 1e-18 * sum) break; }
+    return sum;
+}
+void sdv_resample_taps(int phase, double taps[128])
+{
+    if (phase < 0 || phase >= SDV_RESAMPLE_L) { for (int k = 0; k < 128; k++) taps[k] = 0.0; return; }
+    const double beta = 12.0, pi = 3.14159265358979323846, i0_beta = rs_bessel_i0(beta);
+    long double sum = 0.0L;             /* (the normalisation must not cost the rows their gain of 1 at DC) */
+    for (int k = 0; k < 128; k++) {
+        const double d = (double)(k - (SDV_RESAMPLE_HALF - 1)) - (double)phase / (double)SDV_RESAMPLE_L;
+        double r = 1.0 - (d / SDV_RESAMPLE_HALF) * (d / SDV_RESAMPLE_HALF);
+        if (r < 0.0) r = 0.0;
+        const double w = rs_bessel_i0(beta * sqrt(r)) / i0_beta, x = pi * d;
+        taps[k] = (d == 0.0 ? 1.0 : sin(x) / x) * w;
+        sum += (long double)taps[k];
+    }
+    const double total = (double)sum;
+    for (int k = 0; k < 128; k++) taps[k] /= total;
+}
+
+int sdv_set_resample(sdv_engine *e, int mode)
+{
+    if (!e) return SDV_ERR_BAD_ARG;
+    if (mode != SDV_RESAMPLE_OFF && mode != SDV_RESAMPLE_TO_44100) { set_error(e, "no such resampling mode"); return SDV_ERR_BAD_ARG; }
+    audio_get(e)->rs_mode = mode;
+    return SDV_OK;
+}
+
+int sdv_reset_resample(sdv_engine *e)
+{
+    if (!e) return SDV_ERR_BAD_ARG;
+    sdv_audio *t = audio_get(e);
+    t->rs_seen = 0; t->rs_emitted = 0;
+    return SDV_OK;
+}
+
+size_t sdv_audio_resample_pending(const sdv_engine *e)
+{
+    if (!e || !e->audio) return 0;
+    return (size_t)std::min<uint64_t>(e->audio->rs_seen, (uint64_t)SDV_RESAMPLE_HALF);
+}
+
+/* outputs the first j pairs of a segment own (sdva::rs_owned) */
+static uint64_t rs_owned_host(uint64_t j) { return j == 0 ? 0 : j + (j - 1) / SDV_RESAMPLE_M; }
+
+size_t sdv_audio_resample_room(const sdv_engine *e, size_t n_pairs)
+{
+    if (!e || !e->audio || e->audio->rs_mode == SDV_RESAMPLE_OFF) return n_pairs;
+    /* what the open segment owes when it ends, and per new pair one output and one more per thousand (a segment of n new pairs owns
+     * n + floor((n - 1) / 1000); n pairs that continue the open one at most ceil(n 1001 / 1000) more than it owes) */
+    const sdv_audio *t = e->audio;
+    return (size_t)(rs_owned_host(t->rs_seen) - t->rs_emitted) + n_pairs + n_pairs / SDV_RESAMPLE_M + 2;
+}
+
+int sdv_audio_resample(sdv_engine *e, const sdv_sample_pair *pairs, size_t n_pairs, int flush, sdv_sample_pair *out_pairs, size_t out_cap, size_t *n_out, void *stream)
+{
+    if (!e || !n_out) return SDV_ERR_BAD_ARG;
+    *n_out = 0;
+    sdv_audio *t = audio_get(e);
+    if (n_pairs > 0 && !pairs) { set_error(e, "null sample pair buffer"); return SDV_ERR_NULL_LINES; }
+    if (n_pairs >= 0x7FFF0000u) { set_error(e, "too many sample pairs in one call"); return SDV_ERR_BAD_ARG; }
+    const size_t room = sdv_audio_resample_room(e, n_pairs);
+    const bool off = t->rs_mode == SDV_RESAMPLE_OFF, tail_only = n_pairs == 0 && flush && t->rs_seen > 0;
+    if (!off && n_pairs == 0 && !tail_only) { if (flush) { t->rs_seen = 0; t->rs_emitted = 0; } return SDV_OK; }
+    if (off && n_pairs == 0) { t->rs_seen = 0; t->rs_emitted = 0; return SDV_OK; }
+    if (!out_pairs) { set_error(e, "null output buffer"); return SDV_ERR_NULL_BLOCK; }
+    if (out_cap < room) {
+        set_error(e, "output buffer too small: room for " + std::to_string((unsigned long long)room) + " sample pairs is needed (sdv_audio_resample_room)");
+        return SDV_ERR_BAD_ARG;
+    }
+    if (pairs && (const char *)pairs < (const char *)(out_pairs + out_cap) && (const char *)out_pairs < (const char *)(pairs + n_pairs)) {
+        set_error(e, "the output overlaps the input"); return SDV_ERR_BAD_ARG;
+    }
+    SDV_ON_DEVICE(e);
+    rt::stream_t s = (rt::stream_t)stream;
+    if (off) {
+        RT_CHECK(rt::d2d(out_pairs, pairs, n_pairs * sizeof(sdv_sample_pair), s));
+        RT_CHECK(rt::ssync(s));
+        t->rs_seen = 0; t->rs_emitted = 0;
+        *n_out = n_pairs;
+        return SDV_OK;
+    }
+    if (!t->rs_taps_ready) {
+        /* the table, transposed: the 64 lanes of a wave walk neighbouring phases of one tap */
+        std::vector<double> tab((size_t)sdva::RS_TAPS * sdva::RS_PITCH, 0.0);
+        double row[128];
+        for (int p = 0; p < SDV_RESAMPLE_L; p++) { sdv_resample_taps(p, row); for (int k = 0; k < 128; k++) tab[(size_t)k * sdva::RS_PITCH + p] = row[k]; }
+        RT_CHECK(t->d_rs_taps.reserve(tab.size()));
+        RT_CHECK(rt::h2d(t->d_rs_taps, tab.data(), tab.size() * sizeof(double), s));
+        RT_CHECK(rt::ssync(s));
+        t->rs_taps_ready = true;
+    }
+    const size_t n_tiles = (n_pairs + sdva::RS_TILE - 1) / sdva::RS_TILE;
+    RT_CHECK(rt::reserve_all(sdva::RS_HIST, sdva::RS_HIST, t->d_rs_hist, t->d_rs_hist_spare));
+    RT_CHECK(t->d_rs_result.reserve(1));
+    RT_CHECK(t->d_rs_sums.reserve(n_tiles + 1, n_tiles + n_tiles / 8 + 64));
+    RT_CHECK(t->d_rs_starts.reserve(n_tiles + 1, n_tiles + n_tiles / 8 + 64));
+    sdva::RsArgs a; memset(&a, 0, sizeof(a));
+    a.in = pairs; a.out = out_pairs; a.n = (int64_t)n_pairs; a.out_cap = out_cap; a.hist = t->d_rs_hist; a.hist_out = t->d_rs_hist_spare;
+    a.taps = t->d_rs_taps; a.sums = t->d_rs_sums; a.starts = t->d_rs_starts; a.result = t->d_rs_result;
+    a.seen0 = t->rs_seen; a.emitted0 = t->rs_emitted; a.n_tiles = (uint32_t)n_tiles; a.flush = flush ? 1 : 0;
+    RT_LAUNCH64(sdv_k_resample_classify, n_tiles, a, s);
+    RT_LAUNCH64(sdv_k_resample_scan, 1, a, s);
+    RT_LAUNCH64(sdv_k_resample_emit, n_tiles ? n_tiles : 1, a, s);
+    sdva::RsResult res;
+    RT_CHECK(rt::d2h(&res, t->d_rs_result, sizeof(res), s));
+    if (res.n_out > out_cap) { set_error(e, "internal: the resampler counted more outputs than sdv_audio_resample_room allows"); return SDV_ERR_HIP; }
+    t->d_rs_hist.swap(t->d_rs_hist_spare);
+    t->rs_seen = res.seen; t->rs_emitted = res.emitted;
+    *n_out = (size_t)res.n_out;
     return SDV_OK;
 }
 

@@ -35,6 +35,7 @@ TYPE_M2 = 3                      # VideoToDigital::TYPE_M2 (videotodigital.h:77)
 MODE_DRAFT, MODE_FAST, MODE_NORMAL, MODE_INSANE = 0, 1, 2, 3
 FLAG_NEW_FILE, FLAG_DOUBLED, FLAG_END_FILE = 1, 2, 4
 DEEMPH_OFF, DEEMPH_AUTO, DEEMPH_FORCE = 0, 1, 2       # sdv_set_deemphasis
+RESAMPLE_OFF, RESAMPLE_TO_44100 = 0, 1                # sdv_set_resample
 FRAME_EMPTY = 1                 # sdv_set_frame_flags: SDV_FRAME_EMPTY
 VIS_STC007_LINES, VIS_PCM1_LINES, VIS_PCM16X0_LINES, VIS_STC007_BLOCKS_NTSC, VIS_STC007_BLOCKS_PAL, VIS_STC007_ASM_NTSC, VIS_STC007_ASM_PAL = 0, 1, 2, 3, 4, 5, 6   # SDV_VIS_*
 
@@ -231,6 +232,16 @@ def load_library(path: str | None = None):
     lib.sdv_reset_deemphasis.argtypes = [C.c_void_p]
     lib.sdv_audio_deemphasis.restype = C.c_int
     lib.sdv_audio_deemphasis.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    lib.sdv_resample_taps.argtypes = [C.c_int, C.POINTER(C.c_double)]
+    lib.sdv_resample_taps.restype = None
+    lib.sdv_set_resample.argtypes = [C.c_void_p, C.c_int]
+    lib.sdv_reset_resample.argtypes = [C.c_void_p]
+    lib.sdv_audio_resample_pending.restype = C.c_size_t
+    lib.sdv_audio_resample_pending.argtypes = [C.c_void_p]
+    lib.sdv_audio_resample_room.restype = C.c_size_t
+    lib.sdv_audio_resample_room.argtypes = [C.c_void_p, C.c_size_t]
+    lib.sdv_audio_resample.restype = C.c_int
+    lib.sdv_audio_resample.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
     lib.sdv_decode_frames.restype = C.c_int
     lib.sdv_decode_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint,
                                       C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t,
@@ -896,6 +907,41 @@ class Engine:
         """(b0, b1, a1) of the network at the rate of a pair (44056, anything else reads 44100)."""
         c = (C.c_double * 3)()
         self.lib.sdv_deemphasis_coeffs(int(rate), c)
+        return tuple(c)
+
+    # ---- 44 056 Hz -> 44 100 Hz: beyond the reference, which writes the NTSC rate into the WAV header ---------------------
+    def set_resample(self, mode: int):
+        """RESAMPLE_OFF (the default: audio_resample copies) / RESAMPLE_TO_44100."""
+        self._check(self.lib.sdv_set_resample(self._h, int(mode)))
+
+    def reset_resample(self):
+        """No open segment, nothing pending."""
+        self._check(self.lib.sdv_reset_resample(self._h))
+
+    def audio_resample_pending(self) -> int:
+        return int(self.lib.sdv_audio_resample_pending(self._h))
+
+    def audio_resample(self, pairs, flush=False, out=None, stream=None):
+        """One burst of the stream through the 1001 / 1000 resampler: (n, 12) sdv_sample_pair -> (n_out, 12) on the device; segments of
+        44 056 Hz pairs leave at 44 100 Hz, everything else as it came.  Without flush the last 64 pairs of an open segment wait in the
+        engine for the next call.  out: a buffer of at least sdv_audio_resample_room pairs that does not overlap `pairs`."""
+        import torch
+        _check_out(pairs, 12, pairs.device, "pairs")
+        n = pairs.shape[0]
+        room = int(self.lib.sdv_audio_resample_room(self._h, n))
+        if out is None:
+            out = torch.empty((room, 12), dtype=torch.uint8, device=pairs.device)
+        _check_out(out, 12, pairs.device, "out")
+        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else C.c_void_p(torch.cuda.current_stream(pairs.device).cuda_stream)
+        n_out = C.c_size_t(0)
+        self._check(self.lib.sdv_audio_resample(self._h, C.c_void_p(pairs.data_ptr()) if n else None, n, 1 if flush else 0,
+                                                C.c_void_p(out.data_ptr()) if out.shape[0] else None, out.shape[0], C.byref(n_out), sptr))
+        return out[:n_out.value]
+
+    def resample_taps(self, phase: int):
+        """The 128 taps of a phase (0 .. 1000), as a tuple of floats."""
+        c = (C.c_double * 128)()
+        self.lib.sdv_resample_taps(int(phase), c)
         return tuple(c)
 
     def wav_files(self, out_pairs, purges):
