@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import audio_api as A
+import device_calls as dc
 import dist_worker
 import engine_api as ea
 import pcm1_api as p1
@@ -52,20 +53,21 @@ def _separate(eng, fmt, luma):
     return pairs, frames, stats
 
 
-def _fused_host(lib, h, fmt, luma, with_audio, stop=1, give_stats=True, first_frame_no=1, flags=1 | 4):
+def _fused_host(lib, h, fmt, luma, with_audio, stop=1, give_stats=True, first_frame_no=1, flags=1 | 4, via=dc.HOST):
     luma = np.ascontiguousarray(luma)
     n, hgt, w = luma.shape
     cap = (n + 2) * 1800 + 8192
-    pairs = np.zeros(cap, dtype=PAIR_DTYPE)
-    frames = np.zeros(n + 16, dtype=FRASM[fmt])
-    stats = np.zeros(n + 1, dtype=ea.STATS_DTYPE)
-    pur = np.zeros(8, dtype=A.PURGE_DTYPE)
+    src = via.array(luma)
+    pairs = via.zeros(cap, PAIR_DTYPE)
+    frames = via.zeros(n + 16, FRASM[fmt])
+    stats = via.zeros(n + 1, ea.STATS_DTYPE)
+    pur = via.zeros(8, A.PURGE_DTYPE)
     npairs, nfr, npur, nm = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_uint64(0)
-    rc = lib.sdv_decode_frames(h, fmt, luma.ctypes.data, w, w * hgt, w, hgt, n, first_frame_no, flags, pairs.ctypes.data, cap, C.byref(npairs), frames.ctypes.data, len(frames),
-                               C.byref(nfr), stats.ctypes.data if give_stats else None, len(stats) if give_stats else 0, 1 if with_audio else 0, stop,
-                               pur.ctypes.data, len(pur), C.byref(npur), C.byref(nm), None)
+    rc = lib.sdv_decode_frames(h, fmt, via.ptr(src), w, w * hgt, w, hgt, n, first_frame_no, flags, via.ptr(pairs), cap, C.byref(npairs), via.ptr(frames), len(frames),
+                               C.byref(nfr), via.ptr(stats) if give_stats else None, len(stats) if give_stats else 0, 1 if with_audio else 0, stop,
+                               via.ptr(pur), len(pur), C.byref(npur), C.byref(nm), via.stream())
     assert rc == 0, lib.sdv_last_error(h)
-    return pairs[:npairs.value], frames[:nfr.value], stats, pur[:npur.value], nm.value
+    return via.get(pairs, npairs.value), via.get(frames, nfr.value), via.get(stats), via.get(pur, npur.value), nm.value
 
 
 @pytest.mark.parametrize("fmt", [STC007, PCM1, PCM16X0])
@@ -154,17 +156,21 @@ def test_emu_fused_direct_frames_decoded_again_with_records(emu_lib, oracle_lib,
         assert np.concatenate(got_s).tobytes() == want_s[:13].tobytes()
 
 
-def test_emu_fused_refuses_bad_arguments(emu_lib):
-    lib = A.bind_product(_bind(ea.bind(emu_lib)))
+def _fused_refuses_bad_arguments(lib, via):
     e = EmuEngine(lib)
-    luma = np.zeros((1, 16, 720), dtype=np.uint8)
+    luma = via.array(np.zeros((1, 16, 720), dtype=np.uint8))
     n1, n2 = C.c_size_t(0), C.c_size_t(0)
-    buf = np.zeros(4096, dtype=PAIR_DTYPE)
-    args = (luma.ctypes.data, 720, 720 * 16, 720, 16, 1, 1, 0, buf.ctypes.data, len(buf), C.byref(n1), buf.ctypes.data, 8, C.byref(n2), None, 0)
-    assert lib.sdv_decode_frames(e.h, 5, *args, 0, 0, None, 0, None, None, None) == -1 and b"unknown PCM type" in lib.sdv_last_error(e.h)
-    assert lib.sdv_decode_frames(e.h, STC007, *args, 1, 0, None, 0, None, None, None) == -1 and b"with_audio" in lib.sdv_last_error(e.h)
-    assert lib.sdv_decode_frames(e.h, STC007, None, *args[1:], 0, 0, None, 0, None, None, None) == 1      # LB_RET_NULL_VIDEO
+    buf = via.zeros(4096, PAIR_DTYPE)
+    args = (via.ptr(luma), 720, 720 * 16, 720, 16, 1, 1, 0, via.ptr(buf), len(buf), C.byref(n1), via.ptr(buf), 8, C.byref(n2), None, 0)
+    assert lib.sdv_decode_frames(e.h, 5, *args, 0, 0, None, 0, None, None, via.stream()) == -1 and b"unknown PCM type" in lib.sdv_last_error(e.h)
+    assert lib.sdv_decode_frames(e.h, STC007, *args, 1, 0, None, 0, None, None, via.stream()) == -1 and b"with_audio" in lib.sdv_last_error(e.h)
+    assert lib.sdv_decode_frames(e.h, STC007, None, *args[1:], 0, 0, None, 0, None, None, via.stream()) == 1      # LB_RET_NULL_VIDEO
+    assert via.get(buf).tobytes() == bytes(4096 * 12)
     e.close()
+
+
+def test_emu_fused_refuses_bad_arguments(emu_lib):
+    _fused_refuses_bad_arguments(A.bind_product(_bind(ea.bind(emu_lib))), dc.HOST)
 
 
 # ---- the product on the GPU ------------------------------------------------------------------------------------------
@@ -530,14 +536,13 @@ def test_gpu_fused_stitch_queued_ahead_is_made_over_when_the_frame_stage_needs_m
     assert any(x & 4 for x in piped) and any(x & 8 for x in piped), piped
 
 
-def test_emu_stitch_and_fused_calls_interleaved_with_the_visualiser_feeds_toggled(emu_lib, oracle_lib):
+def _stitch_and_fused_calls_interleaved_with_the_visualiser_feeds_toggled(lib, via, oracle_lib):
     """One stream fed alternately through sdv_decode_frames (records of known layout: the pipelined way through the stitch stage, the next call's state
     copied ahead of the read-back) and through sdv_binarize_frames + sdv_stitch_frames, with the block and assembled-line outputs of the stitch stage
     switched on and off in between (switched on they make the stage run its turns once more for the feed): the hand-over between the calls must not
     depend on which way a call took.  The whole equals the sequential oracle; the emulator build also checks the state that was copied ahead against
     the last turn's (SDV_DEV_AIDS, stitch_engine.inc)."""
     from sdvpcmdecoder_amd import synth
-    lib = A.bind_product(_bind(ea.bind(emu_lib)))
     lib.sdv_set_stitch_block_output.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.sdv_set_stitch_line_output.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     n = 14
@@ -545,8 +550,8 @@ def test_emu_stitch_and_fused_calls_interleaved_with_the_visualiser_feeds_toggle
     want_p, want_f, _ = _oracle_chain(oracle_lib, luma)
     e = EmuEngine(lib)
     lib.sdv_set_pcm_type(e.h, STC007, 0)
-    blocks = np.zeros(4096, dtype=sa.BLOCK_DTYPE)
-    asm = np.zeros(64 * 1024, dtype=np.uint8)
+    blocks = via.zeros(4096, sa.BLOCK_DTYPE)
+    asm = via.zeros(1024, sa.ASM_DTYPE)
     got_p, got_f = [], []
     piped = 0
     info = ea.StitchInfo()
@@ -554,23 +559,43 @@ def test_emu_stitch_and_fused_calls_interleaved_with_the_visualiser_feeds_toggle
     k = 0
     for how, cnt, feed in plan:
         if feed == "blocks":
-            assert lib.sdv_set_stitch_block_output(e.h, blocks.ctypes.data, len(blocks)) == 0
+            assert lib.sdv_set_stitch_block_output(e.h, via.ptr(blocks), len(blocks)) == 0
         elif feed == "lines":
             assert lib.sdv_set_stitch_block_output(e.h, None, 0) == 0
-            assert lib.sdv_set_stitch_line_output(e.h, asm.ctypes.data, len(asm) // 64) == 0
+            assert lib.sdv_set_stitch_line_output(e.h, via.ptr(asm), len(asm)) == 0
         elif feed == "off":
             assert lib.sdv_set_stitch_line_output(e.h, None, 0) == 0
         flags = (1 if k == 0 else 0) | (4 if k + cnt == n else 0)
         if how == "fused":
-            p, f, _st, _, _ = _fused_host(lib, e.h, STC007, luma[k:k + cnt], with_audio=False, first_frame_no=1 + k, flags=flags)
-        else:
-            recs, _stats = e.binarize_frames(luma[k:k + cnt], first_frame_no=1 + k, new_file=k == 0, end_file=k + cnt == n)
-            p, f = e.stitch_frames(recs)
+            p, f, _st, _, _ = _fused_host(lib, e.h, STC007, luma[k:k + cnt], with_audio=False, first_frame_no=1 + k, flags=flags, via=via)
+        else:           # (what EmuEngine.binarize_frames / .stitch_frames do, in `via`'s memory)
+            rc, recs, _stats = via.binarize(lib, e.h, luma[k:k + cnt], first_frame_no=1 + k, flags=flags)
+            assert rc == 0, lib.sdv_last_error(e.h)
+            rc, p, f = via.stitch(lib, e.h, recs, None, pair_cap=len(recs) * 4 + 8192, frame_cap=len(recs) // 8 + 64)
+            assert rc == 0, lib.sdv_last_error(e.h)
         got_p.append(p.copy()); got_f.append(f.copy())
         assert lib.sdv_get_stitch_info(e.h, C.byref(info)) == 0
         piped += int(info.pipelined)
         k += cnt
+    via.check(blocks, asm)
     e.close()
     assert k == n
     assert np.concatenate(got_p).tobytes() == want_p.tobytes() and np.concatenate(got_f).tobytes() == want_f.tobytes()
     assert piped >= 2, piped
+
+
+def test_emu_stitch_and_fused_calls_interleaved_with_the_visualiser_feeds_toggled(emu_lib, oracle_lib):
+    _stitch_and_fused_calls_interleaved_with_the_visualiser_feeds_toggled(A.bind_product(_bind(ea.bind(emu_lib))), dc.HOST, oracle_lib)
+
+
+# ---- the GPU twins of the emulator's call-by-call tests: the same bodies through tests/device_calls.py ----------------------------------------------
+@pytest.mark.gpu
+def test_gpu_stitch_and_fused_calls_interleaved_with_the_visualiser_feeds_toggled(oracle_lib):
+    _stitch_and_fused_calls_interleaved_with_the_visualiser_feeds_toggled(dc.product_lib(), dc.DEVICE, oracle_lib)
+
+
+@pytest.mark.gpu
+def test_gpu_fused_refuses_bad_arguments():
+    """The three refusals are the host's, ahead of any device work: the PCM type and the audio arguments at audio_engine.inc:556-557, the null video
+    in the frame entry the fused one calls first (engine.inc:697, ahead of its first launch; on a new engine nothing is armed for it, stitch_engine.inc:290)."""
+    _fused_refuses_bad_arguments(dc.product_lib(), dc.DEVICE)

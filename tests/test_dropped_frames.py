@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import device_calls as dc
 import engine_api as ea
 import libs
 import pcm16_frames_api as f16
@@ -120,22 +121,25 @@ def test_emu_matches_oracle(name, emu_lib, oracle_lib):
     assert _bytes(*got) == _bytes(*run_cpu(oracle_lib, "orc_", name))
 
 
-def test_emu_marks_are_consumed_by_one_call(emu_lib, oracle_lib):
+def _marks_are_consumed_by_one_call(lib, via):
     """The marks belong to the next frame call only: the call after it decodes its pixels."""
-    lib = ea.bind(emu_lib)
     eng = C.c_void_p(lib.sdv_engine_create(0))
     lib.sdv_set_frame_flags.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.sdv_set_mode(eng, 2)
     luma = synth.stc007_frames(n_frames=4, seed=31, height=64, lines_per_field=34, noise_sigma=3.0)[0]
     mask = np.array([0, 1, 0, 0], dtype=np.uint8)
     assert lib.sdv_set_frame_flags(eng, mask.ctypes.data, 4) == 0
-    rc, recs1, _ = ea.emu_binarize(lib, eng, luma, first_frame_no=1, flags=1)
-    rc2, recs2, _ = ea.emu_binarize(lib, eng, luma, first_frame_no=5, flags=0)
+    rc, recs1, _ = via.binarize(lib, eng, luma, first_frame_no=1, flags=1)
+    rc2, recs2, _ = via.binarize(lib, eng, luma, first_frame_no=5, flags=0)
     lib.sdv_engine_destroy(eng)
     assert rc == 0 and rc2 == 0
     ok1 = [int(((recs1["frame_number"] == f) & ((recs1["flags"] & 64) != 0)).sum()) for f in (1, 2, 3, 4)]
     ok2 = [int(((recs2["frame_number"] == f) & ((recs2["flags"] & 64) != 0)).sum()) for f in (5, 6, 7, 8)]
     assert ok1[1] == 0 and min(ok1[0], ok1[2], ok1[3]) > 50 and min(ok2) > 50
+
+
+def test_emu_marks_are_consumed_by_one_call(emu_lib, oracle_lib):
+    _marks_are_consumed_by_one_call(ea.bind(emu_lib), dc.HOST)
 
 
 # ---- the product on the GPU ------------------------------------------------------------------------------------------------------
@@ -221,3 +225,9 @@ def test_gpu_double_width():
     recs, stats = eng.binarize_frames(d, first_frame_no=1, new_file=True, doubled=True)
     want, want_stats = oracle_binarize(np.repeat(luma, 2, axis=2), mode=2, doubled=True)
     assert recs.cpu().numpy().tobytes() == want.tobytes() and stats.cpu().numpy().tobytes() == want_stats.tobytes()
+
+
+# ---- the GPU twin of the emulator's call-by-call test: the same body through tests/device_calls.py ----------------------------------------------------
+@pytest.mark.gpu
+def test_gpu_marks_are_consumed_by_one_call():
+    _marks_are_consumed_by_one_call(dc.product_lib(), dc.DEVICE)

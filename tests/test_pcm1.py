@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import device_calls as dc
 import engine_api as ea
 import libs
 import pcm1_api as p1
@@ -97,6 +98,11 @@ def emu(emu_lib):
     return ea.bind(emu_lib)
 
 
+@pytest.fixture(scope="module")
+def gpu():
+    return dc.product_lib()
+
+
 @pytest.mark.parametrize("name", list(p1.CASES))
 def test_emu_matches_oracle(name, emu, oracle_lib):
     recs, st, want_p, want_f = _oracle(name)
@@ -107,14 +113,14 @@ def test_emu_matches_oracle(name, emu, oracle_lib):
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
 
 
-def test_emu_streaming_calls_equal_one_call(emu, oracle_lib):
+def _streaming_calls_equal_one_call(emu, via):
     """The stream may arrive in arbitrary pieces: records wait in the engine for their END_FRAME."""
     recs, st, want_p, want_f = _oracle("file_marks")
     eng = emu.sdv_engine_create(0)
     cuts = [0, 1, 2, 300, 496, 497, 1200, 1201, 2000, len(recs) - 1, len(recs)]
     got_p, got_f = [], []
     for a, b in zip(cuts[:-1], cuts[1:]):
-        rc, p, f = ea.emu_pcm1_stitch(emu, eng, recs[a:b], st if a == 0 else None, pair_cap=8000, frame_cap=16)
+        rc, p, f = via.pcm1_stitch(emu, eng, recs[a:b], st if a == 0 else None, pair_cap=8000, frame_cap=16)
         assert rc == 0
         got_p.append(p.copy())
         got_f.append(f.copy())
@@ -123,46 +129,57 @@ def test_emu_streaming_calls_equal_one_call(emu, oracle_lib):
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
 
 
-def test_emu_edge_inputs(emu, oracle_lib):
+def test_emu_streaming_calls_equal_one_call(emu, oracle_lib):
+    _streaming_calls_equal_one_call(emu, dc.HOST)
+
+
+def _edge_inputs(emu, via, oracle_lib):
     eng = emu.sdv_engine_create(0)
-    rc, p, f = ea.emu_pcm1_stitch(emu, eng, np.zeros(0, dtype=p1.LINE1_DTYPE))            # empty
+    rc, p, f = via.pcm1_stitch(emu, eng, np.zeros(0, dtype=p1.LINE1_DTYPE))            # empty
     assert rc == 0 and len(p) == 0 and len(f) == 0
     recs, st = p1.make_input("clean")
     end = int(np.nonzero(recs["service_type"] == p1.SRV_END_FRAME)[0][0])
-    rc, p, f = ea.emu_pcm1_stitch(emu, eng, recs[:end])                                  # a frame without its END_FRAME: nothing yet
+    rc, p, f = via.pcm1_stitch(emu, eng, recs[:end])                                  # a frame without its END_FRAME: nothing yet
     assert rc == 0 and len(p) == 0 and len(f) == 0
-    rc, p, f = ea.emu_pcm1_stitch(emu, eng, recs[end:end + 1])                           # ... now it completes
+    rc, p, f = via.pcm1_stitch(emu, eng, recs[end:end + 1])                           # ... now it completes
     want_p, want_f = p1.run_cpu(oracle_lib, "orc_", recs[:end + 1], st)
     assert rc == 0 and _same(p, f, want_p, want_f)
     lone = recs[end:end + 1].copy()                                                      # a lone END_FRAME: an all-padding frame
     lone["frame_number"] = 9
-    rc, p, f = ea.emu_pcm1_stitch(emu, eng, lone)
+    rc, p, f = via.pcm1_stitch(emu, eng, lone)
     want_p, want_f = p1.run_cpu(oracle_lib, "orc_", lone, st)
     assert rc == 0 and len(p) == 1470 and _same(p, f, want_p, want_f)
-    rc, p, f = ea.emu_pcm1_stitch(emu, eng, recs, pair_cap=100, frame_cap=8)             # output buffer too small: reported, sized
+    rc, p, f = via.pcm1_stitch(emu, eng, recs, pair_cap=100, frame_cap=8)             # output buffer too small: reported, sized
     assert rc != 0 and b"too small" in emu.sdv_last_error(eng)
     emu.sdv_engine_destroy(eng)
 
 
-def test_emu_failed_call_leaves_the_stream_untouched(emu, oracle_lib):
+def test_emu_edge_inputs(emu, oracle_lib):
+    _edge_inputs(emu, dc.HOST, oracle_lib)
+
+
+def _failed_call_leaves_the_stream_untouched(emu, via):
     """A call that is refused (buffers too small) takes nothing: lines that waited for their END_FRAME still wait and the same
     lines can be handed over again."""
     recs, st, want_p, want_f = _oracle("file_marks")
     eng = emu.sdv_engine_create(0)
     cut = 700                                                                            # inside the second frame
-    rc, p0, f0 = ea.emu_pcm1_stitch(emu, eng, recs[:cut], st, pair_cap=8000, frame_cap=16)
+    rc, p0, f0 = via.pcm1_stitch(emu, eng, recs[:cut], st, pair_cap=8000, frame_cap=16)
     assert rc == 0 and len(f0) >= 1
-    rc, p, f = ea.emu_pcm1_stitch(emu, eng, recs[cut:], None, pair_cap=100, frame_cap=16)
+    rc, p, f = via.pcm1_stitch(emu, eng, recs[cut:], None, pair_cap=100, frame_cap=16)
     assert rc != 0 and b"too small" in emu.sdv_last_error(eng)
-    rc, p1_, f1 = ea.emu_pcm1_stitch(emu, eng, recs[cut:], None, pair_cap=8000, frame_cap=16)   # the same lines again
+    rc, p1_, f1 = via.pcm1_stitch(emu, eng, recs[cut:], None, pair_cap=8000, frame_cap=16)   # the same lines again
     assert rc == 0
     emu.sdv_engine_destroy(eng)
     pairs, frames = np.concatenate([p0, p1_]), np.concatenate([f0, f1])
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
 
 
-@pytest.mark.parametrize("name", ["manual_lost_many", "manual_lost_file_marks"])
-def test_emu_field_buffers_outlive_calls(name, emu):
+def test_emu_failed_call_leaves_the_stream_untouched(emu, oracle_lib):
+    _failed_call_leaves_the_stream_untouched(emu, dc.HOST)
+
+
+def _field_buffers_outlive_calls(name, emu, via):
     """Manual line offsets over damaged fields, the stream cut into calls at every frame end and in the middle of frames: the lines earlier
     frames left in the field buffers are found whether those frames came with this call or with one before."""
     recs, st, want_p, want_f = _oracle(name)
@@ -171,12 +188,17 @@ def test_emu_field_buffers_outlive_calls(name, emu):
     eng = emu.sdv_engine_create(0)
     pairs, frames = [], []
     for a, b in zip(cuts[:-1], cuts[1:]):
-        rc, p, f = ea.emu_pcm1_stitch(emu, eng, recs[a:b], st if a == 0 else None, pair_cap=20000, frame_cap=32)
+        rc, p, f = via.pcm1_stitch(emu, eng, recs[a:b], st if a == 0 else None, pair_cap=20000, frame_cap=32)
         assert rc == 0, emu.sdv_last_error(eng)
         pairs.append(p); frames.append(f)
     emu.sdv_engine_destroy(eng)
     pairs, frames = np.concatenate(pairs), np.concatenate(frames)
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
+
+
+@pytest.mark.parametrize("name", ["manual_lost_many", "manual_lost_file_marks"])
+def test_emu_field_buffers_outlive_calls(name, emu):
+    _field_buffers_outlive_calls(name, emu, dc.HOST)
 
 
 def test_emu_refuses_what_the_reference_never_finishes(emu):
@@ -332,3 +354,25 @@ def test_manual_offsets_always_hand_the_deinterleaver_one_field():
                 bot = u16(cdiv(735 - data, 3) - top_pad)
                 queue = 3 * top_pad + (data if data <= 735 else 0) + 3 * bot
                 assert queue >= 735, (ofs, bottom, cnt, data, top_pad, bot)
+
+
+# ---- the GPU twins of the emulator's stream tests: the same bodies through tests/device_calls.py ------------------------------------------------
+@pytest.mark.gpu
+def test_gpu_streaming_calls_equal_one_call(gpu, oracle_lib):
+    _streaming_calls_equal_one_call(gpu, dc.DEVICE)
+
+
+@pytest.mark.gpu
+def test_gpu_edge_inputs(gpu, oracle_lib):
+    _edge_inputs(gpu, dc.DEVICE, oracle_lib)
+
+
+@pytest.mark.gpu
+def test_gpu_failed_call_leaves_the_stream_untouched(gpu, oracle_lib):
+    _failed_call_leaves_the_stream_untouched(gpu, dc.DEVICE)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["manual_lost_many", "manual_lost_file_marks"])
+def test_gpu_field_buffers_outlive_calls(name, gpu, oracle_lib):
+    _field_buffers_outlive_calls(name, gpu, dc.DEVICE)

@@ -110,12 +110,18 @@ def test_clean_tape_decodes_to_its_audio(ei, oracle_lib):
 
 
 # ---- the kernels on the emulator -----------------------------------------------------------------------------------
+import device_calls as dc  # noqa: E402
 import engine_api as ea  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def emu(emu_lib):
     return ea.bind(emu_lib)
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    return dc.product_lib()
 
 
 # (the 372-frame tape takes the emulator most of a minute: it is left to the GPU test and to the comparison of the oracle with the real reference)
@@ -129,8 +135,7 @@ def test_emu_matches_oracle(name, emu, oracle_lib):
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
 
 
-@pytest.mark.parametrize("name", ["si_file_marks", "ei_wander"])
-def test_emu_streaming_calls_equal_one_call(name, emu, oracle_lib):
+def _streaming_calls_equal_one_call(name, emu, via):
     """The stream may arrive in arbitrary pieces: sub-lines wait in the engine for their END_FRAME, the padding and Control Bit
     histories carry over from call to call."""
     recs, st, want_p, want_f = _oracle(name)
@@ -138,7 +143,7 @@ def test_emu_streaming_calls_equal_one_call(name, emu, oracle_lib):
     cuts = [0, 1, 2, 700, 1473, 1474, 3000, 3001, 6000, len(recs) - 1, len(recs)]
     got_p, got_f = [], []
     for a, b in zip(cuts[:-1], cuts[1:]):
-        rc, p, f = ea.emu_pcm16_stitch(emu, eng, recs[a:b], st if a == 0 else None, pair_cap=9000, frame_cap=16)
+        rc, p, f = via.pcm16_stitch(emu, eng, recs[a:b], st if a == 0 else None, pair_cap=9000, frame_cap=16)
         assert rc == 0
         got_p.append(p.copy())
         got_f.append(f.copy())
@@ -147,44 +152,57 @@ def test_emu_streaming_calls_equal_one_call(name, emu, oracle_lib):
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
 
 
-def test_emu_edge_inputs(emu, oracle_lib):
+@pytest.mark.parametrize("name", ["si_file_marks", "ei_wander"])
+def test_emu_streaming_calls_equal_one_call(name, emu, oracle_lib):
+    _streaming_calls_equal_one_call(name, emu, dc.HOST)
+
+
+def _edge_inputs(emu, via, oracle_lib):
     eng = emu.sdv_engine_create(0)
-    rc, p, f = ea.emu_pcm16_stitch(emu, eng, np.zeros(0, dtype=p16.SUB_DTYPE))            # empty
+    rc, p, f = via.pcm16_stitch(emu, eng, np.zeros(0, dtype=p16.SUB_DTYPE))            # empty
     assert rc == 0 and len(p) == 0 and len(f) == 0
     recs, st = p16.make_input("si_clean")
     end = int(np.nonzero(recs["service_type"] == p16.SRV_END_FRAME)[0][0])
-    rc, p, f = ea.emu_pcm16_stitch(emu, eng, recs[:end], st)                             # a frame without its END_FRAME: nothing yet
+    rc, p, f = via.pcm16_stitch(emu, eng, recs[:end], st)                             # a frame without its END_FRAME: nothing yet
     assert rc == 0 and len(p) == 0 and len(f) == 0
-    rc, p, f = ea.emu_pcm16_stitch(emu, eng, recs[end:end + 1])                          # ... now it completes
+    rc, p, f = via.pcm16_stitch(emu, eng, recs[end:end + 1])                          # ... now it completes
     want_p, want_f = p16.run_cpu(oracle_lib, "orc_", recs[:end + 1], st)
     assert rc == 0 and _same(p, f, want_p, want_f)
     emu.sdv_engine_destroy(eng)
     eng = emu.sdv_engine_create(0)
     lone = recs[end:end + 1].copy()                                                      # a lone END_FRAME: an all-padding frame
     lone["frame_number"] = 9
-    rc, p, f = ea.emu_pcm16_stitch(emu, eng, lone, st)
+    rc, p, f = via.pcm16_stitch(emu, eng, lone, st)
     want_p, want_f = p16.run_cpu(oracle_lib, "orc_", lone, st)
     assert rc == 0 and len(p) == 1470 and _same(p, f, want_p, want_f)
-    rc, p, f = ea.emu_pcm16_stitch(emu, eng, recs, pair_cap=100, frame_cap=8)            # output buffer too small: reported, sized
+    rc, p, f = via.pcm16_stitch(emu, eng, recs, pair_cap=100, frame_cap=8)            # output buffer too small: reported, sized
     assert rc != 0 and b"too small" in emu.sdv_last_error(eng)
     emu.sdv_engine_destroy(eng)
 
 
-def test_emu_failed_call_leaves_the_stream_untouched(emu, oracle_lib):
+def test_emu_edge_inputs(emu, oracle_lib):
+    _edge_inputs(emu, dc.HOST, oracle_lib)
+
+
+def _failed_call_leaves_the_stream_untouched(emu, via):
     """A call that is refused takes nothing: waiting sub-lines still wait, the histories are as before, and the same records can be
     handed over again."""
     recs, st, want_p, want_f = _oracle("si_wander")
     eng = emu.sdv_engine_create(0)
     cut = 4000                                                                           # inside the third frame
-    rc, p0, f0 = ea.emu_pcm16_stitch(emu, eng, recs[:cut], st, pair_cap=20000, frame_cap=16)
+    rc, p0, f0 = via.pcm16_stitch(emu, eng, recs[:cut], st, pair_cap=20000, frame_cap=16)
     assert rc == 0 and len(f0) == 2
-    rc, p, f = ea.emu_pcm16_stitch(emu, eng, recs[cut:], None, pair_cap=100, frame_cap=16)
+    rc, p, f = via.pcm16_stitch(emu, eng, recs[cut:], None, pair_cap=100, frame_cap=16)
     assert rc != 0 and b"too small" in emu.sdv_last_error(eng)
-    rc, p1_, f1 = ea.emu_pcm16_stitch(emu, eng, recs[cut:], None, pair_cap=20000, frame_cap=16)   # the same records again
+    rc, p1_, f1 = via.pcm16_stitch(emu, eng, recs[cut:], None, pair_cap=20000, frame_cap=16)   # the same records again
     assert rc == 0
     emu.sdv_engine_destroy(eng)
     pairs, frames = np.concatenate([p0, p1_]), np.concatenate([f0, f1])
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
+
+
+def test_emu_failed_call_leaves_the_stream_untouched(emu, oracle_lib):
+    _failed_call_leaves_the_stream_untouched(emu, dc.HOST)
 
 
 def test_emu_burst_counters_as_mask_arithmetic(emu):
@@ -218,16 +236,20 @@ def test_emu_refuses_what_the_reference_never_finishes(name, recs, st, emu):
     emu.sdv_engine_destroy(eng)
 
 
-def test_emu_long_frame_takes_the_global_memory_path(emu, oracle_lib):
+def _long_frame_takes_the_global_memory_path(emu, via, oracle_lib):
     """More sub-lines in a frame than the LDS staging holds (1536): the same result, read from global memory."""
     recs, _ = synth.pcm16x0_sub_stream(3, seed=88, cut=(4, 6), lead=(30, 30), trail=(20, 25), p_bad=0.03, p_picked=0.05, rate_44100=True)
     assert max(np.diff(np.nonzero(recs["service_type"] == p16.SRV_END_FRAME)[0])) > 1536
     st = p16.default_settings()
     want_p, want_f = p16.run_cpu(oracle_lib, "orc_", recs, st)
     eng = emu.sdv_engine_create(0)
-    rc, pairs, frames = ea.emu_pcm16_stitch(emu, eng, recs, st)
+    rc, pairs, frames = via.pcm16_stitch(emu, eng, recs, st)
     emu.sdv_engine_destroy(eng)
     assert rc == 0 and _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
+
+
+def test_emu_long_frame_takes_the_global_memory_path(emu, oracle_lib):
+    _long_frame_takes_the_global_memory_path(emu, dc.HOST, oracle_lib)
 
 
 # ---- the product on the GPU ------------------------------------------------------------------------------------------
@@ -463,8 +485,7 @@ def test_emu_long_tape_matches_oracle(ei, hurt, emu, oracle_lib):
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
 
 
-@pytest.mark.parametrize("cuts", [(68, 69, 101, 140)])
-def test_emu_long_ei_tape_in_calls_matches_oracle(cuts, emu, oracle_lib):
+def _long_ei_tape_in_calls_matches_oracle(cuts, emu, via, oracle_lib):
     """The EI tape above in several calls: from the second call on the padding history is full when a call begins, so the analysis makes its padding
     tables for that one padding (round 4) - all of them again for the hurt frames (70, 71, 100, 131), and the whole call once more where the history
     says something else in the middle of it (the second tape: its later frames are padded otherwise)."""
@@ -477,13 +498,18 @@ def test_emu_long_ei_tape_in_calls_matches_oracle(cuts, emu, oracle_lib):
     lo = 0
     for k, c in enumerate(list(cuts) + [150]):
         hi = int(ends[c - 1]) + 1
-        rc, pairs, frames = ea.emu_pcm16_stitch(emu, eng, recs[lo:hi], st if k == 0 else None)
+        rc, pairs, frames = via.pcm16_stitch(emu, eng, recs[lo:hi], st if k == 0 else None)
         assert rc == 0
         got_p.append(pairs); got_f.append(frames)
         lo = hi
     emu.sdv_engine_destroy(eng)
     pairs, frames = np.concatenate(got_p), np.concatenate(got_f)
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
+
+
+@pytest.mark.parametrize("cuts", [(68, 69, 101, 140)])
+def test_emu_long_ei_tape_in_calls_matches_oracle(cuts, emu, oracle_lib):
+    _long_ei_tape_in_calls_matches_oracle(cuts, emu, dc.HOST, oracle_lib)
 
 
 def test_emu_ei_call_runs_again_with_full_tables(emu, oracle_lib, monkeypatch, capfd):
@@ -530,3 +556,33 @@ def test_gpu_long_damaged_tape_matches_oracle(ei, oracle_lib):
     pairs = p.cpu().numpy().reshape(-1).view(PAIR_DTYPE)
     frames = f.cpu().numpy().reshape(-1).view(p16.FRASM16_DTYPE)
     assert len(want_f) == n and _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
+
+
+# ---- the GPU twins of the emulator's stream tests: the same bodies through tests/device_calls.py ------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["si_file_marks", "ei_wander"])
+def test_gpu_streaming_calls_equal_one_call(name, gpu, oracle_lib):
+    _streaming_calls_equal_one_call(name, gpu, dc.DEVICE)
+
+
+@pytest.mark.gpu
+def test_gpu_edge_inputs(gpu, oracle_lib):
+    _edge_inputs(gpu, dc.DEVICE, oracle_lib)
+
+
+@pytest.mark.gpu
+def test_gpu_failed_call_leaves_the_stream_untouched(gpu, oracle_lib):
+    _failed_call_leaves_the_stream_untouched(gpu, dc.DEVICE)
+
+
+@pytest.mark.gpu
+def test_gpu_long_frame_takes_the_global_memory_path(gpu, oracle_lib):
+    """analyse_body<false> (pcm16_stitch_device.h): the body asserts that a frame of the tape has more than 1536 sub-lines."""
+    _long_frame_takes_the_global_memory_path(gpu, dc.DEVICE, oracle_lib)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cuts", [(68, 69, 101, 140)])
+def test_gpu_long_ei_tape_in_calls_matches_oracle(cuts, gpu, oracle_lib):
+    """... and the call that runs again with full tables, on the tape that causes it by itself (the hurt frames 70, 71, 100, 131)."""
+    _long_ei_tape_in_calls_matches_oracle(cuts, gpu, dc.DEVICE, oracle_lib)

@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+import device_calls as dc
 import engine_api as ea
 import libs
 import pcm16_api as p16
@@ -63,6 +64,11 @@ def emu(emu_lib):
     return ea.bind(emu_lib)
 
 
+@pytest.fixture(scope="module")
+def gpu():
+    return dc.product_lib()
+
+
 @pytest.mark.parametrize("name", CASES)
 def test_emu_lines_match_oracle(name, emu, oracle_lib):
     recs, st, want_p, want_f, want_l = _oracle(name)
@@ -73,41 +79,47 @@ def test_emu_lines_match_oracle(name, emu, oracle_lib):
     emu.sdv_engine_destroy(eng)
 
 
-def test_emu_lines_in_calls_and_too_small(emu, oracle_lib):
+def _lines_in_calls_and_too_small(emu, via):
     recs, st, want_p, want_f, want_l = _oracle("si_file_marks")
     eng = emu.sdv_engine_create(0)
     cuts = [0, len(recs) // 3, len(recs) // 3 + 11, len(recs)]
     got = []
     for a, b in zip(cuts[:-1], cuts[1:]):
-        rc, p, f, ln = ea.emu_pcm16_stitch_lines(emu, eng, recs[a:b], st if a == 0 else None)
+        rc, p, f, ln = via.pcm16_stitch_lines(emu, eng, recs[a:b], st if a == 0 else None)
         assert rc == 0
         got.append(ln)
     assert np.concatenate(got).tobytes() == want_l.tobytes()
     emu.sdv_engine_destroy(eng)
     eng = emu.sdv_engine_create(0)
-    rc, p, f, ln = ea.emu_pcm16_stitch_lines(emu, eng, recs, st, line_cap=100)
-    assert rc != 0 and b"assembled sub-line records" in emu.sdv_last_error(eng) and ea.emu_pcm16_stitch_lines.last_count == len(want_l)
-    rc, p, f, ln = ea.emu_pcm16_stitch_lines(emu, eng, recs, st)                 # the refused call took nothing: once more with room
+    rc, p, f, ln = via.pcm16_stitch_lines(emu, eng, recs, st, line_cap=100)
+    assert rc != 0 and b"assembled sub-line records" in emu.sdv_last_error(eng) and via.last_count == len(want_l)
+    rc, p, f, ln = via.pcm16_stitch_lines(emu, eng, recs, st)                 # the refused call took nothing: once more with room
     assert rc == 0 and ln.tobytes() == want_l.tobytes()
     emu.sdv_engine_destroy(eng)
 
 
-def test_emu_window_is_the_lines_renderer_on_the_feed(emu, oracle_lib):
+def test_emu_lines_in_calls_and_too_small(emu, oracle_lib):
+    _lines_in_calls_and_too_small(emu, dc.HOST)
+
+
+def _window_is_the_lines_renderer_on_the_feed(emu, via):
     """sdv_vis_render_lines(SDV_VIS_PCM16X0_LINES) on the feed = the oracle's renderer on the oracle's feed."""
     import ctypes as C
     recs, st, want_p, want_f, want_l = _oracle("si_picked_forced")
     eng = emu.sdv_engine_create(0)
-    rc, pairs, frames, lines = ea.emu_pcm16_stitch_lines(emu, eng, recs, st)
+    rc, pairs, frames, lines = via.pcm16_stitch_lines(emu, eng, recs, st)
     assert rc == 0
-    w, h = ra.SIZE[ra.PCM16X0]
     n = ra.n_frames(lines)
-    out = np.zeros((n, h, w), dtype=np.uint32)
-    nf = C.c_size_t(0)
     emu.sdv_vis_render_lines.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
-    assert emu.sdv_vis_render_lines(eng, ra.PCM16X0, lines.ctypes.data, len(lines), out.ctypes.data, n, C.byref(nf), None) == 0 and nf.value == n
+    rc, out, nf = via.render_lines(emu, eng, ra.PCM16X0, lines, cap=n)
+    assert rc == 0 and nf == n
     want, _ = ra.run_oracle(ra.PCM16X0, want_l)
     assert (out == want).all()
     emu.sdv_engine_destroy(eng)
+
+
+def test_emu_window_is_the_lines_renderer_on_the_feed(emu, oracle_lib):
+    _window_is_the_lines_renderer_on_the_feed(emu, dc.HOST)
 
 
 @pytest.mark.gpu
@@ -132,3 +144,14 @@ def test_gpu_lines_and_window_match_oracle(name):
         z = np.load(os.path.join(GOLD, "pcm16asm_" + name + ".npz"))
         assert hashlib.sha256(got.tobytes()).hexdigest() == str(z["lines_sha256"])
         assert ra.digest(canvases.reshape(want.shape), ra.written(ra.PCM16X0, got)) == str(z["canvases_sha256"])
+
+
+# ---- the GPU twins of the emulator's call-by-call tests: the same bodies through tests/device_calls.py ----------------------------------------------------
+@pytest.mark.gpu
+def test_gpu_lines_in_calls_and_too_small(gpu, oracle_lib):
+    _lines_in_calls_and_too_small(gpu, dc.DEVICE)
+
+
+@pytest.mark.gpu
+def test_gpu_window_is_the_lines_renderer_on_the_feed(gpu, oracle_lib):
+    _window_is_the_lines_renderer_on_the_feed(gpu, dc.DEVICE)

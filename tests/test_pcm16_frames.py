@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import device_calls as dc
 import libs
 import pcm16_frames_api as pf
 
@@ -116,18 +117,23 @@ def test_emu_stream_in_two_calls(mode, kw, emu_lib, oracle_lib):
     assert ((i1.rounds, i1.frames_launched), (i2.rounds, i2.frames_launched)) == TWO_CALLS_SCHEDULE[mode, kw["seed"]]
 
 
-def test_emu_bad_arguments(emu_lib):
+def _bad_arguments(lib, via):
     import ctypes as C
-    eng = C.c_void_p(emu_lib.sdv_engine_create(0))
+    eng = C.c_void_p(lib.sdv_engine_create(0))
     luma = np.zeros((1, 8, 200), np.uint8)
-    rc, _, _ = pf.run_engine(emu_lib, eng, luma[:, :, :180], 1, {})
+    rc, _, _ = via.frames(lib, pf, eng, luma[:, :, :180], 1, {})
     assert rc == 3                                              # SDV_ERR_SHORT_LINE: under 193 px
-    f = emu_lib.sdv_pcm16x0_binarize_frames
-    recs = np.zeros(27, dtype=pf.BIN16_DTYPE); st = np.zeros(1, dtype=pf.STATS_DTYPE)
-    emu_lib.sdv_set_mode(eng, 1)
-    assert f(eng, luma.ctypes.data, 200, 1600, 200, 8, 1, 1, 1, recs.ctypes.data, 27, st.ctypes.data, 1, None) == -1      # NEW_FILE needs 28
-    assert f(eng, None, 200, 1600, 200, 8, 1, 1, 0, recs.ctypes.data, 27, st.ctypes.data, 1, None) == 1
-    emu_lib.sdv_engine_destroy(eng)
+    f = lib.sdv_pcm16x0_binarize_frames
+    recs = via.zeros(27, pf.BIN16_DTYPE, 28); st = via.zeros(1, pf.STATS_DTYPE); src = via.array(luma)
+    lib.sdv_set_mode(eng, 1)
+    assert f(eng, via.ptr(src), 200, 1600, 200, 8, 1, 1, 1, via.ptr(recs), 27, via.ptr(st), 1, via.stream()) == -1      # NEW_FILE needs 28
+    assert f(eng, None, 200, 1600, 200, 8, 1, 1, 0, via.ptr(recs), 27, via.ptr(st), 1, via.stream()) == 1
+    via.check(recs, st)
+    lib.sdv_engine_destroy(eng)
+
+
+def test_emu_bad_arguments(emu_lib):
+    _bad_arguments(emu_lib, dc.HOST)
 
 
 # ---- the product on the GPU, through the C-ABI -----------------------------------------------------------------------
@@ -220,3 +226,11 @@ def test_gpu_full_size_batch_decodes_to_what_was_rendered():
         even = fr[3 * (h // 2) + 1:3 * h + 1].reshape(h // 2, 3)
         assert (odd["words"] == w[f % 6, 0::2]).all() and (even["words"] == w[f % 6, 1::2]).all()
     assert (stats["lines_pcm_odd"] == h // 2).all() and (stats["lines_bad_odd"] <= 1).all()
+
+
+# ---- the GPU twin of the emulator's refusals: the same body through tests/device_calls.py -------------------------------------------------------------
+@pytest.mark.gpu
+def test_gpu_bad_arguments():
+    """Every one of these refusals is the host's, ahead of any device work: markerless_frames_engine.inc:41-54 (null video, short line, the record
+    count against the capacity that is stated)."""
+    _bad_arguments(dc.product_lib(), dc.DEVICE)

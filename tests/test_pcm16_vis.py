@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+import device_calls as dc
 import engine_api as ea
 import libs
 import pcm16_api as p16
@@ -90,6 +91,11 @@ def emu(emu_lib):
     return ea.bind(emu_lib)
 
 
+@pytest.fixture(scope="module")
+def gpu():
+    return dc.product_lib()
+
+
 def _emu_canvases(lib, eng, blocks, per):
     lib.sdv_vis_render_blocks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
     w, h = ra.SIZE[ra.PCM16X0_BLOCKS]
@@ -112,23 +118,27 @@ def test_emu_blocks_match_oracle(name, emu, oracle_lib):
     emu.sdv_engine_destroy(eng)
 
 
-def test_emu_blocks_in_calls_and_too_small(emu, oracle_lib):
+def _blocks_in_calls_and_too_small(emu, via):
     recs, st, want_p, want_f, want_b, per = _oracle("si_file_marks")
     eng = emu.sdv_engine_create(0)
     cuts = [0, len(recs) // 3, len(recs) // 3 + 11, len(recs)]
     got = []
     for a, b in zip(cuts[:-1], cuts[1:]):
-        rc, p, f, bl = ea.emu_pcm16_stitch_vis(emu, eng, recs[a:b], st if a == 0 else None)
+        rc, p, f, bl = via.pcm16_stitch_vis(emu, eng, recs[a:b], st if a == 0 else None)
         assert rc == 0
         got.append(bl)
     assert np.concatenate(got).tobytes() == want_b.tobytes()
     emu.sdv_engine_destroy(eng)
     eng = emu.sdv_engine_create(0)
-    rc, p, f, bl = ea.emu_pcm16_stitch_vis(emu, eng, recs, st, block_cap=7)
-    assert rc != 0 and b"blocks for the visualiser" in emu.sdv_last_error(eng) and ea.emu_pcm16_stitch_vis.last_count == len(want_b)
-    rc, p, f, bl = ea.emu_pcm16_stitch_vis(emu, eng, recs, st)                 # the refused call took nothing: once more with room
+    rc, p, f, bl = via.pcm16_stitch_vis(emu, eng, recs, st, block_cap=7)
+    assert rc != 0 and b"blocks for the visualiser" in emu.sdv_last_error(eng) and via.last_count == len(want_b)
+    rc, p, f, bl = via.pcm16_stitch_vis(emu, eng, recs, st)                 # the refused call took nothing: once more with room
     assert rc == 0 and bl.tobytes() == want_b.tobytes()
     emu.sdv_engine_destroy(eng)
+
+
+def test_emu_blocks_in_calls_and_too_small(emu, oracle_lib):
+    _blocks_in_calls_and_too_small(emu, dc.HOST)
 
 
 @pytest.mark.gpu
@@ -153,3 +163,9 @@ def test_gpu_blocks_and_canvases_match_oracle(name):
         z = np.load(os.path.join(GOLD, "pcm16vis_" + name + ".npz"))
         assert hashlib.sha256(got.tobytes()).hexdigest() == str(z["blocks_sha256"])
         assert ra.digest(canvases, ra.written_blocks(ra.PCM16X0_BLOCKS, per)) == str(z["canvases_sha256"])
+
+
+# ---- the GPU twin of the emulator's call-by-call test: the same body through tests/device_calls.py ----------------------------------------------------
+@pytest.mark.gpu
+def test_gpu_blocks_in_calls_and_too_small(gpu, oracle_lib):
+    _blocks_in_calls_and_too_small(gpu, dc.DEVICE)

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import device_calls as dc
 import engine_api as ea
 import libs
 import pcm1_api as p1
@@ -59,6 +60,11 @@ def emu(emu_lib):
     return ea.bind(emu_lib)
 
 
+@pytest.fixture(scope="module")
+def gpu():
+    return dc.product_lib()
+
+
 @pytest.mark.parametrize("name", CASES)
 def test_emu_matches_oracle(name, emu, oracle_lib):
     recs, st, want_p, want_f, want_b, want_l = _oracle(name)
@@ -69,25 +75,29 @@ def test_emu_matches_oracle(name, emu, oracle_lib):
     _check(name, blocks, lines, want_b, want_l)
 
 
-def test_emu_feeds_in_calls_and_too_small(emu, oracle_lib):
+def _feeds_in_calls_and_too_small(emu, via):
     """The feeds over a stream cut into calls (frames complete in later calls), one feed alone, and buffers that are too small."""
     recs, st, want_p, want_f, want_b, want_l = _oracle("file_marks")
     eng = emu.sdv_engine_create(0)
     cuts = [0, len(recs) // 3, len(recs) // 3 + 7, len(recs)]
     got_b, got_l = [], []
     for a, b in zip(cuts[:-1], cuts[1:]):
-        rc, p, f, bl, ln = ea.emu_pcm1_stitch_vis(emu, eng, recs[a:b], st if a == 0 else None)
+        rc, p, f, bl, ln = via.pcm1_stitch_vis(emu, eng, recs[a:b], st if a == 0 else None)
         assert rc == 0
         got_b.append(bl); got_l.append(ln)
     _check("file_marks", np.concatenate(got_b), np.concatenate(got_l), want_b, want_l)
     emu.sdv_engine_destroy(eng)
     eng = emu.sdv_engine_create(0)
-    rc, p, f, bl, ln = ea.emu_pcm1_stitch_vis(emu, eng, recs, st, lines=False)
-    assert rc == 0 and len(ln) == 0 and ea.emu_pcm1_stitch_vis.last_counts == (len(want_b), 0)
+    rc, p, f, bl, ln = via.pcm1_stitch_vis(emu, eng, recs, st, lines=False)
+    assert rc == 0 and len(ln) == 0 and via.last_counts == (len(want_b), 0)
     _check("file_marks", bl, want_l, want_b, want_l)
-    rc, p, f, bl, ln = ea.emu_pcm1_stitch_vis(emu, eng, recs, st, block_cap=5)
-    assert rc != 0 and b"visualiser buffers too small" in emu.sdv_last_error(eng) and ea.emu_pcm1_stitch_vis.last_counts == (len(want_b), len(want_l))
+    rc, p, f, bl, ln = via.pcm1_stitch_vis(emu, eng, recs, st, block_cap=5)
+    assert rc != 0 and b"visualiser buffers too small" in emu.sdv_last_error(eng) and via.last_counts == (len(want_b), len(want_l))
     emu.sdv_engine_destroy(eng)
+
+
+def test_emu_feeds_in_calls_and_too_small(emu, oracle_lib):
+    _feeds_in_calls_and_too_small(emu, dc.HOST)
 
 
 def _gpu_run(eng, recs, st, torch):
@@ -126,3 +136,9 @@ def test_gpu_matches_golden_from_reference(name):
     pairs, frames, blocks, lines = _gpu_run(Engine(0), recs, st, torch)
     assert p1.comparable_blocks(blocks).tobytes() == np.ascontiguousarray(z["blocks"]).tobytes()
     assert lines[lines["flags"] != p1.P1S_SKIP].tobytes() == np.ascontiguousarray(z["lines"]).tobytes()
+
+
+# ---- the GPU twin of the emulator's call-by-call test: the same body through tests/device_calls.py ----------------------------------------------------
+@pytest.mark.gpu
+def test_gpu_feeds_in_calls_and_too_small(gpu, oracle_lib):
+    _feeds_in_calls_and_too_small(gpu, dc.DEVICE)

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import device_calls as dc
 import libs
 import render_api as ra
 
@@ -76,6 +77,11 @@ def emu(emu_lib):
     return lib
 
 
+@pytest.fixture(scope="module")
+def gpu():
+    return dc.product_lib()
+
+
 def _emu_run(emu, eng, kind, recs, cap=None):
     w, h = ra.SIZE[kind]
     n = ra.n_frames(recs) if cap is None else cap
@@ -97,29 +103,33 @@ def test_emu_matches_oracle(name, emu):
     assert (out == want).all(), _diff(out, want, np.ones_like(want, dtype=bool))
 
 
-def test_emu_calls_continue_on_the_kept_canvas(emu):
+def _calls_continue_on_the_kept_canvas(emu, via):
     """Two calls = one call; a reset in between starts from a blank canvas; a buffer that is too small is refused with the count."""
     kind, recs = ra.make_input("stc_shrinking")
     want, _ = ra.run_oracle(kind, recs)
     ends = np.nonzero(recs["service_type"] == ra.SRV_END_FRAME)[0]
     cut = ends[0] + 1
     eng = emu.sdv_engine_create(0)
-    rc, a, _ = _emu_run(emu, eng, kind, recs[:cut])
+    rc, a, _ = via.render_lines(emu, eng, kind, recs[:cut])
     assert rc == 0
-    rc, b, n = _emu_run(emu, eng, kind, recs[cut:], cap=1)
+    rc, b, n = via.render_lines(emu, eng, kind, recs[cut:], cap=1)
     assert rc != 0 and n == 3 and b"3 canvases" in emu.sdv_last_error(eng)
-    rc, b, _ = _emu_run(emu, eng, kind, recs[cut:])
+    rc, b, _ = via.render_lines(emu, eng, kind, recs[cut:])
     assert rc == 0 and (np.concatenate([a, b]) == want).all()
-    assert emu.sdv_vis_reset(eng, kind, None) == 0
-    rc, c, _ = _emu_run(emu, eng, kind, recs[cut:])
+    assert emu.sdv_vis_reset(eng, kind, via.stream()) == 0
+    rc, c, _ = via.render_lines(emu, eng, kind, recs[cut:])
     fresh, _ = ra.run_oracle(kind, recs[cut:])
     assert rc == 0 and (c == fresh).all()
-    rc, d, n = _emu_run(emu, eng, kind, recs[cut:ends[1]])         # no frame ends in these records: nothing is handed out
+    rc, d, n = via.render_lines(emu, eng, kind, recs[cut:ends[1]])         # no frame ends in these records: nothing is handed out
     assert rc == 0 and n == 0
     w, h = C.c_uint32(0), C.c_uint32(0)
     assert emu.sdv_vis_canvas_size(kind, C.byref(w), C.byref(h)) == 0 and (w.value, h.value) == ra.SIZE[kind]
     assert emu.sdv_vis_canvas_size(10, C.byref(w), C.byref(h)) != 0          # no such canvas
     emu.sdv_engine_destroy(eng)
+
+
+def test_emu_calls_continue_on_the_kept_canvas(emu):
+    _calls_continue_on_the_kept_canvas(emu, dc.HOST)
 
 
 # ---- the product on the GPU --------------------------------------------------------------------------------------------------------
@@ -210,8 +220,8 @@ def test_oracle_block_canvases_match_golden(name, oracle_lib):
     assert (_masked(out[-1], mask[-1]) == z["last_canvas"]).all()
 
 
-def _emu_blocks(emu, name, two_calls=False):
-    """The product's path in the emulator: records -> sdv_stitch_frames with a block buffer set -> sdv_vis_render_blocks."""
+def _emu_blocks(emu, name, two_calls=False, via=dc.HOST):
+    """The product's path (in the emulator, or with via=dc.DEVICE on the GPU): records -> sdv_stitch_frames with a block buffer set -> sdv_vis_render_blocks."""
     import engine_api as ea
     import stitch_cases as sc
     import stitch_api as sa
@@ -224,22 +234,22 @@ def _emu_blocks(emu, name, two_calls=False):
     lib.sdv_stitch_block_count.argtypes = [C.c_void_p]
     lib.sdv_vis_render_blocks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
     eng = lib.sdv_engine_create(0)
-    buf = np.zeros(len(want_blocks) + 8, dtype=sa.BLOCK_DTYPE)
-    assert lib.sdv_set_stitch_block_output(eng, buf.ctypes.data, len(buf)) == 0
+    buf = via.zeros(len(want_blocks) + 8, sa.BLOCK_DTYPE)
+    assert lib.sdv_set_stitch_block_output(eng, via.ptr(buf), len(buf)) == 0
     ends = np.nonzero(recs["service_type"] == 5)[0]
     cuts = [0, int(ends[len(ends) // 2]) + 1, len(recs)] if two_calls else [0, len(recs)]
     w, h = ra.SIZE[kind]
     canv, got_blocks, frames = [], [], []
     for a, b in zip(cuts[:-1], cuts[1:]):
-        rc, p, f = ea.emu_stitch(lib, eng, recs[a:b], st if a == 0 else None)
+        rc, p, f = via.stitch(lib, eng, recs[a:b], st if a == 0 else None)
         assert rc == 0
         nb = lib.sdv_stitch_block_count(eng)
-        got_blocks.append(buf[:nb].copy())
+        got_blocks.append(via.get(buf, nb))
         per_call = np.ascontiguousarray(f["blocks_total"][f["service_type"] == 0].astype(np.uint32))
         assert int(per_call.sum()) == nb
-        out = np.zeros((max(len(per_call), 1), h, w), dtype=np.uint32)
-        assert lib.sdv_vis_render_blocks(eng, kind, buf.ctypes.data, nb, per_call.ctypes.data, len(per_call), out.ctypes.data, len(per_call), None) == 0
-        canv.append(out[:len(per_call)])
+        rc, out = via.render_rows(lib, "sdv_vis_render_blocks", eng, kind, buf, nb, per_call)
+        assert rc == 0
+        canv.append(out)
     lib.sdv_engine_destroy(eng)
     return kind, want_blocks, per, np.concatenate(got_blocks), np.concatenate(canv)
 
@@ -252,14 +262,18 @@ def test_emu_blocks_and_their_canvases_match_oracle(name, emu):
     assert (canvases == want).all(), _diff(canvases, want, np.ones_like(want, dtype=bool))
 
 
-def test_emu_blocks_in_two_calls(emu):
-    kind, want_blocks, per, blocks, canvases = _emu_blocks(emu, "blk_burst", two_calls=True)
+def _blocks_in_two_calls(emu, via):
+    kind, want_blocks, per, blocks, canvases = _emu_blocks(emu, "blk_burst", two_calls=True, via=via)
     assert blocks.tobytes() == want_blocks.tobytes()
     want, _ = ra.run_oracle_blocks(kind, want_blocks, per)
     assert (canvases == want).all()
 
 
-def test_emu_block_buffer_too_small_is_refused_with_the_count(emu):
+def test_emu_blocks_in_two_calls(emu):
+    _blocks_in_two_calls(emu, dc.HOST)
+
+
+def _block_buffer_too_small_is_refused_with_the_count(emu, via):
     import engine_api as ea
     import stitch_cases as sc
     import stitch_api as sa
@@ -270,11 +284,16 @@ def test_emu_block_buffer_too_small_is_refused_with_the_count(emu):
     lib.sdv_stitch_block_count.restype = C.c_size_t
     lib.sdv_stitch_block_count.argtypes = [C.c_void_p]
     eng = lib.sdv_engine_create(0)
-    buf = np.zeros(100, dtype=sa.BLOCK_DTYPE)
-    assert lib.sdv_set_stitch_block_output(eng, buf.ctypes.data, len(buf)) == 0
-    rc, p, f = ea.emu_stitch(lib, eng, recs, st)
+    buf = via.zeros(100, sa.BLOCK_DTYPE, 2530)          # (on the device: room for what the call needs behind the 100 it is told of, then the guard)
+    assert lib.sdv_set_stitch_block_output(eng, via.ptr(buf), len(buf)) == 0
+    rc, p, f = via.stitch(lib, eng, recs, st)
     assert rc != 0 and b"data blocks are needed" in lib.sdv_last_error(eng) and lib.sdv_stitch_block_count(eng) == 2530
+    via.check(buf)
     lib.sdv_engine_destroy(eng)
+
+
+def test_emu_block_buffer_too_small_is_refused_with_the_count(emu):
+    _block_buffer_too_small_is_refused_with_the_count(emu, dc.HOST)
 
 
 @pytest.mark.gpu
@@ -445,7 +464,7 @@ def test_oracle_pcm1_stitcher_canvases_match_golden(name, oracle_lib):
     assert (_masked(out[-1], mask[-1]) == z["last_line_canvas"]).all()
 
 
-def _emu_p1vis(emu, blocks, per, lines, calls=1):
+def _emu_p1vis(emu, blocks, per, lines, calls=1, via=dc.HOST):
     import engine_api as ea
     lib = ea.bind(emu)
     lib.sdv_vis_render_blocks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -454,12 +473,11 @@ def _emu_p1vis(emu, blocks, per, lines, calls=1):
     n = len(per)
     cuts = [0, n] if calls == 1 else [0, n // 2, n]
     for a, b in zip(cuts[:-1], cuts[1:]):
-        w, h = ra.SIZE[ra.PCM1_BLOCKS]
-        out = np.zeros((b - a, h, w), dtype=np.uint32)
         pb, pp = np.ascontiguousarray(blocks[16 * a:16 * b]), np.ascontiguousarray(per[a:b])
-        assert lib.sdv_vis_render_blocks(eng, ra.PCM1_BLOCKS, pb.ctypes.data, len(pb), pp.ctypes.data, len(pp), out.ctypes.data, len(pp), None) == 0
+        rc, out = via.render_rows(lib, "sdv_vis_render_blocks", eng, ra.PCM1_BLOCKS, via.array(pb), len(pb), pp)
+        assert rc == 0
         bc.append(out)
-        rc, out, got = _emu_run(emu, eng, ra.PCM1_ASM, np.ascontiguousarray(lines[1470 * a:1470 * b]), cap=b - a)
+        rc, out, got = via.render_lines(lib, eng, ra.PCM1_ASM, np.ascontiguousarray(lines[1470 * a:1470 * b]), cap=b - a)
         assert rc == 0 and got == b - a
         lc.append(out)
     lib.sdv_engine_destroy(eng)
@@ -476,13 +494,17 @@ def test_emu_pcm1_stitcher_canvases_match_oracle(name, emu):
     assert (lc == want).all(), _diff(lc, want, np.ones_like(want, dtype=bool))
 
 
-def test_emu_pcm1_stitcher_canvases_in_two_calls(emu):
+def _pcm1_stitcher_canvases_in_two_calls(emu, via):
     blocks, per, lines = ra.make_p1vis_input("manual_lost_lines")
-    bc, lc = _emu_p1vis(emu, blocks, per, lines, calls=2)
+    bc, lc = _emu_p1vis(emu, blocks, per, lines, calls=2, via=via)
     want, _ = ra.run_oracle_blocks(ra.PCM1_BLOCKS, blocks, per)
     assert (bc == want).all()
     want, _ = ra.run_oracle_lines_into(ra.PCM1_ASM, lines, len(per))
     assert (lc == want).all()
+
+
+def test_emu_pcm1_stitcher_canvases_in_two_calls(emu):
+    _pcm1_stitcher_canvases_in_two_calls(emu, dc.HOST)
 
 
 @pytest.mark.gpu
@@ -513,3 +535,24 @@ def test_gpu_pcm1_stitcher_feeds_to_canvases_match_oracle(name):
         z = np.load(os.path.join(GOLD, "render_p1vis_" + name + ".npz"))
         assert ra.digest(bc, ra.written_p1_blocks(per)) == str(z["block_canvases_sha256"])
         assert ra.digest(lc, ra.written_p1_asm(lines)) == str(z["line_canvases_sha256"])
+
+
+# ---- the GPU twins of the emulator's call-by-call tests: the same bodies through tests/device_calls.py ----------------------------------------------
+@pytest.mark.gpu
+def test_gpu_calls_continue_on_the_kept_canvas(gpu, oracle_lib):
+    _calls_continue_on_the_kept_canvas(gpu, dc.DEVICE)
+
+
+@pytest.mark.gpu
+def test_gpu_blocks_in_two_calls(gpu, oracle_lib):
+    _blocks_in_two_calls(gpu, dc.DEVICE)
+
+
+@pytest.mark.gpu
+def test_gpu_block_buffer_too_small_is_refused_with_the_count(gpu, oracle_lib):
+    _block_buffer_too_small_is_refused_with_the_count(gpu, dc.DEVICE)
+
+
+@pytest.mark.gpu
+def test_gpu_pcm1_stitcher_canvases_in_two_calls(gpu, oracle_lib):
+    _pcm1_stitcher_canvases_in_two_calls(gpu, dc.DEVICE)

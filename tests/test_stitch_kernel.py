@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import device_calls as dc
 import engine_api as ea
 import libs
 import stitch_api as sa
@@ -38,6 +39,11 @@ def emu(emu_lib):
     return ea.bind(emu_lib)
 
 
+@pytest.fixture(scope="module")
+def gpu():
+    return dc.product_lib()
+
+
 @pytest.mark.parametrize("name", EMU_CASES)
 def test_emu_matches_oracle(name, emu, oracle_lib):
     recs, st = sc.make_input(name, lambda luma: oracle_binarize(luma, mode=2))
@@ -49,7 +55,7 @@ def test_emu_matches_oracle(name, emu, oracle_lib):
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
 
 
-def test_emu_streaming_calls_equal_one_call(emu, oracle_lib):
+def _streaming_calls_equal_one_call(emu, via):
     """The stream may arrive in arbitrary pieces (frame by frame, mid-frame): the engine keeps what cannot be stitched yet."""
     recs, st = sc.make_input("ntsc_bad5", lambda luma: oracle_binarize(luma, mode=2))
     want_p, want_f = sa.run_cpu(libs.load_oracle(), "orc_", recs, st)
@@ -57,12 +63,16 @@ def test_emu_streaming_calls_equal_one_call(emu, oracle_lib):
     cuts = [0, 1, 300, 490, 1000, 1471, 1472, 2500, len(recs)]
     got_p, got_f = [], []
     for a, b in zip(cuts[:-1], cuts[1:]):
-        rc, p, f = ea.emu_stitch(emu, eng, recs[a:b], st if a == 0 else None, pair_cap=20000, frame_cap=64)
+        rc, p, f = via.stitch(emu, eng, recs[a:b], st if a == 0 else None, pair_cap=20000, frame_cap=64)
         assert rc == 0
         got_p.append(p.copy()); got_f.append(f.copy())
     emu.sdv_engine_destroy(eng)
     pairs, frames = np.concatenate(got_p), np.concatenate(got_f)
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
+
+
+def test_emu_streaming_calls_equal_one_call(emu, oracle_lib):
+    _streaming_calls_equal_one_call(emu, dc.HOST)
 
 
 def _frame_cuts(recs, frames_per_call):
@@ -109,8 +119,7 @@ PIPE_CASES = {
 }
 
 
-@pytest.mark.parametrize("name", list(PIPE_CASES))
-def test_emu_pipelined_calls_equal_one_call(name, emu, oracle_lib):
+def _pipelined_calls_equal_one_call(name, emu, via):
     """A stream that plays is stitched without waiting for the host between the stages (stitch_engine.inc "1p"): whatever the later calls meet -
     more frames than the estimate, damage, another resolution or field order, the end of the file - the PCM stream is the sequential one's."""
     tape_kw, per_call, dmg, want_piped = PIPE_CASES[name]
@@ -128,13 +137,14 @@ def test_emu_pipelined_calls_equal_one_call(name, emu, oracle_lib):
     got_p, got_f, piped = [], [], []
     info = ea.StitchInfo()
     for a, b in zip(cuts[:-1], cuts[1:]):
-        rc, p, f = ea.emu_stitch(emu, eng, recs[a:b], st if a == 0 else None, pair_cap=30000, frame_cap=64)
+        rc, p, f = via.stitch(emu, eng, recs[a:b], st if a == 0 else None, pair_cap=30000, frame_cap=64)
         assert rc == 0, (a, b)
         got_p.append(p.copy()); got_f.append(f.copy())
         assert emu.sdv_get_stitch_info(eng, C.byref(info)) == 0
         piped.append(int(info.pipelined))
     emu.sdv_engine_destroy(eng)
     pairs, frames = np.concatenate(got_p), np.concatenate(got_f)
+    print("pipelined per call (%s, %s): %s" % (name, via.name, piped))
     assert _same(pairs, frames, want_p, want_f), (_diff(pairs, frames, want_p, want_f), piped)
     assert sum(1 for x in piped if x) >= want_piped, piped
     if name == "plays_long":
@@ -142,7 +152,12 @@ def test_emu_pipelined_calls_equal_one_call(name, emu, oracle_lib):
     assert piped[0] == 0 and piped[-1] == 0, piped          # a cold start and the call with the end of the file never are
 
 
-def test_emu_pipelined_calls_feed_the_visualiser(emu, oracle_lib):
+@pytest.mark.parametrize("name", list(PIPE_CASES))
+def test_emu_pipelined_calls_equal_one_call(name, emu, oracle_lib):
+    _pipelined_calls_equal_one_call(name, emu, dc.HOST)
+
+
+def _pipelined_calls_feed_the_visualiser(emu, via):
     """The data blocks and the assembled lines of pipelined calls (their turns are run once more from the final hand-overs; the first
     round of such a call never went through the host's per-turn arrays) equal those of the sequential run."""
     recs = _pipelined_tape(n=14)
@@ -156,23 +171,27 @@ def test_emu_pipelined_calls_feed_the_visualiser(emu, oracle_lib):
     emu.sdv_stitch_line_count.restype = C.c_size_t
     emu.sdv_stitch_line_count.argtypes = [C.c_void_p]
     eng = emu.sdv_engine_create(0)
-    bbuf = np.zeros(len(want_blocks) + 8, dtype=sa.BLOCK_DTYPE)
-    lbuf = np.zeros(len(want_lines) + 8, dtype=sa.ASM_DTYPE)
-    assert emu.sdv_set_stitch_block_output(eng, bbuf.ctypes.data, len(bbuf)) == 0
-    assert emu.sdv_set_stitch_line_output(eng, lbuf.ctypes.data, len(lbuf)) == 0
+    bbuf = via.zeros(len(want_blocks) + 8, sa.BLOCK_DTYPE)
+    lbuf = via.zeros(len(want_lines) + 8, sa.ASM_DTYPE)
+    assert emu.sdv_set_stitch_block_output(eng, via.ptr(bbuf), len(bbuf)) == 0
+    assert emu.sdv_set_stitch_line_output(eng, via.ptr(lbuf), len(lbuf)) == 0
     cuts = _frame_cuts(recs, [3] * 5)
     blocks, lines, piped = [], [], []
     info = ea.StitchInfo()
     for a, b in zip(cuts[:-1], cuts[1:]):
-        rc, _, _ = ea.emu_stitch(emu, eng, recs[a:b], st if a == 0 else None, pair_cap=30000, frame_cap=64)
+        rc, _, _ = via.stitch(emu, eng, recs[a:b], st if a == 0 else None, pair_cap=30000, frame_cap=64)
         assert rc == 0
-        blocks.append(bbuf[:emu.sdv_stitch_block_count(eng)].copy()); lines.append(lbuf[:emu.sdv_stitch_line_count(eng)].copy())
+        blocks.append(via.get(bbuf, emu.sdv_stitch_block_count(eng))); lines.append(via.get(lbuf, emu.sdv_stitch_line_count(eng)))
         assert emu.sdv_get_stitch_info(eng, C.byref(info)) == 0
         piped.append(int(info.pipelined))
     emu.sdv_engine_destroy(eng)
     assert sum(1 for x in piped if x) >= 2, piped
     assert np.concatenate(blocks).tobytes() == want_blocks.tobytes()
     assert np.concatenate(lines).tobytes() == want_lines.tobytes()
+
+
+def test_emu_pipelined_calls_feed_the_visualiser(emu, oracle_lib):
+    _pipelined_calls_feed_the_visualiser(emu, dc.HOST)
 
 
 def test_emu_pipelined_call_reports_what_the_host_would_have_refused(emu, oracle_lib):
@@ -192,28 +211,32 @@ def test_emu_pipelined_call_reports_what_the_host_would_have_refused(emu, oracle
     emu.sdv_engine_destroy(eng)
 
 
-def test_emu_empty_and_tiny_inputs(emu, oracle_lib):
+def _empty_and_tiny_inputs(emu, via):
     """Nothing in, nothing out; a single frame has no successor yet and produces nothing until the next one arrives; a stream that
     is only the end-of-file frame produces nothing at all."""
     recs, st = sc.make_input("ntsc_clean", lambda luma: oracle_binarize(luma, mode=2))
     want_p, want_f = sa.run_cpu(libs.load_oracle(), "orc_", recs, st)
     eng = emu.sdv_engine_create(0)
-    rc, p, f = ea.emu_stitch(emu, eng, recs[:0], st, pair_cap=16, frame_cap=4)
+    rc, p, f = via.stitch(emu, eng, recs[:0], st, pair_cap=16, frame_cap=4)
     assert rc == 0 and len(p) == 0 and len(f) == 0
     one = 1 + 489                                   # NEW_FILE + the first frame
-    rc, p, f = ea.emu_stitch(emu, eng, recs[:one], None, pair_cap=16, frame_cap=4)
+    rc, p, f = via.stitch(emu, eng, recs[:one], None, pair_cap=16, frame_cap=4)
     assert rc == 0 and len(p) == 0 and len(f) == 0
-    rc, p, f = ea.emu_stitch(emu, eng, recs[one:], None)
+    rc, p, f = via.stitch(emu, eng, recs[one:], None)
     assert rc == 0 and _same(p, f, want_p, want_f), _diff(p, f, want_p, want_f)
     emu.sdv_engine_destroy(eng)
     eng = emu.sdv_engine_create(0)
     tail = recs[-(486 + 4):]                        # filler frame + END_FILE only
-    rc, p, f = ea.emu_stitch(emu, eng, tail, st, pair_cap=16, frame_cap=4)
+    rc, p, f = via.stitch(emu, eng, tail, st, pair_cap=16, frame_cap=4)
     assert rc == 0 and len(p) == 0 and len(f) == 0
     emu.sdv_engine_destroy(eng)
 
 
-def test_emu_rejects_what_it_cannot_reproduce(emu, oracle_lib):
+def test_emu_empty_and_tiny_inputs(emu, oracle_lib):
+    _empty_and_tiny_inputs(emu, dc.HOST)
+
+
+def _rejects_what_it_cannot_reproduce(emu, via):
     """A line numbered for a later frame in the middle of a frame: the real stitcher pops its queue up to that line and never gets past it
     (more frame reports than the stream has frames until the driver's buffers are full).  The product refuses the stream."""
     recs, st = sc.make_input("ntsc_clean", lambda luma: oracle_binarize(luma, mode=2))
@@ -228,13 +251,17 @@ def test_emu_rejects_what_it_cannot_reproduce(emu, oracle_lib):
         assert f(bad.ctypes.data, len(bad), C.byref(st), pairs.ctypes.data, len(pairs), frames.ctypes.data, len(frames), C.byref(nf)) == -1
         assert nf.value > int((bad["service_type"] == 5).sum()) + 2
     eng = emu.sdv_engine_create(0)
-    rc, _, _ = ea.emu_stitch(emu, eng, bad, st)
+    rc, _, _ = via.stitch(emu, eng, bad, st)
     assert rc == -4 and b"frame" in emu.sdv_last_error(eng)      # SDV_ERR_UNSUPPORTED, loudly
     emu.sdv_engine_destroy(eng)
     eng = emu.sdv_engine_create(0)
-    rc, _, _ = ea.emu_stitch(emu, eng, recs, st, pair_cap=100)
+    rc, _, _ = via.stitch(emu, eng, recs, st, pair_cap=100)
     assert rc == -1                                             # output buffer too small
     emu.sdv_engine_destroy(eng)
+
+
+def test_emu_rejects_what_it_cannot_reproduce(emu, oracle_lib):
+    _rejects_what_it_cannot_reproduce(emu, dc.HOST)
 
 
 # ---------------------------------------------------------------------------------------------------------- GPU
@@ -435,3 +462,35 @@ def test_gpu_random_cuts_and_two_files(seed):
     pairs, frames = np.concatenate(got_p), np.concatenate(got_f)
     want_p, want_f = np.concatenate(want_p), np.concatenate(want_f)
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
+
+
+# ---- the GPU twins of the emulator's stream tests: the same bodies through tests/device_calls.py ------------------------------------------------
+@pytest.mark.gpu
+def test_gpu_streaming_calls_equal_one_call(gpu, oracle_lib):
+    _streaming_calls_equal_one_call(gpu, dc.DEVICE)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(PIPE_CASES))
+def test_gpu_pipelined_calls_equal_one_call(name, gpu, oracle_lib):
+    """The kernels of "1p" run from the control words the device wrote, at the estimated launch width, with the next call's state copied ahead of the
+    read-back: the same tapes, cuts, oracle bytes and `pipelined` values as on the emulator (host decisions on the same data)."""
+    _pipelined_calls_equal_one_call(name, gpu, dc.DEVICE)
+
+
+@pytest.mark.gpu
+def test_gpu_pipelined_calls_feed_the_visualiser(gpu, oracle_lib):
+    _pipelined_calls_feed_the_visualiser(gpu, dc.DEVICE)
+
+
+@pytest.mark.gpu
+def test_gpu_empty_and_tiny_inputs(gpu, oracle_lib):
+    _empty_and_tiny_inputs(gpu, dc.DEVICE)
+
+
+@pytest.mark.gpu
+def test_gpu_rejects_what_it_cannot_reproduce(gpu, oracle_lib):
+    """Both refusals come before anything is written to the caller's buffers: on a cold engine the call is not pipelined, the stranger is found in the
+    analysis' briefs read back ahead of the first turn (stitch_engine.inc:510-515), and the small buffer at the host's sum of the turns' counts ahead of
+    the packing kernel (stitch_engine.inc:680; no direct writes without a steady stream, :548)."""
+    _rejects_what_it_cannot_reproduce(gpu, dc.DEVICE)
