@@ -19,6 +19,10 @@
  *       an STC-007 tape recorded with emphasis, whose pairs never carry the flag `auto` goes by; the reference leaves this to an audio editor.
  *       With `44100` the file's pairs - an NTSC tape runs at 44 056 Hz - are resampled to 44 100 Hz (sdv_audio_resample, flush = 1) behind the
  *       de-emphasis, and the header says 44 100 Hz
+ *   decode_tape ingest <video.raw> <pixfmt> <src_w> <src_h> <src_row_stride> <n_frames> <l,r,t,b> <bw|r|g|b> <off|on|auto> <luma.out>
+ *       captured frames as the video decoder delivers them (pixfmt: gray8 uyvy422 yuyv422 v210 gray10le rgb24 bgr24 rgb0 bgr0; rows
+ *       src_row_stride bytes apart, frames src_h rows apart) -> sdv_ingest_frames: crop, channel, 8-bit luma, 2x doubling -> the plane the
+ *       other modes read (and, on the device, the plane the frame entries take); prints `out_w out_h doubled`
  *
  * Build (host code only, any C++ compiler): g++ -std=c++17 -O2 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude examples/decode_tape.cpp
  *        -Lsdvpcmdecoder_amd -lsdvpcm_hip -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$ORIGIN/../sdvpcmdecoder_amd' (build.py: build_example).
@@ -201,6 +205,36 @@ int main(int argc, char **argv)
         sdv_run_info info; sdv_get_run_info(eng, &info);
         printf("pcm16x0 (%s): %d frames -> %zu sub-line records -> %zu sample pairs, %zu frame descriptors (binarize rounds %u)\n", ei ? "EI" : "SI", n, n_lines, n_pairs, n_frames, info.rounds);
         (void)hipFree(d_luma); (void)hipFree(d_lines); (void)hipFree(d_stats); (void)hipFree(d_frames);
+    } else if (mode == "ingest" && argc == 12) {
+        static const char *const fmts[] = { "gray8", "uyvy422", "yuyv422", "v210", "gray10le", "rgb24", "bgr24", "rgb0", "bgr0" };
+        static const char *const cols[] = { "bw", "r", "g", "b" }, *const dbls[] = { "off", "on", "auto" };
+        sdv_ingest_desc d; memset(&d, 0, sizeof(d));
+        int fmt = -1, col = -1, dbl = -1, crop[4] = { -1, -1, -1, -1 };
+        for (int i = 0; i < 9; i++) if (fmts[i] == std::string(argv[3])) fmt = i;
+        for (int i = 0; i < 4; i++) if (cols[i] == std::string(argv[9])) col = i;
+        for (int i = 0; i < 3; i++) if (dbls[i] == std::string(argv[10])) dbl = i;
+        const int n_crop = sscanf(argv[8], "%d,%d,%d,%d", &crop[0], &crop[1], &crop[2], &crop[3]);
+        const long stride = atol(argv[6]); const int n = atoi(argv[7]);
+        if (fmt < 0 || col < 0 || dbl < 0 || n_crop != 4 || crop[0] < 0 || crop[1] < 0 || crop[2] < 0 || crop[3] < 0 || crop[0] > 65535 || crop[1] > 65535 ||
+            crop[2] > 65535 || crop[3] > 65535 || stride <= 0 || n <= 0) { fprintf(stderr, "usage: see the header of examples/decode_tape.cpp\n"); return 1; }
+        d.pix_fmt = (uint8_t)fmt; d.colors = (uint8_t)col; d.double_width = (uint8_t)dbl;
+        d.crop_left = (uint16_t)crop[0]; d.crop_right = (uint16_t)crop[1]; d.crop_top = (uint16_t)crop[2]; d.crop_bottom = (uint16_t)crop[3];
+        d.src_width = atoi(argv[4]); d.src_height = atoi(argv[5]);
+        int out_w = 0, out_h = 0, doubled = 0; size_t row_bytes = 0;
+        const int grc = sdv_ingest_geometry(&d, &out_w, &out_h, &doubled, &row_bytes);
+        if (grc != SDV_OK) { fprintf(stderr, "sdv_ingest_geometry = %d: %s\n", grc, sdv_last_error(NULL)); return 3; }
+        const size_t frame_bytes = (size_t)stride * (size_t)d.src_height;
+        if (!read_file(argv[2], in) || in.size() != frame_bytes * (size_t)n) { fprintf(stderr, "cannot read %s\n", argv[2]); return 1; }
+        uint8_t *d_video = NULL, *d_luma = NULL;
+        const size_t luma_bytes = (size_t)out_w * out_h * n;
+        HIP_OK(hipMalloc((void **)&d_video, in.size()));
+        HIP_OK(hipMalloc((void **)&d_luma, luma_bytes));
+        HIP_OK(hipMemcpy(d_video, in.data(), in.size(), hipMemcpyHostToDevice));
+        SDV_OKAY(sdv_ingest_frames(eng, &d, d_video, (size_t)stride, frame_bytes, n, d_luma, (size_t)out_w, (size_t)out_w * out_h, NULL));
+        HIP_OK(hipDeviceSynchronize());
+        rc = download(d_luma, luma_bytes, argv[11]);
+        printf("%d %d %d\n", out_w, out_h, doubled);
+        (void)hipFree(d_video); (void)hipFree(d_luma);
     } else { fprintf(stderr, "usage: see the header of examples/decode_tape.cpp\n"); rc = 1; }
     if (d_pairs) (void)hipFree(d_pairs);
     sdv_engine_destroy(eng);

@@ -20,12 +20,13 @@
 extern "C" {
 #endif
 
-#define SDV_ABI_VERSION 7   /* 2: output capacities on sdv_binarize_frames / sdv_pcm1_binarize_lines; 3: sdv_audio_process, sdv_wav_pack, sdv_wav_header, sdv_decode_frames (additions only);
+#define SDV_ABI_VERSION 8   /* 2: output capacities on sdv_binarize_frames / sdv_pcm1_binarize_lines; 3: sdv_audio_process, sdv_wav_pack, sdv_wav_header, sdv_decode_frames (additions only);
                              * 4: sdv_pcm16x0_binarize_lines, sdv_audio_stalled, sdv_set_frame_flags, sdv_double_width, sdv_vis_render_lines (additions); the calls that used to refuse PCM-16x0 frames of the wrong size and the
                              * AudioProcessor's dead ends now follow the reference; the PCM-16x0 stitch state blob grew by conv_queue's remainder;
                              * 5: sdv_run_info grew by frames_met (at its end), sdv_binarize_lines (addition);
                              * 6: sdv_deemphasis_coeffs, sdv_set_deemphasis, sdv_reset_deemphasis, sdv_audio_deemphasis (additions only);
-                             * 7: sdv_resample_taps, sdv_set_resample, sdv_reset_resample, sdv_audio_resample_pending, sdv_audio_resample_room, sdv_audio_resample (additions only) */
+                             * 7: sdv_resample_taps, sdv_set_resample, sdv_reset_resample, sdv_audio_resample_pending, sdv_audio_resample_room, sdv_audio_resample (additions only);
+                             * 8: sdv_ingest_geometry, sdv_ingest_frames (additions only) */
 
 /* ---- status codes ---------------------------------------------------------------------------
  * 0..4 mirror Binarizer::LB_RET_* (binarizer.h:268-275); 16.. mirror STC007Deinterleaver::DI_RET_*
@@ -310,6 +311,63 @@ int sdv_set_frame_flags(sdv_engine *e, const uint8_t *flags, size_t n);
  * Device pointers; asynchronous on `stream`; src and dst must not overlap. */
 int sdv_needs_double_width(int width);
 int sdv_double_width(sdv_engine *e, const uint8_t *src, size_t src_row_stride, int width, size_t rows, uint8_t *dst, size_t dst_row_stride, void *stream);
+
+/* ---- ingest: captured video -> the luma plane of the frame entries, on the device -------------------------------------
+ * What FFMPEGWrapper does between the video decoder and the Binarizer (vid_preset_t.h:30-45: `colors` and the four crops;
+ * ffmpegwrapper.cpp:847-869 cropping, :199-251 the target plane, :254-300 doubling, :924-985 sws_scale and one plane handed on), for the packed
+ * formats capture cards, intermediate codecs and screen grabbers deliver.  The crop, plane and doubling RULES are the reference's; the sample
+ * VALUES are the integer formulas below, not libswscale's pixels (SWS_GAUSS is outside the rebuilt path, as for sdv_double_width).
+ *
+ * Sample of source pixel (x, y); `row` is the start of source row y; every result is 8 bit:
+ *   SDV_PIX_GRAY8      row[x].  Also the Y plane of any planar or semi-planar 8-bit YUV frame (YUV420P, YUV422P, NV12): the reference's
+ *                      BUF_FMT_BW plane itself.
+ *   SDV_PIX_UYVY422    row[2 x + 1]
+ *   SDV_PIX_YUYV422    row[2 x]
+ *   SDV_PIX_V210       group g = x / 6, j = x % 6; the group is four little-endian 32-bit words at row + 16 g, each holding three 10-bit
+ *                      components at bits 0-9, 10-19 and 20-29, numbered c = 0..11 across the four words; luma j is component c = 2 j + 1,
+ *                      that is word c / 3 shifted right by 10 (c % 3) and masked with 0x3FF; sample = that value >> 2.
+ *   SDV_PIX_GRAY10LE   little-endian 16-bit word x of the row, & 0x3FF, >> 2.  The Y plane of YUV422P10LE / YUV420P10LE.
+ *   SDV_PIX_RGB24, SDV_PIX_BGR24   3 bytes per pixel in that order;  SDV_PIX_RGB0, SDV_PIX_BGR0   4 bytes per pixel, the fourth ignored
+ *                      (these also serve RGBA and BGRA).  SDV_COLOR_R / _G / _B: that byte.  SDV_COLOR_BW: (77 r + 150 g + 29 b + 128) >> 8;
+ *                      the weights sum to 256, so grey pixels pass unchanged.  This is BT.601 luma at full range, not libswscale's arithmetic.
+ * A colour other than SDV_COLOR_BW with a GRAY or YUV format: SDV_ERR_UNSUPPORTED.  The reference would have swscale convert YUV to GBR planes
+ * there; PCM video carries no chroma to select from.
+ *
+ * Bytes of a source row (*src_row_bytes), w = src_width: GRAY8 w; UYVY422 / YUYV422 4 ceil(w / 2) (whole 4-byte pixel pairs); V210 16 ceil(w / 6); GRAY10LE 2 w;
+ * RGB24 / BGR24 3 w; RGB0 / BGR0 4 w.  (Files of v210 pad rows to 128 bytes: that is the caller's src_row_stride.)  Nothing behind these bytes of
+ * a row is read.  src_row_stride must be at least this value, and src_frame_stride at least (src_height - 1) src_row_stride + src_row_bytes when
+ * n_frames > 1, else SDV_ERR_BAD_ARG.  src_width and src_height: 1..32768.
+ *
+ * Crop (in source pixels / rows): when src_height > 640 (LINES_PER_FRAME_MAX) the effective crop_bottom is src_height - 640 whatever was given
+ * (ffmpegwrapper.cpp:850-854), otherwise the given value.  Kept columns crop_left .. src_width - crop_right - 1, kept rows crop_top ..
+ * src_height - crop_bottom_eff - 1.  An empty result: SDV_ERR_BAD_ARG.
+ *
+ * Doubling: SDV_INGEST_DOUBLE_AUTO means sdv_needs_double_width(cropped width) (keepFrameInCheck, ffmpegwrapper.cpp:279-285: the reference
+ * decides after cropping).  When doubled, dst[r][2 x] = dst[r][2 x + 1] = sample, the rule of sdv_double_width; *doubled tells the caller to pass
+ * SDV_FLAG_DOUBLED on.  out_width is the cropped width, or twice that; out_height the kept rows.
+ *
+ * Destination: row r of frame f goes to dst + f dst_frame_stride + r dst_row_stride, out_width bytes.  Bytes of a row behind out_width, and
+ * anything else in the buffer, are not written.  dst_row_stride >= out_width; dst_frame_stride >= (out_height - 1) dst_row_stride + out_width
+ * when n_frames > 1.
+ *
+ * sdv_ingest_frames: device pointers of any alignment; all work goes to `stream`, the call is asynchronous and reads nothing back; it runs on
+ * the engine's device whatever device is current.  Refused before any launch, the engine untouched, sdv_last_error says why: a null d
+ * (SDV_ERR_BAD_ARG), src (SDV_ERR_NULL_VIDEO) or dst (SDV_ERR_NULL_PCM) with n_frames > 0; an unknown enum value, n_frames < 0, the size and
+ * stride rules above, strides above 4 GiB, any overlap of the source span (all rows of all frames) with the destination span (SDV_ERR_BAD_ARG).
+ * n_frames == 0: SDV_OK, nothing done.  sdv_ingest_geometry is host-only and needs no engine: the same codes for the same descriptor
+ * (sdv_last_error(NULL) says why); any of its output pointers may be NULL. */
+enum { SDV_PIX_GRAY8 = 0, SDV_PIX_UYVY422 = 1, SDV_PIX_YUYV422 = 2, SDV_PIX_V210 = 3, SDV_PIX_GRAY10LE = 4,
+       SDV_PIX_RGB24 = 5, SDV_PIX_BGR24 = 6, SDV_PIX_RGB0 = 7, SDV_PIX_BGR0 = 8 };
+enum { SDV_COLOR_BW = 0, SDV_COLOR_R = 1, SDV_COLOR_G = 2, SDV_COLOR_B = 3 };      /* vid_preset_t::COLOR_* */
+enum { SDV_INGEST_DOUBLE_OFF = 0, SDV_INGEST_DOUBLE_ON = 1, SDV_INGEST_DOUBLE_AUTO = 2 };
+typedef struct sdv_ingest_desc {
+    uint8_t pix_fmt, colors, double_width, _pad;
+    uint16_t crop_left, crop_right, crop_top, crop_bottom;      /* vid_preset_t, in source pixels / rows */
+    int32_t src_width, src_height;
+} sdv_ingest_desc;                                               /* 20 bytes */
+int sdv_ingest_geometry(const sdv_ingest_desc *d, int *out_width, int *out_height, int *doubled, size_t *src_row_bytes);
+int sdv_ingest_frames(sdv_engine *e, const sdv_ingest_desc *d, const void *src, size_t src_row_stride, size_t src_frame_stride,
+                      int n_frames, uint8_t *dst, size_t dst_row_stride, size_t dst_frame_stride, void *stream);
 
 size_t sdv_records_per_frame(int height);
 /* records one sdv_binarize_frames call emits: n_frames * (height + 3), + 1 with SDV_FLAG_NEW_FILE, + height + 4 with SDV_FLAG_END_FILE */

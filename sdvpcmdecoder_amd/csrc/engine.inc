@@ -28,6 +28,8 @@
 #include <utility>
 #include <vector>
 
+#include "ingest_device.h"          /* sdv_k_ingest (sdv_ingest_frames, ingest_engine.inc) */
+
 /* Developer aids (scheduler traces, cycle stamps, launch-shape overrides) are read from the environment only in builds made with
  * -DSDV_DEV_AIDS (build.py: SDVPCM_DEV_AIDS=1, and the test-only emulator build); the product library does not look at the environment. */
 #ifdef SDV_DEV_AIDS
@@ -1276,3 +1278,5 @@ int sdv_deinterleave_blocks(sdv_engine *e, const sdv_deint_line *lines, size_t n
 }
 
 } /* extern "C" */
+
+#include "ingest_engine.inc"         /* sdv_ingest_geometry, sdv_ingest_frames */

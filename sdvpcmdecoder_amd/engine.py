@@ -37,6 +37,11 @@ FLAG_NEW_FILE, FLAG_DOUBLED, FLAG_END_FILE = 1, 2, 4
 DEEMPH_OFF, DEEMPH_AUTO, DEEMPH_FORCE = 0, 1, 2       # sdv_set_deemphasis
 RESAMPLE_OFF, RESAMPLE_TO_44100 = 0, 1                # sdv_set_resample
 FRAME_EMPTY = 1                 # sdv_set_frame_flags: SDV_FRAME_EMPTY
+PIX_GRAY8, PIX_UYVY422, PIX_YUYV422, PIX_V210, PIX_GRAY10LE, PIX_RGB24, PIX_BGR24, PIX_RGB0, PIX_BGR0 = range(9)      # SDV_PIX_*
+PIX_FORMATS = {"gray8": PIX_GRAY8, "uyvy422": PIX_UYVY422, "yuyv422": PIX_YUYV422, "v210": PIX_V210, "gray10le": PIX_GRAY10LE,
+               "rgb24": PIX_RGB24, "bgr24": PIX_BGR24, "rgb0": PIX_RGB0, "bgr0": PIX_BGR0}
+COLOR_BW, COLOR_R, COLOR_G, COLOR_B = 0, 1, 2, 3       # SDV_COLOR_* (vid_preset_t::COLOR_*)
+INGEST_DOUBLE_OFF, INGEST_DOUBLE_ON, INGEST_DOUBLE_AUTO = 0, 1, 2
 VIS_STC007_LINES, VIS_PCM1_LINES, VIS_PCM16X0_LINES, VIS_STC007_BLOCKS_NTSC, VIS_STC007_BLOCKS_PAL, VIS_STC007_ASM_NTSC, VIS_STC007_ASM_PAL = 0, 1, 2, 3, 4, 5, 6   # SDV_VIS_*
 
 
@@ -47,6 +52,16 @@ class BinPreset(C.Structure):
                                           "right_bit_pick", "en_force_coords", "en_coord_search",
                                           "en_first_line_dup", "en_good_no_marker", "_pad")] + \
                [("horiz_start", C.c_int16), ("horiz_stop", C.c_int16)]
+
+
+class IngestDesc(C.Structure):
+    """sdv_ingest_desc"""
+    _fields_ = [("pix_fmt", C.c_uint8), ("colors", C.c_uint8), ("double_width", C.c_uint8), ("_pad", C.c_uint8),
+                ("crop_left", C.c_uint16), ("crop_right", C.c_uint16), ("crop_top", C.c_uint16), ("crop_bottom", C.c_uint16),
+                ("src_width", C.c_int32), ("src_height", C.c_int32)]
+
+
+assert C.sizeof(IngestDesc) == 20
 
 
 class DeintSettings(C.Structure):
@@ -133,6 +148,8 @@ def load_library(path: str | None = None):
     lib.sdv_set_frame_flags.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.sdv_needs_double_width.argtypes = [C.c_int]
     lib.sdv_double_width.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.sdv_ingest_geometry.argtypes = [C.POINTER(IngestDesc), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
+    lib.sdv_ingest_frames.argtypes = [C.c_void_p, C.POINTER(IngestDesc), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
     lib.sdv_vis_canvas_size.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.sdv_vis_reset.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.sdv_vis_render_lines.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
@@ -336,6 +353,39 @@ class Engine:
         sptr = C.c_void_p(stream.cuda_stream) if stream is not None else C.c_void_p(torch.cuda.current_stream(luma.device).cuda_stream)
         self._check(self.lib.sdv_double_width(self._h, C.c_void_p(luma.data_ptr()), w, w, rows, C.c_void_p(out.data_ptr()), 2 * w, sptr))
         return out
+
+    def ingest_geometry(self, desc: IngestDesc):
+        """sdv_ingest_geometry: (out_width, out_height, doubled, src_row_bytes) of a descriptor; host only."""
+        ow, oh, dbl, rb = C.c_int(0), C.c_int(0), C.c_int(0), C.c_size_t(0)
+        rc = self.lib.sdv_ingest_geometry(C.byref(desc), C.byref(ow), C.byref(oh), C.byref(dbl), C.byref(rb))
+        if rc != 0:
+            raise RuntimeError(f"sdvpcm error {rc}: " + self.lib.sdv_last_error(None).decode())
+        return ow.value, oh.value, bool(dbl.value), rb.value
+
+    def ingest(self, src, pix_fmt, src_width: int, src_height: int, crop=(0, 0, 0, 0), colors: int = COLOR_BW, double="auto", stream=None):
+        """sdv_ingest_frames: captured frames in a packed format -> (luma (n, out_height, out_width) uint8 CUDA tensor, doubled).
+        src: uint8 CUDA tensor (n, src_height, row stride in bytes) or (src_height, row stride) whose last dimension is the row in bytes;
+        pix_fmt: a PIX_* value or its name; crop: (left, right, top, bottom) in source pixels / rows; double: "off", "on", "auto" or an
+        INGEST_DOUBLE_* value.  Pass `doubled` on to the frame entries."""
+        import torch
+        if not (src.is_cuda and src.dtype == torch.uint8 and src.dim() in (2, 3) and src.stride(-1) == 1):
+            raise ValueError("src must be a torch.uint8 CUDA tensor (frames, rows, row bytes) or (rows, row bytes) with contiguous rows")
+        if src.dim() == 2:
+            src = src.unsqueeze(0)
+        if src.shape[1] != src_height:
+            raise ValueError(f"src has {src.shape[1]} rows, src_height is {src_height}")
+        fmt = PIX_FORMATS[pix_fmt] if isinstance(pix_fmt, str) else int(pix_fmt)
+        dbl = {"off": INGEST_DOUBLE_OFF, "on": INGEST_DOUBLE_ON, "auto": INGEST_DOUBLE_AUTO}[double] if isinstance(double, str) else int(double)
+        desc = IngestDesc(fmt, colors, dbl, 0, crop[0], crop[1], crop[2], crop[3], src_width, src_height)
+        ow, oh, doubled, rb = self.ingest_geometry(desc)
+        if src.shape[2] < rb:
+            raise ValueError(f"rows of {src.shape[2]} bytes; {src_width} pixels of this format take {rb}")
+        n = src.shape[0]
+        out = torch.empty((n, oh, ow), dtype=torch.uint8, device=src.device)
+        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else C.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
+        self._check(self.lib.sdv_ingest_frames(self._h, C.byref(desc), C.c_void_p(src.data_ptr()), src.stride(1), src.stride(0) if n > 1 else 0, n,
+                                               C.c_void_p(out.data_ptr()), ow, oh * ow, sptr))
+        return out, doubled
 
     # ---- visualiser feed (RenderPCM's canvas of binarized lines) ----
     def vis_canvas_size(self, kind: int):
