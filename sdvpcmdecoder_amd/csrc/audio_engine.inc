@@ -587,26 +587,27 @@ int sdv_decode_frames(sdv_engine *e, int pcm_type, const uint8_t *luma, size_t r
          * records. */
         const sdv_v2d_state chain_before = e->chain; const bool worn_before = e->worn_tape;
         const bool flags_pending = e->frame_flags_pending;
+        FusedHooks hooks;           /* for the first of the frame calls below */
+        memset(&hooks, 0, sizeof(hooks));
         if (plain_frames && !flags_pending) {
-            void *df = NULL; sdv::DirectFrame *dd = NULL; int dofs = 0;
-            rc = stitch_prepare_direct(e, (size_t)n_frames, reg.recs_per_frame, raw_cap, frames_cap, &df, &dd, &dofs);
+            rc = stitch_prepare_direct(e, (size_t)n_frames, reg.recs_per_frame, raw_cap, frames_cap, &hooks.direct_fields, &hooks.direct_frames, &hooks.direct_seg_ofs);
             if (rc != SDV_OK) return rc;
-            e->direct_fields = df; e->direct_frames = dd; e->direct_seg_ofs = dofs; e->direct_pitch = (int)sdvs::FIELD_PITCH; e->direct_lines = (int)sdvs::BUF_FIELD;
+            hooks.direct_pitch = (int)sdvs::FIELD_PITCH; hooks.direct_lines = (int)sdvs::BUF_FIELD;
         }
         /* ... and the stitch stage's kernels are queued right behind the frame kernel's first round, ahead of the host's look at that round (a tape that plays
          * settles in it: the last call did).  Should the round not have been the last, the stitch call is made over. */
         struct Ahead { sdv_engine *e; const sdv_line_rec *recs; size_t n_recs; sdv_sample_pair *raw; size_t raw_cap; sdv_frame_asm *frames; size_t frames_cap; void *stream;
                        const StitchRegular *reg; int rc; } ahead = { e, recs, n_recs, raw, raw_cap, (sdv_frame_asm *)out_frames, frames_cap, stream, &reg, SDV_STITCH_NOT_QUEUED };
-        const bool may_queue_ahead = e->direct_fields != NULL && e->binarize_settled_at_once && !e->profiling && !dev_env("SDV_NO_QUEUE_AHEAD");
+        const bool may_queue_ahead = hooks.direct_fields != NULL && e->binarize_settled_at_once && !e->profiling && !dev_env("SDV_NO_QUEUE_AHEAD");
         if (may_queue_ahead) {
-            e->after_ctx = &ahead;
-            e->after_first_round = [](void *ctx) -> int {
+            hooks.after_ctx = &ahead;
+            hooks.after_first_round = [](void *ctx) -> int {
                 Ahead *h = (Ahead *)ctx; size_t np = 0, nf = 0;
                 h->rc = stitch_frames_impl(h->e, h->recs, h->n_recs, h->raw, h->raw_cap, &np, h->frames, h->frames_cap, &nf, h->stream, h->reg, STITCH_QUEUE_AHEAD);
                 return (h->rc == SDV_STITCH_QUEUED_AHEAD || h->rc == SDV_STITCH_NOT_QUEUED || h->rc == SDV_STITCH_RETRY_WITH_RECORDS) ? SDV_OK : h->rc;
             };
         }
-        rc = sdv_binarize_frames(e, luma, row_stride, frame_stride, width, height, n_frames, first_frame_no, flags, recs, n_recs, stats, stats_room, stream);
+        rc = stc007_binarize_frames_impl(e, luma, row_stride, frame_stride, width, height, n_frames, first_frame_no, flags, recs, n_recs, stats, stats_room, stream, &hooks);
         /* (an error behind the point where the stitch stage's work was queued ahead: that work writes the caller's buffers - nothing of it is left in flight
          * when the call returns) */
         if (rc != SDV_OK) { if (e->stitch) e->stitch->direct_armed = false; if (may_queue_ahead) (void)rt::ssync(s); return rc; }

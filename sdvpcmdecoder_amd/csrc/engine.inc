@@ -18,7 +18,8 @@
  * anchors are usually right and the number of rounds does not grow with the number of dropouts.  Frames a lean
  * wave gave up are decoded by the full kernel, all of them in one launch.  The loop ends when the whole chain
  * verifies, so the result is always identical to the sequential reference order; only the amount of parallelism
- * depends on the video.
+ * depends on the video.  (The STC-007 frame entry and its scheduler: stc007_frames_engine.inc, stc007_chain_plan.h; the marker-less formats':
+ * markerless_frames_engine.inc.)
  */
 
 #include <cstdio>
@@ -190,7 +191,7 @@ static inline hipError_t launch_frames(const sdv::FrameArgs &a, stream_t s, bool
     if (lean) hipLaunchKernelGGL(sdv_k_stc007_frames_lean, dim3((unsigned)n), dim3(64), 0, s, a);
     else if (a.fat_levels) hipLaunchKernelGGL(sdv_k_stc007_frames_fat, dim3((unsigned)n), dim3(64 * (1 + sdv::FAT_WORKERS)), 0, s, a);   /* (a small round: the sweeps it misses are settled while it runs) */
     else if (a.tc_hdr) hipLaunchKernelGGL(sdv_k_stc007_frames, dim3((unsigned)n), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL(sdv_k_stc007_frames_plain, dim3((unsigned)n), dim3(64), 0, s, a);       /* (no snapshots in this call: the build without them, engine.inc plain_general) */
+    else hipLaunchKernelGGL(sdv_k_stc007_frames_plain, dim3((unsigned)n), dim3(64), 0, s, a);       /* (no snapshots in this call: the build without them, sdv_engine::plain_general) */
     return hipGetLastError();
 }
 /* the reference-level sweeps a round asked for: the levels (a wave per 64 levels of a line), then chain, vote and pick (a wave per line) */
@@ -407,9 +408,6 @@ struct sdv_engine {
     /* ... and hardly any of their decodes met the frame's last pass (a tape whose damage re-tunes the binarizer for good every few dozen lines): the general
      * kernel's build without the snapshots is a sixth faster there (stc007_device.h, kMeet).  Looked at again with the snapshots every eighth call. */
     bool plain_general = false; unsigned plain_calls = 0;
-    /* set by sdv_decode_frames for the one sdv_binarize_frames call it makes next (taken and cleared there): the stitcher's field buffers, for the frames the
-     * whole-frame capture takes from end to end (FrameArgs::direct_fields) */
-    void *direct_fields = NULL; sdv::DirectFrame *direct_frames = NULL; int direct_seg_ofs = 0, direct_pitch = 0, direct_lines = 0;
     sdv_stitcher *stitch = NULL;
     sdv_pcm1_stitcher *pcm1 = NULL;
     /* PCM-16x0 streams: their chain state is longer (pcm16_frames_device.h, State16) */
@@ -425,9 +423,6 @@ struct sdv_engine {
     bool have_events = false;
     hipEvent_t ev_mark; bool have_mark = false;     /* behind the first round's read-back of sdv_binarize_frames when work of the next stage is queued behind it */
 #endif
-    /* the fused entry (sdv_decode_frames): device work of the stage behind, queued right behind the first round of the next sdv_binarize_frames call - a tape
-     * that plays settles in that round, and the stage behind need not wait for the host to have seen that.  One call only; returns SDV_OK or an error. */
-    int (*after_first_round)(void *ctx) = NULL; void *after_ctx = NULL;
     bool binarize_settled_at_once = false;      /* the last sdv_binarize_frames call of the fused entry needed one round */
 #ifdef SDV_DEV_AIDS
     uint32_t dev_counts[16] = {};            /* developer builds: the launches of the last sdv_binarize_frames / sdv_binarize_lines call, by build (DevCount) */
@@ -627,8 +622,31 @@ static int take_frame_flags(sdv_engine *e, size_t n_frames, rt::stream_t s, cons
     return SDV_OK;
 }
 
+/* What every frame entry refuses ahead of its first launch, in this order: no video, no output, the geometry, a line too short for the format, frames that
+ * overlap, output buffers too small.  The formats differ in the widest line they take, the narrowest (min_width, with short_line as its refusal), the
+ * records a call writes (need_lines) and what they are called (rec_noun). */
+static int check_frame_call(sdv_engine *e, const void *luma, const void *out_lines, const void *out_stats, size_t row_stride, size_t frame_stride, int width, int height,
+                            int n_frames, unsigned flags, size_t lines_cap, size_t stats_cap,
+                            int max_width, int min_width, const char *short_line, size_t need_lines, const char *rec_noun)
+{
+    if (!luma) { set_error(e, "null video"); return SDV_ERR_NULL_VIDEO; }
+    if (!out_lines || !out_stats) { set_error(e, "null output"); return SDV_ERR_NULL_PCM; }
+    if (n_frames <= 0 || height < 2 || height > SDV_MAX_HEIGHT || width <= 0 || width > max_width || row_stride < (size_t)width) {
+        set_error(e, "bad frame geometry"); return SDV_ERR_BAD_ARG;
+    }
+    if (width < min_width) { set_error(e, short_line); return SDV_ERR_SHORT_LINE; }
+    /* frames must not overlap (the kernels prefetch whole rows of their own frame only) */
+    if (n_frames > 1 && frame_stride < (size_t)(height - 1) * row_stride + (size_t)width) { set_error(e, "frame_stride smaller than one frame"); return SDV_ERR_BAD_ARG; }
+    const size_t need_stats = (size_t)n_frames + ((flags & SDV_FLAG_END_FILE) ? 1 : 0);
+    if (lines_cap < need_lines || stats_cap < need_stats) {
+        set_error(e, "output buffers too small: " + std::to_string(need_lines) + " " + rec_noun + " and " + std::to_string(need_stats) + " frame descriptors are needed");
+        return SDV_ERR_BAD_ARG;
+    }
+    return SDV_OK;
+}
+
 /* The block a round's one read-back brings (d_flag / h_flag): a flag byte per frame; at the next multiple of 16 the last frame's outgoing state and, behind it,
- * the count of sweep requests (16 bytes); then a give-up signature per frame (FrameArgs::sig). */
+ * the count of sweep requests and the count of passes that met the frame's last one (16 bytes); then a give-up signature per frame (FrameArgs::sig). */
 static inline size_t flag_tail_ofs(size_t n_frames) { return (n_frames + 15) & ~(size_t)15; }
 enum : size_t { FLAG_TAIL_BYTES = sizeof(sdv_v2d_state) + 16, FLAG_SIG_OFS = (FLAG_TAIL_BYTES + 15) & ~(size_t)15 };
 static inline size_t flag_block_bytes(size_t n_frames) { return flag_tail_ofs(n_frames) + FLAG_SIG_OFS + n_frames + 16; }
@@ -651,7 +669,7 @@ static int ensure_capacity(sdv_engine *e, size_t n_frames, size_t height)
 
 /* The pool of reference-level sweeps (requests / outcomes), its list heads (a list per line: a lookup meets the entries of its own line only), the
  * per-level records of a chunk of sweeps and the black / white memo: sized for a tape with damage in every frame (the pool grows in the call should a
- * tape ask for more, sdv_binarize_frames).  Made when a call first sends a frame to the full kernel - a stream that plays never asks for them
+ * tape ask for more, Stc007FrameCall::settle_sweeps in stc007_frames_engine.inc).  Made when a call first sends a frame to the full kernel - a stream that plays never asks for them
  * (12 bytes per video line: about 59 MB for 10 000 NTSC frames). */
 static int ensure_memo_capacity(sdv_engine *e, size_t n_frames, size_t height, bool with_snapshots = true)
 {
@@ -684,514 +702,6 @@ static int settle_sweep_chunks(sdv_engine *e, sdv::SweepArgs sa, int lo, int hi,
     }
     return SDV_OK;
 }
-
-int sdv_binarize_frames(sdv_engine *e, const uint8_t *luma, size_t row_stride, size_t frame_stride, int width, int height,
-                        int n_frames, uint32_t first_frame_no, unsigned flags, sdv_line_rec *out_lines, size_t lines_cap,
-                        sdv_frame_stats *out_stats, size_t stats_cap, void *stream)
-{
-    if (!e) return SDV_ERR_BAD_ARG;
-    FrameFlagsConsumed flags_consumed(e);
-    void *const direct_fields = e->direct_fields; sdv::DirectFrame *const direct_frames = e->direct_frames;
-    const int direct_seg_ofs = e->direct_seg_ofs, direct_pitch = e->direct_pitch, direct_lines = e->direct_lines;
-    e->direct_fields = NULL; e->direct_frames = NULL;           /* (for this call only) */
-    int (*const after_first_round)(void *) = e->after_first_round; void *const after_ctx = e->after_ctx;
-    e->after_first_round = NULL; e->after_ctx = NULL;
-    if (!luma) { set_error(e, "null video"); return SDV_ERR_NULL_VIDEO; }
-    if (!out_lines || !out_stats) { set_error(e, "null output"); return SDV_ERR_NULL_PCM; }
-    if (n_frames <= 0 || height < 2 || height > SDV_MAX_HEIGHT || width <= 0 || width > SDV_MAX_WIDTH || row_stride < (size_t)width) {
-        set_error(e, "bad frame geometry"); return SDV_ERR_BAD_ARG;
-    }
-    if (width < sdv::BITS_IN_LINE) { set_error(e, "line shorter than the 137 bit cells of an STC-007 line"); return SDV_ERR_SHORT_LINE; }
-    /* frames must not overlap (the kernels prefetch whole rows of their own frame only) */
-    if (n_frames > 1 && frame_stride < (size_t)(height - 1) * row_stride + (size_t)width) { set_error(e, "frame_stride smaller than one frame"); return SDV_ERR_BAD_ARG; }
-    {
-        const size_t need_lines = sdv_binarize_records(height, n_frames, flags), need_stats = (size_t)n_frames + ((flags & SDV_FLAG_END_FILE) ? 1 : 0);
-        if (lines_cap < need_lines || stats_cap < need_stats) {
-            set_error(e, "output buffers too small: " + std::to_string(need_lines) + " line records and " + std::to_string(need_stats) + " frame descriptors are needed");
-            return SDV_ERR_BAD_ARG;
-        }
-    }
-    rt::stream_t s = (rt::stream_t)stream;
-    SDV_ON_DEVICE(e);
-    const int n_real = n_frames;
-    if (flags & SDV_FLAG_END_FILE) n_frames++;          /* the filler frame is decoded like any other frame of the chain */
-    int rc = ensure_capacity(e, (size_t)n_frames, (size_t)height);
-    if (rc != SDV_OK) return rc;
-
-    sdv::FrameArgs a;
-    memset(&a, 0, sizeof(a));
-    a.luma = luma; a.frame_stride = frame_stride; a.row_stride = row_stride; a.width = width; a.height = height;
-    a.first_frame_no = first_frame_no;
-    a.new_file_frame = (flags & SDV_FLAG_NEW_FILE) ? 0 : -1;
-    a.end_file_frame = (flags & SDV_FLAG_END_FILE) ? n_real : -1;
-    a.doubled = (flags & SDV_FLAG_DOUBLED) ? 1 : 0;
-    a.mode = (uint8_t)e->mode; a.check_line_copy = (uint8_t)e->check_line_dup; a.coordinate_damper = (uint8_t)e->coordinate_damper;
-    a.m2_format = (uint8_t)e->m2_format;
-    a.preset = e->preset;
-    a.states_in = e->d_states_in; a.states_out = e->d_states_out;
-    a.recs = out_lines; a.stats = out_stats; a.scratch = e->d_scratch;
-    a.flag = e->d_flag; a.refs = e->d_refs; a.n_total = n_frames;
-    rc = take_frame_flags(e, (size_t)n_frames, s, &a.frame_flags); if (rc != SDV_OK) return rc;
-    if (direct_fields && direct_frames && !(flags & (SDV_FLAG_NEW_FILE | SDV_FLAG_END_FILE))) {
-        a.direct_fields = direct_fields; a.direct_frames = direct_frames; a.direct_seg_ofs = direct_seg_ofs; a.direct_pitch = direct_pitch; a.direct_lines = direct_lines < direct_pitch ? direct_lines : direct_pitch;
-    }
-
-    memset(&e->info, 0, sizeof(e->info));
-    dev_reset_counts(e);
-    e->info.frames = (uint32_t)n_frames;
-    /* A stream that plays (the chain is tuned, the last call's frames did not need the full kernel): the waves of the first round make the state they start
-     * from themselves, from the one state that is known (FrameArgs::predict_in_kernel) - no copy and no kernel in front of the frame kernel.  The states go to
-     * the device the usual way (copy + sdv_k_predict) when that round was not the last. */
-    const bool chain_cold = e->chain.bin.in_def_reference < e->preset.min_ref_lvl || e->chain.reset_stats;
-    bool states_owed = !chain_cold && !e->worn_tape && !dev_env("SDV_NO_PREDICT_IN_KERNEL");
-    if (!states_owed) RT_CHECK(rt::h2d(e->d_states_in, &e->chain, sizeof(sdv_v2d_state), s));
-
-    const int n = n_frames;
-    sdv::PredictArgs pa; pa.states = e->d_states_in; pa.doubled = a.doubled; pa.min_ref_lvl = e->preset.min_ref_lvl; pa.first_of = NULL; pa.skip = NULL; pa.flag = e->d_flag;
-    /* one scheduling round: the lean kernel over a range or a list, the full kernel over a list, timed together */
-    std::vector<int> list_lean, list_full, anchors, first_of;
-    std::vector<uint32_t> patches;
-    std::vector<uint8_t> in_round((size_t)n_frames, 0);
-    const size_t tail_ofs = flag_tail_ofs((size_t)n);            /* where the last state sits behind the flags */
-    const size_t tail_bytes = FLAG_TAIL_BYTES;                   /* ... and behind it the count of sweep requests */
-    const size_t sig_ofs = tail_ofs + FLAG_SIG_OFS;              /* ... and the give-up signatures (read back with the rest once a frame was given up) */
-    a.sig = e->d_flag + sig_ofs;
-    bool timing_pending = false;
-    /* Reference-level sweeps (stc007_sweep_device.h).  The full kernel does not sweep: a line that needs the outcome of a sweep looks it up, and
-     * where there is none it leaves a request and its frame comes back as given up.  After every round the requests that are new are settled
-     * (all of them at once, a wave per 64 levels of a line) and those frames decoded again, with the outcomes at hand. */
-    bool memo_ready = false; int memo_done = 0;
-    int sweeps_seen = 0;            /* requests of the call as of the last read-back */
-    bool cold_frame = false;        /* the round decodes the first frame of a cold chain: nothing is tuned, its first lines are swept */
-    bool round_fat = false;         /* the last round's general frames ran in the kernel that settles its sweeps itself */
-    /* the count of requests lives behind the flags and the last state for the time of the call: it comes back with every round's one read-back */
-    int32_t *const d_count = reinterpret_cast<int32_t *>(e->d_flag + tail_ofs + sizeof(sdv_v2d_state));
-    auto prepare_memo = [&]() -> int {
-        if (memo_ready) return SDV_OK;
-        { const int mrc = ensure_memo_capacity(e, (size_t)n, (size_t)height); if (mrc != SDV_OK) return mrc; }
-        RT_CHECK(rt::dfill_bytes(e->d_memo_head, 0xFF, (size_t)n * (size_t)height * sizeof(int32_t), s));
-        RT_CHECK(rt::dfill_bytes(d_count, 0, 16, s));
-        RT_CHECK(rt::dfill_bytes(e->d_bw_memo, 0, (size_t)n * (size_t)height * sizeof(unsigned long long), s));
-        a.bw_memo = e->d_bw_memo;
-        const bool plain_now = e->plain_general && (e->plain_calls % 8u) != 7u;
-        if ((size_t)n * 2 * sdv::TC_ENTRIES <= e->d_tc_snaps.cap && !dev_env("SDV_NO_TC") && !plain_now) {
-            RT_CHECK(rt::dfill_bytes(e->d_tc_hdr, 0, (size_t)n * 2 * sizeof(uint32_t), s));        /* no frame has a complete pass yet */
-            a.tc_snaps = e->d_tc_snaps; a.tc_hdr = e->d_tc_hdr; a.tc_keys = e->d_tc_keys;
-        }
-        a.memo = e->d_memo; a.memo_head = e->d_memo_head; a.memo_count = d_count; a.memo_cap = (int32_t)e->d_memo.cap;
-        memo_ready = true; memo_done = 0;
-        return SDV_OK;
-    };
-    /* settle what the last round asked for; count = requests handed out so far (read back with the flags) */
-    auto settle_sweeps = [&](int count) -> int {
-        if (!memo_ready) return SDV_OK;
-        const int cap = (int)e->d_memo.cap, have = count < cap ? count : cap;
-        sweeps_seen = count;
-        if (round_fat) {            /* settled where they were asked for */
-            round_fat = false;
-            if (have > memo_done) { e->info.sweeps += (uint32_t)(have - memo_done); memo_done = have; }
-        }
-        if (have > memo_done) {
-            sdv::SweepArgs sa;
-            memset(&sa, 0, sizeof(sa));
-            sa.luma = a.luma; sa.frame_stride = a.frame_stride; sa.row_stride = a.row_stride; sa.width = a.width;
-            sa.doubled = a.doubled; sa.mode = a.mode; sa.preset = a.preset;
-            { const int src = settle_sweep_chunks(e, sa, memo_done, have, s); if (src != SDV_OK) return src; }
-            e->info.sweeps += (uint32_t)(have - memo_done);
-        }
-        memo_done = have;
-        if (count > cap) {
-            /* the pool ran over: the requests that did not fit were dropped (their frames come again and ask again) - a bigger pool for them */
-            rt::DevBuf<sdv::SweepMemo> bigger;      /* (the one buffer that grows with its contents; an early return frees it) */
-            RT_CHECK(bigger.reserve((size_t)count + (size_t)count / 2 + 4096));
-            RT_CHECK(rt::d2d(bigger, e->d_memo, (size_t)cap * sizeof(sdv::SweepMemo), s));
-#ifndef SDV_EMU
-            RT_CHECK(hipStreamSynchronize(s));
-#endif
-            e->d_memo.swap(bigger);
-            const int32_t c32 = cap;
-            RT_CHECK(rt::h2d(d_count, &c32, sizeof(c32), s));
-#ifndef SDV_EMU
-            RT_CHECK(hipStreamSynchronize(s));      /* (the copy's source is on this stack frame) */
-#endif
-            a.memo = e->d_memo; a.memo_cap = (int32_t)e->d_memo.cap;
-        }
-        return SDV_OK;
-    };
-    /* (the lists of a round go to the device through the page-locked staging e->h_lists: every round ends with a synchronising read-back before the
-     * next lists are made, so the staging is free again by then) */
-    auto run_round = [&](int lo, int hi, bool range_lean, bool range_full) -> int {
-#ifndef SDV_EMU
-        if (e->profiling) {
-            if (!e->have_events) { RT_CHECK(hipEventCreate(&e->ev0)); RT_CHECK(hipEventCreate(&e->ev1)); e->have_events = true; }
-            RT_CHECK(hipEventRecord(e->ev0, s));
-        }
-#endif
-        uint32_t launched = 0, general = 0;
-        if (range_full || (!range_lean && !list_full.empty())) { const int prc = prepare_memo(); if (prc != SDV_OK) return prc; }
-        if (range_lean || range_full) {
-            a.frame_list = NULL; a.frame_lo = lo; a.frame_hi = hi;
-            /* (the cold chain's first frame: the kernel that settles the sweeps it asks for itself - see below.  Not for a short call whose frames ALL ask
-             * for sweeps, ten each: those are better settled side by side - 400 PAL frames 7.7 against 8.4 ms) */
-            const bool fat = range_full && memo_ready && cold_frame && hi - lo == 1 && !dev_env("SDV_NO_FAT");
-            if (fat) { a.fat_levels = e->d_sweep_levels; round_fat = true; }
-            dev_count_frames(e, a, range_lean, hi - lo);
-            RT_CHECK(rt::launch_frames(a, s, range_lean));
-            a.fat_levels = NULL;
-            launched += (uint32_t)(hi - lo); if (range_full) general += (uint32_t)(hi - lo);
-        } else {
-            /* both lists of the round in one copy: the lean one, the full one behind it */
-            if (!list_lean.empty() || !list_full.empty()) {
-                int *h = e->h_lists;            /* slots 0 and 1: 2 n_frames ints */
-                if (!list_lean.empty()) memcpy(h, list_lean.data(), list_lean.size() * sizeof(int));
-                if (!list_full.empty()) memcpy(h + list_lean.size(), list_full.data(), list_full.size() * sizeof(int));
-                RT_CHECK(rt::h2d(e->d_list_lean, h, (list_lean.size() + list_full.size()) * sizeof(int), s));
-            }
-            if (!list_lean.empty()) {
-                a.frame_list = e->d_list_lean;
-                dev_count_frames(e, a, true, (int)list_lean.size());
-                RT_CHECK(rt::launch_frames(a, s, true, (int)list_lean.size()));
-                launched += (uint32_t)list_lean.size();
-            }
-            if (!list_full.empty()) {
-                a.frame_list = e->d_list_lean + list_lean.size();
-                /* A small round on a tape whose lines ask for sweeps: the kernel that settles them while the frame waits (sdv_k_stc007_frames_fat) - no round
-                 * for the frame to come again with the outcome at hand.  (The first rounds of a damaged tape are not small, and their thousands of sweeps are
-                 * better settled all at once: the machine is full of them.) */
-                const bool fat = memo_ready && sweeps_seen > 0 && list_full.size() <= (e->d_sweep_levels.cap / 256 < 512 ? e->d_sweep_levels.cap / 256 : (size_t)512) && !dev_env("SDV_NO_FAT");
-                if (fat) { a.fat_levels = e->d_sweep_levels; round_fat = true; }
-                dev_count_frames(e, a, false, (int)list_full.size());
-                RT_CHECK(rt::launch_frames(a, s, false, (int)list_full.size()));
-                a.fat_levels = NULL;
-                launched += (uint32_t)list_full.size(); general += (uint32_t)list_full.size();
-            }
-            a.frame_list = NULL;
-        }
-#ifndef SDV_EMU
-        if (e->profiling) { RT_CHECK(hipEventRecord(e->ev1, s)); timing_pending = true; }       /* read after the next synchronising copy */
-#endif
-        /* the last frame's outgoing state travels with the flags: one read-back per round (the frame writes it there itself, v2d_store_state) */
-        e->info.rounds++; e->info.frames_launched += launched; e->info.frames_general += general;
-        return SDV_OK;
-    };
-    auto resolve_timing = [&]() -> int {
-#ifndef SDV_EMU
-        if (timing_pending) {
-            float ms = 0.f;
-            RT_CHECK(hipEventSynchronize(e->ev1));
-            RT_CHECK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-            e->info.kernel_ms += ms;
-            timing_pending = false;
-        }
-#endif
-        return SDV_OK;
-    };
-
-    int first = 0;          /* frames below are final */
-    uint8_t *const flag = e->h_flag;        /* tail_ofs + tail_bytes bytes */
-    auto sweep_count = [&]() -> int { int32_t c; memcpy(&c, flag + tail_ofs + sizeof(sdv_v2d_state), sizeof(c)); return (int)c; };
-    /* a cold chain (nothing tuned yet) cannot be predicted: decode its first frame alone, with the full kernel (again while sweeps are owed to it:
-     * nothing is tuned, the first lines go through the reference-level sweep) */
-    const bool cold = e->chain.bin.in_def_reference < e->preset.min_ref_lvl || e->chain.reset_stats;
-    cold_frame = cold;
-    if (cold) {
-        for (int pass = 0;; pass++) {
-            if (pass > 2 * height + 16) { set_error(e, "the sweeps of the first frame did not settle"); return SDV_ERR_HIP; }
-            rc = run_round(0, 1, false, true); if (rc != SDV_OK) return rc;
-            RT_CHECK(rt::d2h_pinned(flag, e->d_flag, tail_ofs + tail_bytes, s));
-            rc = resolve_timing(); if (rc != SDV_OK) return rc;
-            rc = settle_sweeps(sweep_count()); if (rc != SDV_OK) return rc;
-            if ((flag[0] & sdv::VF_KIND) != sdv::VF_ABORTED) break;
-        }
-        first = 1;
-        if (n > 1) RT_CHECK(rt::d2d(&e->d_states_in[1], &e->d_states_out[0], sizeof(sdv_v2d_state), s));
-    }
-    cold_frame = false;
-    /* first pass over everything: predicted from the one state that is known, lean kernel - unless the last call on this stream had to give most of
-     * its frames to the full kernel (a tape with damage in every frame): then the lean kernel would only give them all up again, twice (once as a
-     * crowd, once after the crowd's first frame), and the frames go to the full kernel at once */
-    enum : uint8_t { H_NONE = 0, H_FULL = 1 /* full kernel from now on */, H_PENDING = 2 /* gave up in a crowd, waits for the crowd's first frame */,
-                     H_TRIED = 3 /* ... and has had its second try with the lean kernel */, H_NEW = 0xFF };
-    const bool worn = e->worn_tape && !cold;
-    if (first < n) {
-        pa.first = first; pa.hi = n; pa.first_of = NULL;
-        if (states_owed) { a.predict_in_kernel = 1; a.base_frame = first; a.base = e->chain; }
-        else RT_CHECK(rt::launch_predict(pa, s));
-        rc = run_round(first, n, !worn, worn); if (rc != SDV_OK) return rc;
-        a.predict_in_kernel = 0;
-    }
-    std::vector<uint8_t> hard((size_t)n, worn ? (uint8_t)H_FULL : (uint8_t)H_NONE), is_anchor((size_t)n, 0), changed((size_t)n, 0), held((size_t)n, 0);
-    std::vector<uint8_t> slow((size_t)n, 0);        /* the last decode of the frame took lines through the general path (VF_SLOW) */
-    std::vector<uint8_t> hist_off((size_t)n, 0);    /* the link behind the frame broke (also) over the 16-frame history (VF_HIST) */
-    bool have_tail = false;
-    int repair_rounds = 0;
-    const bool trace = dev_env("SDV_SCHED_TRACE") != NULL;        /* developer aid */
-    for (unsigned iter = 0; first < n; iter++) {
-        if (iter > 4u * (unsigned)n + 16u) { set_error(e, "chain speculation did not settle"); return SDV_ERR_HIP; }
-        /* every frame has written how it left the chain (stc007_device.h, v2d_store_state) */
-        if (iter == 0 && after_first_round) {
-            /* the read-back of the first round, then the work of the stage behind, and the host waits for the read-back only */
-#ifndef SDV_EMU
-            if (!e->have_mark) { RT_CHECK(hipEventCreateWithFlags(&e->ev_mark, hipEventDisableTiming)); e->have_mark = true; }
-            RT_CHECK(hipMemcpyAsync(flag + first, e->d_flag + first, tail_ofs + tail_bytes - (size_t)first, hipMemcpyDeviceToHost, s));
-            RT_CHECK(hipEventRecord(e->ev_mark, s));
-#else
-            RT_CHECK(rt::d2h_pinned(flag + first, e->d_flag + first, tail_ofs + tail_bytes - (size_t)first, s));
-#endif
-            rc = after_first_round(after_ctx);
-#ifndef SDV_EMU
-            /* (the flags' read-back is in flight into h_flag, and the stage behind may have queued kernels that write the caller's buffers: an error return
-             * waits for all of it - the caller may free or reuse its memory the moment the call is back) */
-            if (rc != SDV_OK) { (void)hipStreamSynchronize(s); return rc; }
-            { const hipError_t ev_rc = hipEventSynchronize(e->ev_mark); if (ev_rc != hipSuccess) { (void)hipStreamSynchronize(s); set_error(e, std::string("hipEventSynchronize(e->ev_mark): ") + rt::err_str(ev_rc)); return SDV_ERR_HIP; } }
-#else
-            if (rc != SDV_OK) return rc;
-#endif
-        } else
-        RT_CHECK(rt::d2h_pinned(flag + first, e->d_flag + first, tail_ofs + tail_bytes - (size_t)first, s));
-        have_tail = true;
-        rc = resolve_timing(); if (rc != SDV_OK) return rc;
-        if (memo_ready) {
-            const int before = memo_done;
-            rc = settle_sweeps(sweep_count()); if (rc != SDV_OK) return rc;
-            if (memo_done > before && iter > 0) iter--;         /* (a round that only waited for sweeps is not one the speculation failed in) */
-        }
-        if (!trace) {       /* a tape that plays: every frame left the chain as predicted (all flags VF_OK) - nothing below has anything to do */
-            uint64_t acc = 0; int k = first;
-            for (; k + 8 <= n; k += 8) { uint64_t v; memcpy(&v, flag + k, 8); acc |= v; }
-            for (; k < n; k++) acc |= flag[k];
-            if (acc == 0) { std::fill(slow.begin() + first, slow.end(), (uint8_t)0); break; }
-        }
-        if (states_owed) {      /* the round was not the last: what its waves were started from, for the kernels and the book-keeping of the rounds behind it */
-            states_owed = false;
-            RT_CHECK(rt::h2d(e->d_states_in, &e->chain, sizeof(sdv_v2d_state), s));
-            pa.first = 0; pa.hi = n; pa.first_of = NULL;
-            RT_CHECK(rt::launch_predict(pa, s));
-        }
-        for (int k = first; k < n; k++) {
-            changed[(size_t)k] = (flag[k] & (sdv::VF_RETUNED | sdv::VF_MOVED)) == sdv::VF_RETUNED; slow[(size_t)k] = (flag[k] & sdv::VF_SLOW) ? 1 : 0;
-            hist_off[(size_t)k] = (flag[k] & sdv::VF_HIST) ? 1 : 0;
-            flag[k] &= sdv::VF_KIND;
-        }
-        /* frames a lean wave gave up: all of them to the full kernel, each from the state it has */
-        list_lean.clear(); list_full.clear();
-        /* A frame the lean kernel gave up is decoded by the full kernel, from the state it has, and by the full kernel from then on -
-         * unless it gave up together with the frames behind it.  That is not a damaged frame but a state that does not fit any more
-         * (the data window moved): the full kernel would search every one of those frames for the new window, where the reference
-         * searches the first and hands the result on.  So only the first frame of such a crowd is decoded now; the others wait, and
-         * are then predicted from what it found and given to the lean kernel once more. */
-        bool redo_first = false;
-        for (int k = first; k < n; k++) {
-            held[(size_t)k] = 0;
-            if (flag[k] == sdv::VF_ABORTED && hard[k] == H_PENDING) {       /* to be decoded again: as if the link into it had broken */
-                /* ... once the frame in front of the crowd is settled: while that one is still owed a reference-level sweep (it came back from the full
-                 * kernel as given up) its outcome is a guess, and the crowd goes on waiting */
-                if (k > first && (held[(size_t)k - 1] || (flag[k - 1] == sdv::VF_ABORTED && hard[k - 1] != H_PENDING))) { held[(size_t)k] = 1; continue; }
-                flag[k] = sdv::VF_OK;
-                if (k > first) flag[k - 1] = sdv::VF_BREAK; else redo_first = true;
-            }
-        }
-        int n_break = 0, b0 = -1, n_leaders = 0;
-        for (int k = first; k < n; k++) {
-            if (held[(size_t)k]) continue;
-            if (flag[k] == sdv::VF_ABORTED) { hard[k] = hard[k] == H_NONE ? H_NEW : H_FULL; list_full.push_back(k); }
-            else if (flag[k] == sdv::VF_BREAK) {
-                /* A broken link makes the next frame an anchor - the first of a run of broken links, that is.  The frames further
-                 * into the run were started from states that descend from one now known to be wrong, so what they handed over, and
-                 * the breaks behind them, may only be a consequence of that: the data coordinates a frame inherits pass through it
-                 * unchanged as long as its lines decode with them (a few pixels off still decodes), and the 16-frame coordinate
-                 * history passes through by construction.  An anchor with such a state would hand it down the chain one frame per
-                 * round; predicted again from the run's first anchor the frames follow a jump of the data window in one round. */
-                const bool in_run = k > first ? flag[k - 1] == sdv::VF_BREAK : redo_first;
-                if (b0 < 0) b0 = k;
-                n_break++;
-                /* ... unless the frame only came out with other levels than the model makes of what it went in with (VF_RETUNED without VF_MOVED): a
-                 * lost line makes the worker measure black and white again from the pixels that follow, whatever they were before, so the frame
-                 * most likely leaves the same levels when it is decoded again from the right state - its successor is started from what it left.
-                 * Frames that moved their coordinates or histories are different: those pass through the 9-line window, the damper and the 16-frame
-                 * history, what a frame leaves does depend on what it got, and the model from the run's first anchor is the better guess.
-                 * (Measured on 10 000 frames: a line lost in every frame 51 -> 12 ms; the same rule for frames that moved, 16 jumps: 18 -> 312 ms.
-                 * Tried on top and dropped: working out the levels of a whole run byte by byte from which bytes each frame passed on and which it set
-                 * in the last round - black and white are measured again to nearly the same values by every damaged frame and pass for handed on.) */
-                if (k + 1 < n) is_anchor[(size_t)k + 1] = (in_run && !changed[(size_t)k]) ? 0 : 1;
-            }
-        }
-        {
-            /* ... the first frame of every WINDOW the crowd looks at, that is: a crowd that spans several jumps (all of them out of reach of the state the
-             * frames were started from) would otherwise find its windows one per pair of rounds - leader, the frames predicted from it, the next stretch
-             * gives up, its leader ...  The lean waves leave where the line they gave up on began (FrameArgs::sig); a frame whose line begins two pixels or
-             * more beside its crowd leader's leads a crowd of its own.  A guess like any other: a leader too many is a frame through the general kernel too
-             * many, a leader missed is found the old way. */
-            size_t w = 0;
-            bool have_sig = false;
-            const uint8_t *const sig = flag + sig_ofs;
-            for (size_t i = 0; i < list_full.size();) {
-                size_t j = i + 1;
-                while (j < list_full.size() && list_full[j] == list_full[j - 1] + 1) j++;
-                bool fresh = j - i >= 8;
-                for (size_t q = i; q < j && fresh; q++) fresh = hard[(size_t)list_full[q]] == H_NEW;
-                if (fresh && !have_sig && !dev_env("SDV_SCHED_NO_SIG")) { RT_CHECK(rt::d2h_pinned(flag + sig_ofs, e->d_flag + sig_ofs, (size_t)n, s)); have_sig = true; }
-                int lead_sig = -1, since_lead = 0;
-                for (size_t q = i; q < j; q++) {
-                    const int k = list_full[q];
-                    bool leader = !fresh || q == i;
-                    if (!leader && have_sig) {
-                        const int sg = sig[k];
-                        /* (a leader needs followers: the last few frames of a run stay with the leader they have - they would go through the general kernel one by one anyway) */
-                        if (sg != 0xFF && lead_sig >= 0 && (sg >= lead_sig + 2 || sg + 2 <= lead_sig) && since_lead >= 2) leader = true;
-                    }
-                    if (leader) { hard[(size_t)k] = H_FULL; list_full[w++] = k; if (fresh) { lead_sig = have_sig && sig[k] != 0xFF ? (int)sig[k] : -1; since_lead = 0; n_leaders++; } }
-                    else { hard[(size_t)k] = H_PENDING; since_lead++; }
-                }
-                i = j;
-            }
-            list_full.resize(w);
-        }
-        if (trace && b0 >= 0 && b0 + 1 < n) {           /* developer aid: what the first broken link disagrees on */
-            sdv_v2d_state so, si;
-            RT_CHECK(rt::d2h(&so, &e->d_states_out[b0], sizeof(so), s)); RT_CHECK(rt::d2h(&si, &e->d_states_in[b0 + 1], sizeof(si), s));
-            const uint32_t *x = (const uint32_t *)&so, *y = (const uint32_t *)&si;
-            for (unsigned i = 0; i < sizeof(so) / 4; i++) if (x[i] != y[i]) fprintf(stderr, "[sched]   link %d: dword %u out %08x, next frame started from %08x\n", b0, i, x[i], y[i]);
-        }
-        if (trace) { int nch = 0; for (int k = first; k < n; k++) if (flag[k] == sdv::VF_BREAK) nch += changed[(size_t)k]; fprintf(stderr, "[sched]   of the broken links: %d behind frames that only re-tuned their levels\n", nch); }
-        if (trace) fprintf(stderr, "[sched] iter %u first %d: %zu given up (%d crowd leaders), %d breaks (first at %d); %u frame decodes, %.3f ms in kernels so far\n", iter, first, list_full.size(), n_leaders, n_break, b0, e->info.frames_launched, e->info.kernel_ms);
-        if (!list_full.empty()) { rc = run_round(0, 0, false, false); if (rc != SDV_OK) return rc; continue; }
-        if (redo_first) b0 = first - 1;
-        if (b0 < 0 && !redo_first) break;                              /* the whole chain holds */
-        /* frames up to the first break are final.  Behind it: the first link of every run of broken links, of this round or an earlier
-         * one, is an anchor (the next frame starts from its predecessor's real outcome), the frames in between are predicted from
-         * their anchor, and every segment whose anchor changed is decoded again - all of them in one round, over the whole rest of
-         * the batch: decoding a short window at a time would pay the rounds a disturbance takes once per window. */
-        const int done = b0 + 1 - first;
-        first = b0 + 1;
-        /* ... unless the chain still breaks in many places after more rounds than the history is deep: then the model does not fit
-         * this tape (heavy noise re-tunes the binarizer all the time) and decoding everything again every round is wasted work -
-         * from there on only a window that grows with what the last round settled */
-        int hi = n;
-        if (++repair_rounds > 24 && (long long)n_break * 64 > (long long)(n - first)) {
-            long long w = 4ll * done; if (w < 16) w = 16;
-            if (first + w < n) hi = (int)(first + w);
-        }
-        /* A level that passes through.  The reference level is sticky: a frame whose lines read with the level it inherits hands it on as it got it.
-         * When a link broke over the levels only, the frame behind it now starts from another reference level - and if it handed on the old one
-         * unchanged the last time, it will most likely hand on the new one, to a successor that was started from the old one and whose link held.
-         * Decoding only the frame behind the break would find that out one frame per round (a sweep that settles on an odd level is followed by 25
-         * such frames on the tape of SURVEY 8d C3: 77 rounds); so the new level is carried along the chain for as long as the frames are known to
-         * pass their level through, those frames get it written into the state they start from (sdv_k_ref_patch, behind the anchor copies) and
-         * are decoded in this round too.  A guess like every other state the rounds start frames from: the frames themselves say whether it held. */
-        patches.clear();
-        bool any_moved = false;         /* a link broke over coordinates or histories: the history carry below has something to do */
-        /* (... or the frame only re-tuned its levels but its successor holds another history than the one it hands on: the first frames behind a jump of the
-         * window each measure their levels anew and are anchors one by one; what they were started from the round before is older than what their predecessors
-         * hand on now - without the carry the right history would reach them one frame per round) */
-        for (int j = first > 1 ? first : 1; j < hi && !any_moved; j++) any_moved = flag[j - 1] == sdv::VF_BREAK && (!changed[(size_t)j - 1] || hist_off[(size_t)j - 1]);
-        {
-            bool any = false;
-            for (int j = first > 1 ? first : 1; j < hi && !any; j++) any = flag[j - 1] == sdv::VF_BREAK && changed[(size_t)j - 1];
-            if (any && !dev_env("SDV_SCHED_NO_PASS")) {
-                RT_CHECK(rt::d2h_pinned(e->h_refs, e->d_refs, 3 * (size_t)n, s));
-                const uint8_t *refs = e->h_refs;
-                int prop = -1;
-                for (int j = first > 1 ? first : 1; j < hi; j++) {
-                    const bool broken = flag[j - 1] == sdv::VF_BREAK;
-                    if ((broken && !changed[(size_t)j - 1]) || hard[(size_t)j] == H_PENDING) { prop = -1; continue; }      /* a frame that moved: the run model takes over */
-                    const int had = refs[3 * j], gave = refs[3 * j + 1], brought = refs[3 * (j - 1) + 1];
-                    int incoming;
-                    if (prop >= 0) incoming = prop;
-                    else if (broken) incoming = brought;
-                    else continue;                                      /* nothing new arrives at this frame */
-                    if (!broken) {
-                        if (incoming == had) { prop = -1; continue; }   /* the level it had anyway */
-                        patches.push_back((uint32_t)j | ((uint32_t)incoming << 24));
-                        flag[j - 1] = sdv::VF_BREAK; is_anchor[(size_t)j] = 1;         /* decoded again, from its own (patched) state */
-                    } else if (incoming != brought) patches.push_back((uint32_t)j | ((uint32_t)incoming << 24));     /* (the anchor copy brings the predecessor's old level) */
-                    prop = (incoming != had && gave == had) ? incoming : -1;
-                }
-                if (trace) fprintf(stderr, "[sched]   a level carried on into %zu frames\n", patches.size());
-            }
-        }
-        /* only the segments whose anchor gets a new state are decoded again; the others keep what they have */
-        anchors.clear(); first_of.resize((size_t)(hi - first));
-        int cur = first; bool dirty = true, any_hard = false, contiguous = true;
-        int run_lo = first, run_hi = first;
-        for (int k = first; k < hi; k++) {
-            if (k == first || is_anchor[(size_t)k]) {       /* anchors stay anchors: a link that held is not predicted over */
-                cur = k; dirty = k == first || flag[k - 1] == sdv::VF_BREAK;
-                if (dirty) anchors.push_back(k);
-            }
-            first_of[(size_t)(k - first)] = dirty ? cur : k;
-            in_round[(size_t)k] = dirty ? 1 : 0;
-            if (dirty) {
-                if (hard[k] == H_PENDING) hard[k] = H_TRIED;
-                (hard[k] == H_FULL ? list_full : list_lean).push_back(k);
-                any_hard = any_hard || hard[k] == H_FULL;
-                if (k != run_hi) contiguous = false;
-                run_hi = k + 1;
-            }
-        }
-        /* the round's three small lists in one copy: anchors, then the level patches, then first_of */
-        int *const d_anch = e->d_anchors; uint32_t *const d_pat = reinterpret_cast<uint32_t *>(d_anch + anchors.size()); int *const d_fof = d_anch + anchors.size() + patches.size();
-        {
-            static_assert(sizeof(uint32_t) == sizeof(int), "one staging area for the three lists");
-            int *h = e->h_lists + 2 * (size_t)n_frames;         /* slots 2 .. 4: 3 n_frames ints; every list holds at most n_frames */
-            if (!anchors.empty()) memcpy(h, anchors.data(), anchors.size() * sizeof(int));
-            if (!patches.empty()) memcpy(h + anchors.size(), patches.data(), patches.size() * sizeof(uint32_t));
-            if (!first_of.empty()) memcpy(h + anchors.size() + patches.size(), first_of.data(), first_of.size() * sizeof(int));
-            RT_CHECK(rt::h2d(d_anch, h, (anchors.size() + patches.size() + first_of.size()) * sizeof(int), s));
-        }
-        sdv::AnchorArgs aa; aa.states_in = e->d_states_in; aa.states_out = e->d_states_out; aa.list = d_anch; aa.n = (int)anchors.size(); aa.flag = e->d_flag;
-        RT_CHECK(rt::launch_anchor(aa, s));
-        if (!patches.empty()) {
-            sdv::RefPatchArgs ra; ra.states_in = e->d_states_in; ra.patch = d_pat; ra.n = (int)patches.size();
-            RT_CHECK(rt::launch_ref_patch(ra, s));
-        }
-        pa.first = first; pa.hi = hi; pa.first_of = d_fof;
-        const bool use_skip = !dev_env("SDV_SCHED_NO_SKIP");
-        if (use_skip) { RT_CHECK(rt::dfill_bytes(e->d_skip + first, 0, (size_t)(hi - first), s)); pa.skip = e->d_skip; }
-        RT_CHECK(rt::launch_predict(pa, s));
-        pa.skip = NULL;
-        if (any_moved && !anchors.empty() && !dev_env("SDV_SCHED_NO_CARRY")) {     /* the history moves on (sdv_k_hist_carry): frames it reaches are decoded in this round too */
-            RT_CHECK(rt::dfill_bytes(e->d_patched + first, 0, (size_t)(hi - first), s));
-            sdv::HistCarryArgs ha; ha.states_in = e->d_states_in; ha.refs = e->d_refs; ha.anchors = d_anch; ha.n_anchors = (int)anchors.size(); ha.hi = hi; ha.patched = e->d_patched; ha.skip = use_skip ? e->d_skip.p : NULL;
-            RT_CHECK(rt::launch_hist_carry(ha, s));
-            RT_CHECK(rt::d2h_pinned(e->h_patched + first, e->d_patched + first, (size_t)(hi - first), s));
-            size_t reached = 0;
-            for (int k = first; k < hi; k++)
-                if (e->h_patched[k] && !in_round[(size_t)k]) {
-                    if (hard[k] == H_PENDING) hard[k] = H_TRIED;
-                    (hard[k] == H_FULL ? list_full : list_lean).push_back(k);
-                    any_hard = any_hard || hard[k] == H_FULL; contiguous = false; reached++;
-                }
-            if (trace) fprintf(stderr, "[sched]   the history moved on into %zu more frames\n", reached);
-        }
-        a.skip = use_skip ? e->d_skip.p : NULL;
-        if (!any_hard && contiguous) rc = run_round(run_lo, run_hi, true, false);
-        else rc = run_round(0, 0, false, false);
-        a.skip = NULL;
-        if (rc != SDV_OK) return rc;
-    }
-    uint32_t frames_met_now = 0;
-    if (have_tail && memo_ready) { int32_t met; memcpy(&met, flag + tail_ofs + sizeof(sdv_v2d_state) + 4, sizeof(met)); frames_met_now = (uint32_t)met; }
-    {   /* A worn tape: most frames of the call did take lines through the general path - the next call starts its frames on the full kernel.  Decided on
-         * what the frames did (VF_SLOW of their last decode), not on where they were scheduled (a worn call schedules every frame on the full kernel:
-         * judged by that, the mark never came off again, and a cold one-frame call was enough to set it); the cold first frame does not count, and a call
-         * of a few frames says nothing either way. */
-        const int from = cold ? 1 : 0;
-        size_t n_slow = 0;
-        for (int k = from; k < n; k++) n_slow += slow[(size_t)k];
-        if (n - from >= 8) e->worn_tape = n_slow * 2 > (size_t)(n - from);
-        /* (which build of the general kernel the next call takes: see plain_general) */
-        if (memo_ready && n - from >= 8) {
-            if (a.tc_hdr) { e->plain_general = e->worn_tape && e->info.frames_general >= (uint32_t)n && (uint64_t)frames_met_now * 16u < (uint64_t)e->info.frames_general; e->plain_calls = 0; }
-            else e->plain_calls++;
-        } else if (!memo_ready) { e->plain_general = false; e->plain_calls = 0; }
-    }
-    if (have_tail && memo_ready) { int32_t met; memcpy(&met, flag + tail_ofs + sizeof(sdv_v2d_state) + 4, sizeof(met)); e->info.frames_met = (uint32_t)met; }     /* (behind the count of sweep requests) */
-    if (have_tail) memcpy(&e->chain, flag + tail_ofs, sizeof(sdv_v2d_state));     /* came with the flags of the round that settled the chain */
-    else { RT_CHECK(rt::d2h(&e->chain, &e->d_states_out[n_frames - 1], sizeof(sdv_v2d_state), s)); rc = resolve_timing(); if (rc != SDV_OK) return rc; }
-    return SDV_OK;
-}
-
 
 /* Binarizer::processLine with an STC007Line as output, a wave per line (stc007_device.h, stc_line_body).  The reference-level sweeps the lines ask for are
  * settled between passes like the frame entry's: a pass, the round's requests through the sweep kernels, the lines that waited again - a line asks for one
@@ -1279,4 +789,5 @@ int sdv_deinterleave_blocks(sdv_engine *e, const sdv_deint_line *lines, size_t n
 
 } /* extern "C" */
 
+#include "stc007_frames_engine.inc"  /* sdv_binarize_frames */
 #include "ingest_engine.inc"         /* sdv_ingest_geometry, sdv_ingest_frames */

@@ -38,26 +38,15 @@ static int markerless_binarize_frames(sdv_engine *e, const uint8_t *luma, size_t
     using sdvp1f::PrescanRes;
     if (!e) return SDV_ERR_BAD_ARG;
     FrameFlagsConsumed flags_consumed(e);
-    if (!luma) { set_error(e, "null video"); return SDV_ERR_NULL_VIDEO; }
-    if (!out_lines || !out_stats) { set_error(e, "null output"); return SDV_ERR_NULL_PCM; }
-    if (n_frames <= 0 || height < 2 || height > SDV_MAX_HEIGHT || width <= 0 || width > SDV_PX_BYTES || row_stride < (size_t)width) {
-        set_error(e, "bad frame geometry"); return SDV_ERR_BAD_ARG;
-    }
-    if (width < Fmt::MIN_WIDTH) { set_error(e, Fmt::short_line()); return SDV_ERR_SHORT_LINE; }
-    if (n_frames > 1 && frame_stride < (size_t)(height - 1) * row_stride + (size_t)width) { set_error(e, "frame_stride smaller than one frame"); return SDV_ERR_BAD_ARG; }
-    {
-        const size_t need_lines = Fmt::records_needed(height, n_frames, flags), need_stats = (size_t)n_frames + ((flags & SDV_FLAG_END_FILE) ? 1 : 0);
-        if (lines_cap < need_lines || stats_cap < need_stats) {
-            set_error(e, "output buffers too small: " + std::to_string(need_lines) + " " + Fmt::rec_noun() + " and " + std::to_string(need_stats) + " frame descriptors are needed");
-            return SDV_ERR_BAD_ARG;
-        }
-    }
+    int rc = check_frame_call(e, luma, out_lines, out_stats, row_stride, frame_stride, width, height, n_frames, flags, lines_cap, stats_cap,
+                              SDV_PX_BYTES, Fmt::MIN_WIDTH, Fmt::short_line(), Fmt::records_needed(height, n_frames, flags), Fmt::rec_noun());
+    if (rc != SDV_OK) return rc;
     rt::stream_t s = (rt::stream_t)stream;
     SDV_ON_DEVICE(e);
     const int n_real = n_frames;
     if (flags & SDV_FLAG_END_FILE) n_frames++;
     const int n = n_frames;
-    int rc = ensure_capacity(e, (size_t)n, (size_t)height * Fmt::LINES_PER_ROW);
+    rc = ensure_capacity(e, (size_t)n, (size_t)height * Fmt::LINES_PER_ROW);
     if (rc != SDV_OK) return rc;
     RT_CHECK(Fmt::reserve_states(e, (size_t)n));
     rt::DevBuf<uint8_t> &prescan_buf = Fmt::prescan_buf(e);

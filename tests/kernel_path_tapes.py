@@ -1,11 +1,12 @@
-"""Tapes that steer sdv_binarize_frames onto each build of the STC-007 frame kernel (engine.inc: run_round, prepare_memo, settle_sweeps), as streams of
+"""Tapes that steer sdv_binarize_frames onto each build of the STC-007 frame kernel (stc007_frames_engine.inc: run_round_range / run_round_lists, prepare_memo,
+settle_sweeps), as streams of
 several calls.  Shared by the emulator tests, the GPU tests against the oracle (test_gpu_kernel_paths.py) and the child process that runs them through the
 developer build of the HIP library, counts the launches and decodes every tape again under each off-switch of the scheduler."""
 import numpy as np
 
 from sdvpcmdecoder_amd import synth
 
-# the scheduler's off-switches (read by developer builds only: engine.inc dev_env)
+# the scheduler's off-switches (read by developer builds only: engine.inc dev_env; stc007_frames_engine.inc reads them)
 SWITCHES = ("SDV_NO_FAT", "SDV_NO_TC", "SDV_SCHED_NO_SIG", "SDV_SCHED_NO_PASS", "SDV_SCHED_NO_SKIP", "SDV_SCHED_NO_CARRY", "SDV_NO_PREDICT_IN_KERNEL")
 
 
@@ -103,6 +104,45 @@ TAPES = {
     "general_kernel_later_shift_stage": _general_shift_tape,
     "model_gives_old_state": _model_skip_tape,
 }
+
+
+# What every call of a stream costs, (rounds, frames_launched, frames_general, sweeps, frames_met) of sdv_run_info: records that equal the sequential oracle's
+# say that the schedule settled, not which schedule it was - any that settles gives them.  The emulator's figures are deterministic; taken before the frame
+# entry was split into a plan and a driver (profiles/stc007_scheduler_notes.md), they pin the scheduler's decisions round by round.
+# (big_round_with_sweeps, worn_plain_reprobe and pass_meets_last_16x200 are not decoded on the emulator at these sizes: GPU_SCHEDULE has them.)
+SCHEDULE = {
+    "cold_chain_first_sweep": [(2, 4, 1, 1, 0)],
+    "general_kernel_later_shift_stage": [(4, 13, 4, 1, 0)],
+    "crowd_waits_for_first_frame": [(6, 42, 21, 103, 0)],
+    "crowd_over_several_windows": [(2, 20, 1, 1, 0), (7, 516, 113, 0, 37)],
+    "model_gives_old_state": [(2, 20, 1, 1, 0), (7, 362, 65, 0, 23)],
+    "pass_meets_last_30x64": [(2, 8, 1, 1, 0), (7, 119, 64, 156, 0)],
+    "worn_mark_comes_and_goes": [(1, 1, 1, 1, 0), (1, 12, 0, 0, 0), (7, 47, 24, 153, 0), (1, 12, 12, 0, 0), (1, 12, 0, 0, 0)],
+}
+# ... and crowd_over_several_windows under each off-switch: every switch goes on steering the code it steered
+SWITCH_SCHEDULE = {
+    "SDV_NO_FAT": [(3, 21, 2, 1, 0), (7, 516, 113, 0, 37)],
+    "SDV_NO_TC": [(2, 20, 1, 1, 0), (7, 516, 113, 0, 0)],
+    "SDV_SCHED_NO_SIG": [(2, 20, 1, 1, 0), (9, 702, 341, 0, 45)],
+    "SDV_SCHED_NO_PASS": SCHEDULE["crowd_over_several_windows"],
+    "SDV_SCHED_NO_SKIP": SCHEDULE["crowd_over_several_windows"],
+    "SDV_SCHED_NO_CARRY": [(2, 20, 1, 1, 0), (13, 560, 116, 0, 37)],
+    "SDV_NO_PREDICT_IN_KERNEL": SCHEDULE["crowd_over_several_windows"],
+}
+
+# The same on the MI355X (test_gpu_kernel_paths.test_gpu_tape_equals_the_sequential_oracle): every tape decoded twice there gave the same figures both times,
+# and the emulator's where the emulator decodes the tape - so the GPU column is the emulator's, with the three tapes only the GPU decodes at this size.
+GPU_SCHEDULE = dict(SCHEDULE)
+GPU_SCHEDULE.update({
+    "worn_plain_reprobe": [(7, 44, 23, 211, 0), (3, 35, 35, 217, 0), (4, 36, 36, 215, 0), (3, 34, 34, 212, 0), (3, 35, 35, 218, 0), (5, 47, 47, 223, 0), (3, 35, 35, 215, 0),
+                           (5, 40, 40, 210, 0), (5, 42, 42, 216, 0), (3, 35, 35, 214, 0)],
+    "big_round_with_sweeps": [(13, 4204, 3007, 2771, 7), (14, 3366, 3366, 2518, 0)],
+    "pass_meets_last_16x200": [(2, 8, 1, 1, 0), (7, 63, 34, 262, 0)],
+})
+
+
+def schedule_of(info):
+    return (info.rounds, info.frames_launched, info.frames_general, info.sweeps, info.frames_met)
 
 
 def run_stream(call, luma, calls):

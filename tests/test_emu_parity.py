@@ -9,6 +9,7 @@ import pytest
 
 import engine_api
 import golden_cases
+import kernel_path_tapes as K
 import libs
 from oracle_run import oracle_binarize
 from sdvpcmdecoder_amd import synth
@@ -205,7 +206,7 @@ def test_emu_crowd_over_several_windows_is_led_by_the_first_frame_of_each(emu_li
         if switch: monkeypatch.setenv(switch, "1")
         eng = C.c_void_p(emu_lib.sdv_engine_create(0))
         emu_lib.sdv_set_mode(eng, 2)
-        a, sa, _ = emu_run(emu_lib, luma0[:20], 2, eng=eng)
+        a, sa, info_a = emu_run(emu_lib, luma0[:20], 2, eng=eng)
         b, sb, info = emu_run(emu_lib, luma, 2, flags=0, first=21, eng=eng)
         emu_lib.sdv_engine_destroy(eng)
         if switch: monkeypatch.delenv(switch)
@@ -213,6 +214,8 @@ def test_emu_crowd_over_several_windows_is_led_by_the_first_frame_of_each(emu_li
         assert got.tobytes() == want.tobytes(), golden_cases.diff_report(got, want)
         assert np.concatenate([sa, sb]).view(np.uint8).tobytes() == want_stats.tobytes()
         seen[switch] = (info.rounds, info.frames_general)
+        # (the tape is kernel_path_tapes' crowd_over_several_windows: its schedule, call by call)
+        assert [K.schedule_of(info_a), K.schedule_of(info)] == (K.SWITCH_SCHEDULE[switch] if switch else K.SCHEDULE["crowd_over_several_windows"])
     assert seen[None][0] < seen["SDV_SCHED_NO_SIG"][0] and seen[None][1] < seen["SDV_SCHED_NO_SIG"][1], seen
     assert seen[None][0] <= 8, seen
 
@@ -267,6 +270,7 @@ def test_emu_cold_chain_settles_its_first_sweep_in_one_pass(emu_lib, oracle_lib,
         assert got.tobytes() == want.tobytes(), golden_cases.diff_report(got, want)
         assert got_stats.view(np.uint8).tobytes() == want_stats.tobytes()
         seen[switch] = (info.rounds, info.sweeps)
+        if not switch: assert [K.schedule_of(info)] == K.SCHEDULE["cold_chain_first_sweep"]
         if switch: assert counts["fat"] == 0 and counts["sweep_levels"] >= 1, counts
         else: assert counts["fat"] == 1 and counts["fat_frames"] == 1 and counts["sweep_levels"] == 0, counts
     assert seen[None] == (2, seen["SDV_NO_FAT"][1]) and seen["SDV_NO_FAT"][0] == 3 and seen[None][1] >= 1, seen
@@ -331,6 +335,7 @@ def test_emu_general_kernel_on_a_later_shift_stage(emu_lib, oracle_lib):
     assert got.tobytes() == want.tobytes(), golden_cases.diff_report(got, want)
     assert got_stats.view(np.uint8).tobytes() == want_stats.tobytes()
     assert info.frames_general >= 2
+    assert [K.schedule_of(info)] == K.SCHEDULE["general_kernel_later_shift_stage"]
 
 
 def test_emu_frames_the_model_gives_their_old_state_are_not_decoded_again(emu_lib, oracle_lib, monkeypatch):
@@ -347,7 +352,7 @@ def test_emu_frames_the_model_gives_their_old_state_are_not_decoded_again(emu_li
         if switch: monkeypatch.setenv(switch, "1")
         eng = C.c_void_p(emu_lib.sdv_engine_create(0))
         emu_lib.sdv_set_mode(eng, 2)
-        a, sa, _ = emu_run(emu_lib, luma0[:20], 2, eng=eng)
+        a, sa, info_a = emu_run(emu_lib, luma0[:20], 2, eng=eng)
         b, sb, info = emu_run(emu_lib, luma, 2, flags=0, first=21, eng=eng)
         emu_lib.sdv_engine_destroy(eng)
         if switch: monkeypatch.delenv(switch)
@@ -355,13 +360,14 @@ def test_emu_frames_the_model_gives_their_old_state_are_not_decoded_again(emu_li
         assert got.tobytes() == want.tobytes(), golden_cases.diff_report(got, want)
         assert np.concatenate([sa, sb]).view(np.uint8).tobytes() == want_stats.tobytes()
         seen[switch] = (info.rounds, info.frames_launched)
+        if not switch: assert [K.schedule_of(info_a), K.schedule_of(info)] == K.SCHEDULE["model_gives_old_state"]
     assert seen[None] == seen["SDV_SCHED_NO_SKIP"], seen
 
 
 def test_emu_worn_tape_without_meetings_takes_the_plain_general_kernel(emu_lib, oracle_lib):
     """A tape with an unreadable cell in every fifth line: every frame goes through the general kernel, and hardly a decode meets the frame's last pass (each
     damaged line re-tunes the binarizer for good).  The engine sees that in the first call and gives the calls behind it to the build of the general kernel
-    without snapshots (engine.inc, plain_general; stc007_device.h, kMeet) - the records stay the sequential oracle's."""
+    without snapshots (stc007_chain_plan.h, judge_tape: plain_general; stc007_device.h, kMeet) - the records stay the sequential oracle's."""
     n, h = 12, 96
     luma0, _, _ = synth.stc007_frames(4 * n, seed=31, height=h, noise_sigma=4.0)
     lum = luma0.copy()
@@ -444,7 +450,7 @@ def test_emu_worn_tape_mark_comes_and_goes(emu_lib, oracle_lib):
     per = 96 + 3
     eng = C.c_void_p(emu_lib.sdv_engine_create(0))
     emu_lib.sdv_set_mode(eng, 2)
-    got0, _, _ = emu_run(emu_lib, clean[:1], 2, eng=eng)                          # the cold frame alone
+    got0, _, info0 = emu_run(emu_lib, clean[:1], 2, eng=eng)                      # the cold frame alone
     got1, _, info = emu_run(emu_lib, clean[1:13], 2, flags=0, first=2, eng=eng)
     assert info.frames_general == 0, "a clean tape behind a one-frame cold call: nothing for the full kernel"
     assert np.concatenate([got0, got1]).tobytes() == want[:1 + 13 * per].tobytes()
@@ -464,13 +470,14 @@ def test_emu_worn_tape_mark_comes_and_goes(emu_lib, oracle_lib):
     assert c3["snap_frames"] + c3["plain_frames"] >= 12 and c3["lean"] == 0, c3          # the worn call: every frame on a general build from the start
     assert c4["lean_frames"] >= 12 and c4["snap"] + c4["plain"] + c4["fat"] == 0, c4
     assert info3.frames_general >= 12 and info4.frames_general == 0, (info3.frames_general, info4.frames_general)
+    assert [K.schedule_of(i) for i in (info0, info, info2, info3, info4)] == K.SCHEDULE["worn_mark_comes_and_goes"]
 
 
 @pytest.mark.parametrize("noise", [4.0, 0.0])
 def test_emu_unreadable_cells_sweep_every_level(emu_lib, oracle_lib, noise):
     """A bit cell inverted on some lines: their reference level sweep runs over every level, the levels near white leave a zero source CRC word
     (two outcomes per level, chained through the lanes - stc007_device.h sweep_ref_level); the scheduler carries the level such a sweep settles on
-    along the chain (engine.inc, "a level that passes through").  (Also on a tape without noise: two thirds of a sweep's levels then lie in the gap between the dark
+    along the chain (stc007_chain_plan.h, carry_levels: "a level that passes through").  (Also on a tape without noise: two thirds of a sweep's levels then lie in the gap between the dark
     and the bright pixels and all come out alike.)"""
     from test_gpu_parity import _unreadable_cells
     luma, _, _ = synth.stc007_frames(6, seed=78, noise_sigma=noise, height=120, lines_per_field=60)
@@ -495,6 +502,7 @@ def test_emu_crowd_waits_for_the_sweeps_of_its_first_frame(emu_lib, oracle_lib):
     assert got.tobytes() == want.tobytes(), golden_cases.diff_report(got, want)
     assert got_stats.view(np.uint8).tobytes() == want_stats.tobytes()
     assert info.sweeps > 50
+    assert [K.schedule_of(info)] == K.SCHEDULE["crowd_waits_for_first_frame"]
 
 
 def _jittered_tape(n, seed, jit, **kw):
@@ -523,7 +531,7 @@ def test_emu_lines_that_read_on_other_rungs_of_the_ladder(emu_lib, oracle_lib, s
 
 def test_emu_worn_tape_plain_build_and_its_reprobe(emu_lib, oracle_lib):
     """The worn tape of the test above in ten calls of twelve frames (at a small height): the first call looks at the tape with the snapshots, calls 2-8 and
-    10 take the plain build, call 9 looks again with the snapshots (engine.inc: plain_calls % 8) - launch counts by build, records, frame descriptors and the
+    10 take the plain build, call 9 looks again with the snapshots (stc007_frames_engine.inc, prepare_memo: plain_calls % 8) - launch counts by build, records, frame descriptors and the
     chain state at the end against the sequential oracle."""
     import kernel_path_tapes as K
     luma = K.worn_tape(120, 24)
@@ -545,3 +553,35 @@ def test_emu_worn_tape_plain_build_and_its_reprobe(emu_lib, oracle_lib):
     assert stats.tobytes() == want_stats.tobytes() and state.raw == want_state.tobytes()
     counts = [c for _, c in per_call]
     assert K.check_counts("worn_plain_reprobe", counts) is None, counts
+
+
+def _emu_schedule(emu_lib, name):
+    """(rounds, frames_launched, frames_general, sweeps, frames_met) of every call of a tape of kernel_path_tapes, MODE_NORMAL, from a new file"""
+    luma, calls = K.TAPES[name]()
+    eng = C.c_void_p(emu_lib.sdv_engine_create(0))
+    emu_lib.sdv_set_mode(eng, 2)
+
+    def call(chunk, first, new_file):
+        rc, r, st = engine_api.emu_binarize(emu_lib, eng, chunk, first_frame_no=first, flags=1 if new_file else 0)
+        assert rc == 0
+        info = engine_api.RunInfo(); emu_lib.sdv_get_run_info(eng, C.byref(info))
+        return r, st, info, None
+
+    _, _, per_call = K.run_stream(call, luma, calls)
+    emu_lib.sdv_engine_destroy(eng)
+    return [K.schedule_of(i) for i, _ in per_call]
+
+
+def test_emu_schedule_of_the_tape_whose_passes_meet(emu_lib):
+    """pass_meets_last_30x64 without a switch (test_emu_a_pass_that_meets_the_last_one_changes_nothing decodes it under SDV_NO_FAT): what every call costs is
+    what it cost before the scheduler was split into a plan and a driver (kernel_path_tapes.SCHEDULE; the other small tapes are pinned by the tests above
+    that decode them anyway)."""
+    assert _emu_schedule(emu_lib, "pass_meets_last_30x64") == K.SCHEDULE["pass_meets_last_30x64"]
+
+
+@pytest.mark.parametrize("switch", [s for s in K.SWITCHES if s != "SDV_SCHED_NO_SIG"])
+def test_emu_every_switch_steers_what_it_steered(emu_lib, monkeypatch, switch):
+    """crowd_over_several_windows under each off-switch of the scheduler (SDV_SCHED_NO_SIG: test_emu_crowd_over_several_windows_is_led_by_the_first_frame_of_each):
+    the schedule the switch gave before the split - another one than the default's where the switch has something to switch off on this tape."""
+    monkeypatch.setenv(switch, "1")
+    assert _emu_schedule(emu_lib, "crowd_over_several_windows") == K.SWITCH_SCHEDULE[switch]

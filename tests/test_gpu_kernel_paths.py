@@ -75,6 +75,8 @@ def test_gpu_tape_equals_the_sequential_oracle(name):
     assert stats == want[1]
     assert state == want[2]
     info = [i for i, _ in per_call]
+    if name in K.GPU_SCHEDULE:      # (what every call cost before the scheduler was split into a plan and a driver: the schedule itself, not only that it settles)
+        assert [K.schedule_of(i) for i in info] == K.GPU_SCHEDULE[name]
     if name == "worn_plain_reprobe":
         assert all(i.frames_general >= 12 for i in info), [i.frames_general for i in info]
         assert [i.frames_met for i in info[1:8]] == [0] * 7 and info[9].frames_met == 0, [i.frames_met for i in info]      # (the plain build meets nothing)

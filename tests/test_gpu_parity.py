@@ -73,7 +73,7 @@ def test_hip_jitter_and_dropouts(torch_cuda):
 
 def test_hip_sparse_dropouts_settle_in_few_rounds(torch_cuda):
     """A long tape with a lost line now and then: every dropout frame is given up by the lean kernel and re-tunes the chain behind it.
-    The output equals the sequential decode and the number of rounds stays small (anchors at every broken link, engine.inc)."""
+    The output equals the sequential decode and the number of rounds stays small (anchors at every broken link: stc007_chain_plan.h, collect_given_up_and_breaks)."""
     n = 400
     luma, _, _ = synth.stc007_frames(n, seed=77, noise_sigma=4.0)
     luma = luma.copy()

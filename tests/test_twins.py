@@ -39,6 +39,8 @@ COVERED_BY = {
     "test_emu_parity::test_emu_crowd_waits_for_the_sweeps_of_its_first_frame": _KP,                                # crowd_waits_for_first_frame
     "test_emu_parity::test_emu_lines_that_read_on_other_rungs_of_the_ladder": "test_gpu_parity::test_hip_lines_that_read_on_other_rungs_of_the_ladder",
     "test_emu_parity::test_emu_worn_tape_plain_build_and_its_reprobe": _KP,                                        # worn_plain_reprobe
+    "test_emu_parity::test_emu_schedule_of_the_tape_whose_passes_meet": _KP,                                       # pass_meets_last_30x64
+    "test_emu_parity::test_emu_every_switch_steers_what_it_steered": "test_gpu_kernel_paths::test_gpu_kernel_paths_on_a_developer_build",     # every tape under every switch
     # ---- pairs by name that are written separately (the GPU test goes through sdvpcmdecoder_amd.Engine, often on more or larger cases): named on purpose
     "test_audio::test_emu_matches_oracle": "test_audio::test_gpu_matches_oracle",
     "test_audio::test_emu_random_tapes": "test_audio::test_gpu_random_tapes",
@@ -92,7 +94,7 @@ COVERED_BY = {
     "test_pcm16::test_emu_refuses_what_the_reference_never_finishes":
         "emulator only: FE_FOREIGN is read back (pcm16_engine.inc:361, :383) after the emit kernels have written pairs and descriptors to the caller (:345)",
     # argument checks of the per-line entries: host code ahead of any device work, the same in both builds; not among the call-by-call tests twinned so far
-    "test_stc_lines::test_emu_lines_refuse_bad_arguments": "emulator only: the checks of sdv_binarize_lines are the host's, ahead of its first launch (engine.inc:1200-1207)",
+    "test_stc_lines::test_emu_lines_refuse_bad_arguments": "emulator only: the checks of sdv_binarize_lines are the host's, ahead of its first launch (engine.inc:712-719)",
     "test_pcm1_front::test_emu_argument_checks": "emulator only: the checks of sdv_pcm1_binarize_lines are the host's, ahead of its launch (pcm1_engine.inc:221-227)",
     "test_pcm16_front::test_emu_lines_argument_checks":
         "emulator only: the checks of sdv_pcm16x0_binarize_lines are the host's, ahead of its launch (pcm16_frames_engine.inc:41-47); the rows nothing is preset for "
