@@ -23,6 +23,12 @@
  *       captured frames as the video decoder delivers them (pixfmt: gray8 uyvy422 yuyv422 v210 gray10le rgb24 bgr24 rgb0 bgr0; rows
  *       src_row_stride bytes apart, frames src_h rows apart) -> sdv_ingest_frames: crop, channel, 8-bit luma, 2x doubling -> the plane the
  *       other modes read (and, on the device, the plane the frame entries take); prints `out_w out_h doubled`
+ *   decode_tape encode <in.wav> <out.luma> [pal] [16] [noctrl] [emphasis] [nocopy]
+ *       the way back: a 16-bit stereo PCM WAV file -> sdv_encode_frames -> 8-bit luma frames of an STC-007 tape (`16`: PCM-F1, 16 bit) as the
+ *       other modes read them: 720 pixels wide, data window 12 .. 708, every line of both fields (NTSC 492 rows, PAL 590; with `noctrl`, without
+ *       the control line, 490 / 588), top field first, black 30, white 200.  One frame more than the samples fill is made from no pairs: it plays
+ *       the 112 lines of interleave delay out.  `emphasis` and `nocopy` set the bits of the control block (the samples are not pre-emphasised).
+ *       Prints `n_frames width height`; `decode_tape wav <out.luma> 720 <height> <n_frames> <back.wav>` gives the samples back
  *
  * Build (host code only, any C++ compiler): g++ -std=c++17 -O2 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude examples/decode_tape.cpp
  *        -Lsdvpcmdecoder_amd -lsdvpcm_hip -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$ORIGIN/../sdvpcmdecoder_amd' (build.py: build_example).
@@ -235,6 +241,45 @@ int main(int argc, char **argv)
         rc = download(d_luma, luma_bytes, argv[11]);
         printf("%d %d %d\n", out_w, out_h, doubled);
         (void)hipFree(d_video); (void)hipFree(d_luma);
+    } else if (mode == "encode" && argc >= 4) {
+        sdv_encode_desc d; memset(&d, 0, sizeof(d));
+        d.ctrl_block = 1; d.black = 30; d.white = 200; d.width = 720; d.data_start = 12; d.data_stop = 708;
+        for (int i = 4; i < argc; i++) {
+            const std::string opt = argv[i];
+            if (opt == "pal") d.video_standard = SDV_ENC_PAL;
+            else if (opt == "16") d.resolution = SDV_ENC_16BIT;
+            else if (opt == "noctrl") d.ctrl_block = 0;
+            else if (opt == "emphasis") d.ctrl_flags |= SDV_ENC_CTRL_EMPHASIS;
+            else if (opt == "nocopy") d.ctrl_flags |= SDV_ENC_CTRL_COPY_PROHIBITED;
+            else { fprintf(stderr, "usage: see the header of examples/decode_tape.cpp\n"); return 1; }
+        }
+        size_t per_frame = 0; int lines_per_field = 0;
+        d.height = 2;                       /* (any: the geometry tells the lines of a field, the height follows from them) */
+        const int grc = sdv_encode_geometry(&d, &per_frame, &lines_per_field, NULL);
+        if (grc != SDV_OK) { fprintf(stderr, "sdv_encode_geometry = %d: %s\n", grc, sdv_last_error(NULL)); return 3; }
+        d.height = 2 * lines_per_field;
+        /* the data chunk of a RIFF/WAVE file with 16-bit stereo PCM */
+        if (!read_file(argv[2], in) || in.size() < 12 || memcmp(in.data(), "RIFF", 4) || memcmp(in.data() + 8, "WAVE", 4)) { fprintf(stderr, "cannot read %s as a WAV file\n", argv[2]); return 1; }
+        size_t at = 12, data_at = 0, data_len = 0; unsigned channels = 0, bits = 0;
+        while (at + 8 <= in.size()) {
+            const size_t len = (size_t)in[at + 4] | (size_t)in[at + 5] << 8 | (size_t)in[at + 6] << 16 | (size_t)in[at + 7] << 24;
+            if (!memcmp(in.data() + at, "fmt ", 4) && at + 8 + 16 <= in.size()) { channels = in[at + 10] | in[at + 11] << 8; bits = in[at + 22] | in[at + 23] << 8; }
+            if (!memcmp(in.data() + at, "data", 4)) { data_at = at + 8; data_len = len < in.size() - data_at ? len : in.size() - data_at; break; }
+            at += 8 + len + (len & 1);
+        }
+        if (!data_at || channels != 2 || bits != 16) { fprintf(stderr, "%s: 16-bit stereo PCM is what a tape holds\n", argv[2]); return 1; }
+        const size_t n_in = data_len / 4;
+        const int n = (int)((n_in + per_frame - 1) / per_frame) + 1;           /* ... and the frame that plays the delay out */
+        const size_t frame_bytes = (size_t)d.width * d.height;
+        int16_t *d_pcm = NULL; uint8_t *d_luma = NULL;
+        HIP_OK(hipMalloc((void **)&d_pcm, n_in * 4 + 4));
+        HIP_OK(hipMalloc((void **)&d_luma, frame_bytes * n));
+        HIP_OK(hipMemcpy(d_pcm, in.data() + data_at, n_in * 4, hipMemcpyHostToDevice));
+        SDV_OKAY(sdv_encode_frames(eng, &d, d_pcm, n_in, n, d_luma, (size_t)d.width, frame_bytes, NULL));
+        HIP_OK(hipDeviceSynchronize());
+        rc = download(d_luma, frame_bytes * n, argv[3]);
+        printf("%d %d %d\n", n, d.width, d.height);
+        (void)hipFree(d_pcm); (void)hipFree(d_luma);
     } else { fprintf(stderr, "usage: see the header of examples/decode_tape.cpp\n"); rc = 1; }
     if (d_pairs) (void)hipFree(d_pairs);
     sdv_engine_destroy(eng);

@@ -20,13 +20,14 @@
 extern "C" {
 #endif
 
-#define SDV_ABI_VERSION 8   /* 2: output capacities on sdv_binarize_frames / sdv_pcm1_binarize_lines; 3: sdv_audio_process, sdv_wav_pack, sdv_wav_header, sdv_decode_frames (additions only);
+#define SDV_ABI_VERSION 9   /* 2: output capacities on sdv_binarize_frames / sdv_pcm1_binarize_lines; 3: sdv_audio_process, sdv_wav_pack, sdv_wav_header, sdv_decode_frames (additions only);
                              * 4: sdv_pcm16x0_binarize_lines, sdv_audio_stalled, sdv_set_frame_flags, sdv_double_width, sdv_vis_render_lines (additions); the calls that used to refuse PCM-16x0 frames of the wrong size and the
                              * AudioProcessor's dead ends now follow the reference; the PCM-16x0 stitch state blob grew by conv_queue's remainder;
                              * 5: sdv_run_info grew by frames_met (at its end), sdv_binarize_lines (addition);
                              * 6: sdv_deemphasis_coeffs, sdv_set_deemphasis, sdv_reset_deemphasis, sdv_audio_deemphasis (additions only);
                              * 7: sdv_resample_taps, sdv_set_resample, sdv_reset_resample, sdv_audio_resample_pending, sdv_audio_resample_room, sdv_audio_resample (additions only);
-                             * 8: sdv_ingest_geometry, sdv_ingest_frames (additions only) */
+                             * 8: sdv_ingest_geometry, sdv_ingest_frames (additions only);
+                             * 9: sdv_encode_geometry, sdv_encode_frames, sdv_reset_encoder (additions only) */
 
 /* ---- status codes ---------------------------------------------------------------------------
  * 0..4 mirror Binarizer::LB_RET_* (binarizer.h:268-275); 16.. mirror STC007Deinterleaver::DI_RET_*
@@ -368,6 +369,67 @@ typedef struct sdv_ingest_desc {
 int sdv_ingest_geometry(const sdv_ingest_desc *d, int *out_width, int *out_height, int *doubled, size_t *src_row_bytes);
 int sdv_ingest_frames(sdv_engine *e, const sdv_ingest_desc *d, const void *src, size_t src_row_stride, size_t src_frame_stride,
                       int n_frames, uint8_t *dst, size_t dst_row_stride, size_t dst_frame_stride, void *stream);
+
+/* ---- encode: 16-bit PCM -> STC-007 / PCM-F1 video frames, on the device (no reference equivalent: the reference only reads tapes) ---------------
+ * The write side of the format the frame entries read: what goes back to a PCM-F1 / PCM-501 tape, or makes a calibration tape.
+ *   WAV -> sdv_encode_frames -> sdv_decode_frames -> the same samples.
+ * `pcm` is interleaved int16 L R, the layout sdv_wav_pack writes and a WAV file holds.  A call makes n_frames frames and consumes
+ * n_frames * *pairs_per_frame = n_frames * 2 * lpf * 3 pairs, lpf = 245 (SDV_ENC_NTSC) or 294 (SDV_ENC_PAL) data lines a field (config.h:80-81).
+ * Where n_pairs is smaller the rest is silence (zero words); pairs beyond that count are not read.  A word leaves the encoder 112 lines
+ * after it went in (the interleave), so a caller ends a tape by asking for one more frame with no pairs: that plays the delay out.
+ *
+ * Words.  Block b of the tape is its pairs 3 b .. 3 b + 2 as the six words L0 R0 L1 R1 L2 R2.
+ *   SDV_ENC_14BIT: a word is (sample >> 2) & 0x3FFF - a truncation, the inverse of getSample's << 2; dither is the caller's business.
+ *       P = the XOR of the six words; Q = T^6 L0 + T^5 R0 + T^4 L1 + T^3 R1 + T^2 L2 + T R2, T v = ((v << 1) & 0x3FFF) ^ (v & 0x2000 ? 0x0101 : 0):
+ *       the multiplication by x modulo x^14 + x^8 + 1 (stc007deinterleaver.cpp:1297-1317).
+ *   SDV_ENC_16BIT (PCM-F1): the six 16-bit words and P16, their XOR; no Q.
+ * Lines.  Data line M of the tape, counted from the reset, is line j of field F: M = F lpf + j.  Its slot k = 0 .. 7 carries word k (L0 R0 L1 R1 L2 R2
+ *   P Q) of block M - 16 k, and zero where that block lies in front of the tape.  With SDV_ENC_16BIT slots 0 .. 6 carry the upper 14 bits of the six
+ *   16-bit words and of P16, each of its own block M - 16 k, and slot 7 the two low bits of the seven 16-bit words of this same line, slot k's at
+ *   shift 12 - 2 k (stc007datablock.h:80-92).  The CRC is CRC-16/CCITT-FALSE (polynomial 0x1021, initial value 0xFFFF, no reflection, no final
+ *   XOR) over the eight 14-bit words, MSB first (stc007line.cpp:245-251); a silent line's is 0xA96A.
+ * Cells.  A line is 137 cells: 1 0 1 0, the eight words with 14 bits each MSB first, the 16 CRC bits MSB first, 0 1 1 1 1.
+ * Control line.  With ctrl_block = 1 every field is lpf + 1 lines: line 0 is the control line, the lpf data lines follow it (it replaces none
+ *   of them).  Its eight words: 0x3333 0x0CCC 0x3333 0x0CCC, ID = 0, ADDR1 = tc_index << 8 | hour << 4 | minute >> 2,
+ *   ADDR2 = (minute & 3) << 12 | second << 6 | field, CTRL = (SDV_ENC_CTRL_COPY_PROHIBITED ? 8 : 0) | (SDV_ENC_16BIT ? 2 : 0) |
+ *   (SDV_ENC_CTRL_EMPHASIS ? 0 : 1) (stc007line.h:104-152, getters stc007line.cpp:361-443); CRC and cells as for a data line.  The bit that
+ *   says "no P word" cannot be asked for.  tc_hour .. tc_field are the time code of the first field after a reset; it advances by one field per
+ *   field, carries into the seconds at 60 (NTSC) or 50 (PAL) fields, on into minutes and hours, and the hours wrap at 16.  tc_index and
+ *   ctrl_flags are taken from every call's descriptor.  (SDV_ENC_CTRL_EMPHASIS only sets the bit: pre-emphasis of the samples is the caller's.)
+ * Frame.  lines_per_field = lpf + ctrl_block.  Row 2 r of frame f shows line top_line + r of the field that is first in time (field 2 f of the
+ *   tape), row 2 r + 1 the same line of the other field; with SDV_ENC_BFF the two swap.  A row whose line does not exist (below 0, at or beyond
+ *   lines_per_field) is `black` throughout, and so is the last row of an odd height.
+ * Raster.  Pixel x of a line's row is `white` where data_start <= x < data_stop and cell ((x - data_start) * 137) / (data_stop - data_start)
+ *   (integer division) is 1, else `black`.  The window may reach past the picture on either side.
+ *
+ * State.  The engine keeps the words of the tape's last 112 blocks and the field count on the device, updated in stream order (the calls of a
+ * tape go to one HIP stream): a tape encoded in several calls equals the tape encoded in one.  sdv_engine_create and sdv_reset_encoder start a
+ * new tape.  video_standard, resolution and ctrl_block stay as they were in the first call after a reset (else SDV_ERR_BAD_ARG); geometry,
+ * levels, field order, tc_index and ctrl_flags may change from call to call.
+ *
+ * sdv_encode_frames: device pointers of any alignment; all work goes to `stream`, the call is asynchronous and reads nothing back; it runs on
+ * the engine's device whatever device is current.  Row r of frame f goes to dst + f dst_frame_stride + r dst_row_stride, `width` bytes.  Bytes of
+ * a row behind `width`, and anything else in the buffer, are not written.  Refused before any launch, the engine and the tape untouched,
+ * sdv_last_error says why: SDV_ERR_BAD_ARG for a null d, an unknown enum value or control bit, n_frames < 0 or above 2^24, width or height outside
+ * 1 .. 32768, data_stop <= data_start, white <= black, a time-code field out of range (tc_index 0 .. 63, tc_hour 0 .. 15, tc_minute and tc_second
+ * 0 .. 59, tc_field below 60 / 50), dst_row_stride < width, dst_frame_stride < (height - 1) dst_row_stride + width when n_frames > 1, strides
+ * above 4 GiB, any overlap of the pairs the call reads with the destination span; SDV_ERR_NULL_PCM for a null pcm with n_pairs > 0;
+ * SDV_ERR_NULL_VIDEO for a null dst.  n_frames == 0: SDV_OK, nothing done.  sdv_encode_geometry is host-only and needs no engine: the same codes for
+ * the same descriptor (sdv_last_error(NULL) says why); any of its output pointers may be NULL; *row_bytes = width. */
+enum { SDV_ENC_NTSC = 0, SDV_ENC_PAL = 1 };
+enum { SDV_ENC_14BIT = 0, SDV_ENC_16BIT = 1 };
+enum { SDV_ENC_TFF = 0, SDV_ENC_BFF = 1 };
+enum { SDV_ENC_CTRL_COPY_PROHIBITED = 1 << 0, SDV_ENC_CTRL_EMPHASIS = 1 << 1 };
+typedef struct sdv_encode_desc {
+    uint8_t video_standard, resolution, ctrl_block, ctrl_flags;     /* SDV_ENC_NTSC / _PAL, SDV_ENC_14BIT / _16BIT, 0 / 1, SDV_ENC_CTRL_* */
+    uint8_t field_order, black, white, _pad;                        /* SDV_ENC_TFF / _BFF; the two levels */
+    uint8_t tc_index, tc_hour, tc_minute, tc_second, tc_field, _pad2[3];
+    int32_t width, height, data_start, data_stop, top_line;
+} sdv_encode_desc;                                                   /* 36 bytes */
+int sdv_encode_geometry(const sdv_encode_desc *d, size_t *pairs_per_frame, int *lines_per_field, size_t *row_bytes);
+int sdv_encode_frames(sdv_engine *e, const sdv_encode_desc *d, const int16_t *pcm, size_t n_pairs, int n_frames,
+                      uint8_t *dst, size_t dst_row_stride, size_t dst_frame_stride, void *stream);
+int sdv_reset_encoder(sdv_engine *e);
 
 size_t sdv_records_per_frame(int height);
 /* records one sdv_binarize_frames call emits: n_frames * (height + 3), + 1 with SDV_FLAG_NEW_FILE, + height + 4 with SDV_FLAG_END_FILE */

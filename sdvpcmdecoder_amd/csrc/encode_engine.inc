@@ -1,0 +1,161 @@
+/*
+ * encode_engine.inc - host side of sdv_encode_geometry / sdv_encode_frames / sdv_reset_encoder (include/sdvpcm.h): the checks, the tape's
+ * state and the two launches of encode_device.h.  Included at the end of engine.inc, so by the one translation unit of either build.
+ */
+
+namespace rt {
+#ifndef SDV_EMU
+/* threads of the raster launch: a grid stride walks the rest (encode_raster_body).  2048 workgroups of 256, as sdv_k_ingest has them. */
+static inline uint32_t encode_threads(uint64_t items) { const uint64_t wg = (items + 255) / 256; return 256u * (uint32_t)(wg < 2048 ? wg : 2048); }
+static inline status_t launch_encode_words(const sdv::EncodeWordsArgs &a, stream_t s)
+{
+    const uint64_t threads = a.n_lines + (uint64_t)a.width + 2 * sdv::ENC_TABLE_PAD;
+    hipLaunchKernelGGL(sdv_k_encode_words, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+static inline status_t launch_encode_raster(const sdv::EncodeRasterArgs &a, uint32_t threads, stream_t s)
+{
+    hipLaunchKernelGGL(sdv_k_encode_raster, dim3(threads / 256), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+#else
+/* Few threads: every test walks the stride, with carries from slots to rows to frames (the product's launch takes a second trip only in a call
+ * of more than 2048 x 256 chunk slots: _more_than_one_trip, tests/test_encode.py). */
+static inline uint32_t encode_threads(uint64_t) { return 320; }
+static inline status_t launch_encode_words(const sdv::EncodeWordsArgs &a, stream_t)
+{
+    for (uint64_t t = 0; t < a.n_lines + (uint64_t)a.width + 2 * sdv::ENC_TABLE_PAD; t++) sdv::encode_words_body(a, t);
+    return 0;
+}
+static inline status_t launch_encode_raster(const sdv::EncodeRasterArgs &a, uint32_t threads, stream_t)
+{
+    for (uint32_t t = 0; t < threads; t++) sdv::encode_raster_body(a, t);
+    return 0;
+}
+#endif
+} // namespace rt
+
+enum { ENCODE_MAX_DIM = 32768, ENCODE_MAX_FRAMES = 1 << 24 };
+
+struct sdv_encoder {
+    bool fresh = true;                              /* no call since the engine was made or sdv_reset_encoder */
+    uint8_t video_standard = 0, resolution = 0, ctrl_block = 0;     /* of the tape: the first call's */
+    rt::DevBuf<sdv::EncodeState> d_state, d_state_next;             /* what the next call reads, what this one writes */
+    rt::DevBuf<uint32_t> d_lines;                   /* the packed lines of a call */
+    rt::DevBuf<uint8_t> d_cell_of;                  /* the cell of every x of a row, and of 16 on either side of it */
+};
+
+static void encoder_free(sdv_engine *e) { delete e->enc; e->enc = NULL; }
+
+struct EncodeGeo { int lpf, lpft; uint32_t fps; };
+
+/* what the descriptor asks for, or why it cannot be had */
+static int encode_geo(const sdv_encode_desc *d, EncodeGeo *g, std::string *why)
+{
+    if (!d) { *why = "null encode descriptor"; return SDV_ERR_BAD_ARG; }
+    if (d->video_standard > SDV_ENC_PAL) { *why = "unknown video standard"; return SDV_ERR_BAD_ARG; }
+    if (d->resolution > SDV_ENC_16BIT) { *why = "unknown resolution"; return SDV_ERR_BAD_ARG; }
+    if (d->ctrl_block > 1) { *why = "ctrl_block is 0 or 1"; return SDV_ERR_BAD_ARG; }
+    if (d->ctrl_flags & ~(SDV_ENC_CTRL_COPY_PROHIBITED | SDV_ENC_CTRL_EMPHASIS)) { *why = "unknown control bits (the P word cannot be left out)"; return SDV_ERR_BAD_ARG; }
+    if (d->field_order > SDV_ENC_BFF) { *why = "unknown field order"; return SDV_ERR_BAD_ARG; }
+    if (d->width <= 0 || d->height <= 0 || d->width > ENCODE_MAX_DIM || d->height > ENCODE_MAX_DIM) {
+        *why = "frame size outside 1.." + std::to_string((int)ENCODE_MAX_DIM); return SDV_ERR_BAD_ARG;
+    }
+    if (d->data_stop <= d->data_start) { *why = "data_stop is not behind data_start"; return SDV_ERR_BAD_ARG; }
+    if (d->white <= d->black) { *why = "white is not above black"; return SDV_ERR_BAD_ARG; }
+    g->lpf = d->video_standard == SDV_ENC_PAL ? 294 : 245;          /* config.h:80-81 */
+    g->lpft = g->lpf + d->ctrl_block;
+    g->fps = d->video_standard == SDV_ENC_PAL ? 50 : 60;
+    if (d->tc_index > 63 || d->tc_hour > 15 || d->tc_minute > 59 || d->tc_second > 59 || d->tc_field >= g->fps) { *why = "time code out of range"; return SDV_ERR_BAD_ARG; }
+    return SDV_OK;
+}
+
+extern "C" {
+
+int sdv_encode_geometry(const sdv_encode_desc *d, size_t *pairs_per_frame, int *lines_per_field, size_t *row_bytes)
+{
+    EncodeGeo g; std::string why;
+    const int rc = encode_geo(d, &g, &why);
+    if (rc != SDV_OK) { set_error(NULL, "sdv_encode_geometry: " + why); return rc; }
+    if (pairs_per_frame) *pairs_per_frame = (size_t)g.lpf * 6;
+    if (lines_per_field) *lines_per_field = g.lpft;
+    if (row_bytes) *row_bytes = (size_t)d->width;
+    return SDV_OK;
+}
+
+int sdv_reset_encoder(sdv_engine *e)
+{
+    if (!e) return SDV_ERR_BAD_ARG;
+    if (e->enc) e->enc->fresh = true;
+    return SDV_OK;
+}
+
+int sdv_encode_frames(sdv_engine *e, const sdv_encode_desc *d, const int16_t *pcm, size_t n_pairs, int n_frames,
+                      uint8_t *dst, size_t dst_row_stride, size_t dst_frame_stride, void *stream)
+{
+    if (!e) return SDV_ERR_BAD_ARG;
+    if (n_frames < 0) { set_error(e, "negative frame count"); return SDV_ERR_BAD_ARG; }
+    if (n_frames == 0) return SDV_OK;
+    if (n_frames > ENCODE_MAX_FRAMES) { set_error(e, "more than " + std::to_string((int)ENCODE_MAX_FRAMES) + " frames in one call"); return SDV_ERR_BAD_ARG; }
+    EncodeGeo g; std::string why;
+    const int rc = encode_geo(d, &g, &why);
+    if (rc != SDV_OK) { set_error(e, why); return rc; }
+    if (!pcm && n_pairs > 0) { set_error(e, "null pcm"); return SDV_ERR_NULL_PCM; }
+    if (!dst) { set_error(e, "null video"); return SDV_ERR_NULL_VIDEO; }
+    const size_t max_stride = (size_t)1 << 32;          /* (keeps the spans below inside 64 bits) */
+    if (dst_row_stride > max_stride || (n_frames > 1 && dst_frame_stride > max_stride)) { set_error(e, "stride above 4 GiB"); return SDV_ERR_BAD_ARG; }
+    const size_t dst_frame = (size_t)(d->height - 1) * dst_row_stride + (size_t)d->width;
+    if (dst_row_stride < (size_t)d->width) { set_error(e, "dst_row_stride smaller than the " + std::to_string(d->width) + " bytes of a row"); return SDV_ERR_BAD_ARG; }
+    if (n_frames > 1 && dst_frame_stride < dst_frame) { set_error(e, "dst_frame_stride smaller than one frame"); return SDV_ERR_BAD_ARG; }
+    const uint64_t n_fields = 2 * (uint64_t)n_frames, n_data = n_fields * (uint64_t)g.lpf, n_lines = n_fields * (uint64_t)g.lpft;
+    const size_t used_pairs = n_pairs < 3 * n_data ? n_pairs : (size_t)(3 * n_data);       /* the pairs the call reads */
+    const uintptr_t s0 = (uintptr_t)pcm, s1 = s0 + 4 * used_pairs;
+    const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (size_t)(n_frames - 1) * dst_frame_stride + dst_frame;
+    if (used_pairs && s0 < d1 && d0 < s1) { set_error(e, "pcm and destination overlap"); return SDV_ERR_BAD_ARG; }
+    sdv_encoder *t = e->enc;
+    if (t && !t->fresh && (t->video_standard != d->video_standard || t->resolution != d->resolution || t->ctrl_block != d->ctrl_block)) {
+        set_error(e, "video standard, resolution and control block stay as the tape began: sdv_reset_encoder starts another tape"); return SDV_ERR_BAD_ARG;
+    }
+    SDV_ON_DEVICE(e);
+    if (!t) t = e->enc = new sdv_encoder();
+    RT_CHECK(rt::reserve_all(1, 1, t->d_state, t->d_state_next));
+    RT_CHECK(t->d_lines.reserve((size_t)n_lines * sdv::ENC_REC_DWORDS));
+    RT_CHECK(t->d_cell_of.reserve((size_t)d->width + 2 * sdv::ENC_TABLE_PAD, ENCODE_MAX_DIM + 2 * sdv::ENC_TABLE_PAD));
+    const rt::stream_t s = (rt::stream_t)stream;
+
+    sdv::EncodeWordsArgs w;
+    w.pcm = (const uint8_t *)pcm; w.n_pairs = used_pairs;
+    w.st_in = t->d_state; w.st_out = t->d_state_next;
+    w.lines = t->d_lines;
+    w.cell_of = t->d_cell_of; w.width = d->width; w.data_start = d->data_start; w.span = (int64_t)d->data_stop - (int64_t)d->data_start;
+    w.n_lines = n_lines; w.n_data = n_data; w.lpf = g.lpf; w.lpft = g.lpft;
+    w.fps = g.fps; w.tc_wrap = 16u * 3600u * g.fps;
+    w.tc0 = (((uint32_t)d->tc_hour * 60u + d->tc_minute) * 60u + d->tc_second) * g.fps + d->tc_field;
+    w.addr1_index = (uint16_t)(d->tc_index << 8);
+    /* CTRL_COPY_MASK 8, CTRL_EN_Q_MASK 2 (set: no Q word, 16 bit), CTRL_EMPH_MASK 1 (set: no emphasis), stc007line.h:143-152 */
+    w.ctrl_word = (uint16_t)((d->ctrl_flags & SDV_ENC_CTRL_COPY_PROHIBITED ? 8 : 0) | (d->resolution == SDV_ENC_16BIT ? 2 : 0) | (d->ctrl_flags & SDV_ENC_CTRL_EMPHASIS ? 0 : 1));
+    w.ctrl = d->ctrl_block; w.res16 = d->resolution == SDV_ENC_16BIT; w.fresh = t->fresh;
+    RT_CHECK(rt::launch_encode_words(w, s));
+
+    sdv::EncodeRasterArgs a;
+    a.lines = t->d_lines; a.cell_of = t->d_cell_of.p + sdv::ENC_TABLE_PAD;
+    a.dst = dst; a.dst_row_stride = dst_row_stride; a.dst_frame_stride = dst_frame_stride;
+    a.n_frames = n_frames; a.width = d->width; a.height = d->height; a.line_rows = d->height & ~1;
+    a.lpft = g.lpft; a.bff = d->field_order == SDV_ENC_BFF;
+    /* any top_line at or beyond these bounds leaves no row with a line, as the bound itself does: no overflow in the kernel */
+    a.top_line = d->top_line < -ENCODE_MAX_DIM ? -ENCODE_MAX_DIM : d->top_line > g.lpft ? g.lpft : d->top_line;
+    a.black4 = 0x01010101u * d->black; a.white4 = 0x01010101u * d->white;
+    /* cells 15 pixels apart are at most 15 * 137 / span, rounded up, apart, and a step more at a window edge: beyond 31 the raster's window does not hold them */
+    a.narrow = (15 * (int64_t)sdv::ENC_CELLS) / w.span + 2 > 31;
+    a.slots = (d->width + 30) / 16;
+    const uint32_t threads = rt::encode_threads((uint64_t)n_frames * (uint64_t)d->height * (uint64_t)a.slots);
+    const uint32_t rows = threads / (uint32_t)a.slots;
+    a.step_c = (int)(threads % (uint32_t)a.slots); a.step_r = (int)(rows % (uint32_t)d->height); a.step_f = (int)(rows / (uint32_t)d->height);
+    RT_CHECK(rt::launch_encode_raster(a, threads, s));
+
+    t->d_state.swap(t->d_state_next);
+    t->video_standard = d->video_standard; t->resolution = d->resolution; t->ctrl_block = d->ctrl_block; t->fresh = false;
+    return SDV_OK;
+}
+
+} /* extern "C" */

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "ingest_device.h"          /* sdv_k_ingest (sdv_ingest_frames, ingest_engine.inc) */
+#include "encode_device.h"          /* sdv_k_encode_words, sdv_k_encode_raster (sdv_encode_frames, encode_engine.inc) */
 
 /* Developer aids (scheduler traces, cycle stamps, launch-shape overrides) are read from the environment only in builds made with
  * -DSDV_DEV_AIDS (build.py: SDVPCM_DEV_AIDS=1, and the test-only emulator build); the product library does not look at the environment. */
@@ -366,12 +367,14 @@ struct sdv_pcm1_stitcher;           /* PCM-1 back half, pcm1_engine.inc */
 struct sdv_pcm16_stitcher;          /* PCM-16x0 back half, pcm16_engine.inc */
 struct sdv_audio;                   /* AudioProcessor, audio_engine.inc */
 struct sdv_vis;                     /* visualiser canvases, vis_engine.inc */
+struct sdv_encoder;                 /* the tape sdv_encode_frames writes, encode_engine.inc */
 struct sdv_engine;
 static void stitcher_free(sdv_engine *e);
 static void pcm1_free(sdv_engine *e);
 static void pcm16_free(sdv_engine *e);
 static void audio_free(sdv_engine *e);
 static void vis_free(sdv_engine *e);
+static void encoder_free(sdv_engine *e);
 struct sdv_engine {
     int device = 0;
     std::string last_error;
@@ -418,6 +421,7 @@ struct sdv_engine {
     sdv_pcm16_stitcher *pcm16 = NULL;
     sdv_audio *audio = NULL;
     sdv_vis *vis = NULL;
+    sdv_encoder *enc = NULL;
 #ifndef SDV_EMU
     hipEvent_t ev0, ev1;
     bool have_events = false;
@@ -495,6 +499,7 @@ void sdv_engine_destroy(sdv_engine *e)
     pcm16_free(e);
     audio_free(e);
     vis_free(e);
+    encoder_free(e);
 #ifndef SDV_EMU
     if (e->bounce.p) (void)hipHostFree(e->bounce.p);
 #endif
@@ -791,3 +796,4 @@ int sdv_deinterleave_blocks(sdv_engine *e, const sdv_deint_line *lines, size_t n
 
 #include "stc007_frames_engine.inc"  /* sdv_binarize_frames */
 #include "ingest_engine.inc"         /* sdv_ingest_geometry, sdv_ingest_frames */
+#include "encode_engine.inc"         /* sdv_encode_geometry, sdv_encode_frames, sdv_reset_encoder */

@@ -42,6 +42,10 @@ PIX_FORMATS = {"gray8": PIX_GRAY8, "uyvy422": PIX_UYVY422, "yuyv422": PIX_YUYV42
                "rgb24": PIX_RGB24, "bgr24": PIX_BGR24, "rgb0": PIX_RGB0, "bgr0": PIX_BGR0}
 COLOR_BW, COLOR_R, COLOR_G, COLOR_B = 0, 1, 2, 3       # SDV_COLOR_* (vid_preset_t::COLOR_*)
 INGEST_DOUBLE_OFF, INGEST_DOUBLE_ON, INGEST_DOUBLE_AUTO = 0, 1, 2
+ENC_NTSC, ENC_PAL = 0, 1                               # SDV_ENC_*
+ENC_14BIT, ENC_16BIT = 0, 1
+ENC_TFF, ENC_BFF = 0, 1
+ENC_CTRL_COPY_PROHIBITED, ENC_CTRL_EMPHASIS = 1, 2
 VIS_STC007_LINES, VIS_PCM1_LINES, VIS_PCM16X0_LINES, VIS_STC007_BLOCKS_NTSC, VIS_STC007_BLOCKS_PAL, VIS_STC007_ASM_NTSC, VIS_STC007_ASM_PAL = 0, 1, 2, 3, 4, 5, 6   # SDV_VIS_*
 
 
@@ -62,6 +66,18 @@ class IngestDesc(C.Structure):
 
 
 assert C.sizeof(IngestDesc) == 20
+
+
+class EncodeDesc(C.Structure):
+    """sdv_encode_desc"""
+    _fields_ = [("video_standard", C.c_uint8), ("resolution", C.c_uint8), ("ctrl_block", C.c_uint8), ("ctrl_flags", C.c_uint8),
+                ("field_order", C.c_uint8), ("black", C.c_uint8), ("white", C.c_uint8), ("_pad", C.c_uint8),
+                ("tc_index", C.c_uint8), ("tc_hour", C.c_uint8), ("tc_minute", C.c_uint8), ("tc_second", C.c_uint8), ("tc_field", C.c_uint8),
+                ("_pad2", C.c_uint8 * 3),
+                ("width", C.c_int32), ("height", C.c_int32), ("data_start", C.c_int32), ("data_stop", C.c_int32), ("top_line", C.c_int32)]
+
+
+assert C.sizeof(EncodeDesc) == 36
 
 
 class DeintSettings(C.Structure):
@@ -150,6 +166,9 @@ def load_library(path: str | None = None):
     lib.sdv_double_width.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.sdv_ingest_geometry.argtypes = [C.POINTER(IngestDesc), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
     lib.sdv_ingest_frames.argtypes = [C.c_void_p, C.POINTER(IngestDesc), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+    lib.sdv_encode_geometry.argtypes = [C.POINTER(EncodeDesc), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
+    lib.sdv_encode_frames.argtypes = [C.c_void_p, C.POINTER(EncodeDesc), C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+    lib.sdv_reset_encoder.argtypes = [C.c_void_p]
     lib.sdv_vis_canvas_size.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.sdv_vis_reset.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.sdv_vis_render_lines.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
@@ -386,6 +405,42 @@ class Engine:
         self._check(self.lib.sdv_ingest_frames(self._h, C.byref(desc), C.c_void_p(src.data_ptr()), src.stride(1), src.stride(0) if n > 1 else 0, n,
                                                C.c_void_p(out.data_ptr()), ow, oh * ow, sptr))
         return out, doubled
+
+    def encode_geometry(self, desc: EncodeDesc):
+        """sdv_encode_geometry: (pairs a frame consumes, lines per field, bytes of a row) of a descriptor; host only."""
+        pairs, lines, rb = C.c_size_t(0), C.c_int(0), C.c_size_t(0)
+        rc = self.lib.sdv_encode_geometry(C.byref(desc), C.byref(pairs), C.byref(lines), C.byref(rb))
+        if rc != 0:
+            raise RuntimeError(f"sdvpcm error {rc}: " + self.lib.sdv_last_error(None).decode())
+        return pairs.value, lines.value, rb.value
+
+    def encode_frames(self, pcm, n_frames: int, standard="ntsc", bits: int = 14, ctrl_block: bool = False, ctrl_flags: int = 0, bff: bool = False,
+                      width: int = 720, height: int = 486, data_start: int = 12, data_stop=None, top_line: int = 0, black: int = 30, white: int = 200,
+                      time_code=(0, 0, 0, 0, 0), stream=None):
+        """sdv_encode_frames: the next n_frames frames of the tape this engine writes -> (n_frames, height, width) uint8 CUDA tensor.
+        pcm: torch.int16 CUDA tensor (pairs, 2), interleaved L R; a frame consumes encode_geometry()[0] pairs, pairs that lack are silence (end a
+        tape with one frame more from an empty tensor: the interleave delay is played out).  standard: "ntsc" / "pal" or an ENC_* value; bits 14
+        or 16; time_code (index, hour, minute, second, field) of the first field after reset_encoder; data_stop defaults to width - 12."""
+        import torch
+        if not (pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous() and (pcm.dim() == 2 and pcm.shape[1] == 2 or pcm.numel() == 0)):
+            raise ValueError("pcm must be a contiguous torch.int16 CUDA tensor of shape (pairs, 2)")
+        std = {"ntsc": ENC_NTSC, "pal": ENC_PAL}[standard] if isinstance(standard, str) else int(standard)
+        if bits not in (14, 16):
+            raise ValueError("bits is 14 or 16")
+        desc = EncodeDesc(std, ENC_16BIT if bits == 16 else ENC_14BIT, int(bool(ctrl_block)), ctrl_flags, ENC_BFF if bff else ENC_TFF, black, white, 0,
+                          time_code[0], time_code[1], time_code[2], time_code[3], time_code[4], (C.c_uint8 * 3)(), width, height, data_start,
+                          width - 12 if data_stop is None else data_stop, top_line)
+        self.encode_geometry(desc)
+        out = torch.empty((n_frames, height, width), dtype=torch.uint8, device=pcm.device)
+        n_pairs = pcm.numel() // 2
+        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else C.c_void_p(torch.cuda.current_stream(pcm.device).cuda_stream)
+        self._check(self.lib.sdv_encode_frames(self._h, C.byref(desc), C.c_void_p(pcm.data_ptr()) if n_pairs else None, n_pairs, n_frames,
+                                               C.c_void_p(out.data_ptr()), width, height * width, sptr))
+        return out
+
+    def reset_encoder(self):
+        """sdv_reset_encoder: the next encode_frames call starts a new tape."""
+        self._check(self.lib.sdv_reset_encoder(self._h))
 
     # ---- visualiser feed (RenderPCM's canvas of binarized lines) ----
     def vis_canvas_size(self, kind: int):

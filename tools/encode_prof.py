@@ -1,0 +1,100 @@
+"""sdv_encode_frames against a hipMemsetAsync of the bytes it writes (the floor of a write-only pass) and against synth.stc007_frames_torch, which
+made such batches until now: BASELINE's batch of 10 000 NTSC frames (720 x 486), 14 bit with the control block, resident; timed between HIP events
+on the engine's stream, 3 calls of warm-up, median of 20, the calls of a comparison alternating in one process.
+usage: encode_prof.py [n_frames] [reps] [--out FILE]
+  -> one JSON line (also written to FILE).  What the figures mean is prose in profiles/encode_notes.md, written by whoever ran the tool.
+The share of the raster kernel is taken from a call with the same frames and a picture of 1 x 1: its words step is the same, its raster step is
+10 000 bytes."""
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from sdvpcmdecoder_amd import Engine, EncodeDesc, synth  # noqa: E402
+
+W, H = 720, 486
+
+
+def timed(fns, reps, warmup=3):
+    """the calls of `fns` in turn, reps times -> [(median ms, min ms)] in their order"""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    times = [[] for _ in fns]
+    for _ in range(reps):
+        for k, fn in enumerate(fns):
+            t0.record(); fn(); t1.record(); t1.synchronize()
+            times[k].append(t0.elapsed_time(t1))
+    return [(float(np.median(t)), float(np.min(t))) for t in times]
+
+
+def main():
+    argv = sys.argv[1:]
+    out_path = None
+    if "--out" in argv:
+        at = argv.index("--out")
+        out_path = argv[at + 1]
+        del argv[at:at + 2]
+    n = int(argv[0]) if len(argv) > 0 else 10_000
+    reps = int(argv[1]) if len(argv) > 1 else 20
+    eng = Engine(0)
+    lib, h = eng.lib, eng._h
+    sptr = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemsetAsync.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
+    nbytes = n * H * W
+    pcm = torch.randint(-32768, 32768, (n * 1470, 2), dtype=torch.int16, device="cuda")
+    dst = torch.empty(nbytes + 64, dtype=torch.uint8, device="cuda")
+
+    # what it makes is what the repository's generator makes: two frames without the control block against synth.stc007_frames on the same words
+    two = eng.encode_frames(pcm[:2 * 1470], 2, height=H, top_line=2).cpu().numpy()
+    words = (pcm[:2 * 1470].cpu().numpy().view(np.uint16).reshape(-1, 6) >> 2).astype(np.uint32)
+    assert np.array_equal(two, synth.stc007_frames(2, audio=words, height=H, cut_top=2)[0])
+    eng.reset_encoder()
+
+    def encode(width=W, height=H, at=0):
+        d = EncodeDesc(0, 0, 1, 0, 0, 30, 200, 0, 0, 0, 0, 0, 0, (C.c_uint8 * 3)(), width, height, 12, 708, 2)
+
+        def fn():
+            rc = lib.sdv_encode_frames(h, C.byref(d), C.c_void_p(pcm.data_ptr()), n * 1470, n, C.c_void_p(dst.data_ptr() + at), width, width * height, sptr)
+            assert rc == 0, lib.sdv_last_error(h)
+        return fn
+
+    def fill():
+        assert hip.hipMemsetAsync(dst.data_ptr(), 30, nbytes, sptr) == 0
+
+    p = torch.cuda.get_device_properties(0)
+    res = {"n_frames": n, "reps": reps, "device": torch.cuda.get_device_name(0), "arch": p.gcnArchName, "cus": p.multi_processor_count, "bytes": nbytes}
+    (e_ms, e_min), (f_ms, f_min), (w_ms, w_min), (m_ms, m_min) = timed([encode(), fill, encode(1, 1), encode(at=3)], reps)
+    res.update({"encode_ms": e_ms, "encode_ms_min": e_min, "encode_gbps": nbytes / e_ms / 1e6, "memset_ms": f_ms, "memset_ms_min": f_min,
+                "memset_gbps": nbytes / f_ms / 1e6, "encode_over_memset": e_ms / f_ms, "words_only_ms": w_ms, "words_only_ms_min": w_min,
+                "raster_share": 1.0 - w_ms / e_ms, "raster_over_memset": (e_ms - w_ms) / f_ms,
+                "dst_plus_3_ms": m_ms, "dst_plus_3_ms_min": m_min, "dst_plus_3_over_aligned": m_ms / e_ms})
+    del dst
+    torch.cuda.empty_cache()
+    # the generator of the benchmark's batch, on the same box: once at 256 frames to warm it up, then the whole tape against a host clock
+    synth.stc007_frames_torch(256, seed=1)
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(2):
+        t0 = time.perf_counter()
+        luma, _ = synth.stc007_frames_torch(n, seed=1)
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1e3)
+        del luma
+    res.update({"synth_torch_ms": min(times), "synth_torch_over_encode": min(times) / e_ms})
+    line = json.dumps(res)
+    print(line)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        open(out_path, "w").write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
