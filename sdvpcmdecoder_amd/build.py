@@ -17,9 +17,9 @@ HIP_LIB = os.path.join(PKG, "libsdvpcm_hip.so")
 
 # the sources a kernel is compiled from and launched by (its device header, the engine that configures the launch, the C-ABI)
 KERNEL_SOURCES = {
-    "sdv_k_stc007_frames": ("stc007_device.h", "stc007_sweep_device.h", "engine.inc", "stc007_chain_plan.h", "stc007_frames_engine.inc"),
-    "sdv_k_stc007_sweep": ("stc007_device.h", "stc007_sweep_device.h", "engine.inc", "stc007_chain_plan.h", "stc007_frames_engine.inc"),
-    "sdv_k_hist_carry": ("stc007_device.h", "engine.inc", "stc007_chain_plan.h", "stc007_frames_engine.inc"),
+    "sdv_k_stc007_frames": ("stc007_device.h", "stc007_sweep_device.h", "engine.inc", "runtime.inc", "stc007_chain_plan.h", "stc007_frames_engine.inc"),
+    "sdv_k_stc007_sweep": ("stc007_device.h", "stc007_sweep_device.h", "engine.inc", "runtime.inc", "stc007_chain_plan.h", "stc007_frames_engine.inc"),
+    "sdv_k_hist_carry": ("stc007_device.h", "engine.inc", "runtime.inc", "stc007_chain_plan.h", "stc007_frames_engine.inc"),
     "sdv_k_pcm1_lines": ("stc007_device.h", "pcm1_bin_device.h", "pcm1_engine.inc"),
     "sdv_k_pcm1_frames": ("pcm1_stitch_device.h", "pcm1_engine.inc"),
     "sdv_k_pcm1_frames_bin": ("stc007_device.h", "pcm1_bin_device.h", "pcm1_frames_device.h", "markerless_chain_device.h", "markerless_frames_engine.inc", "pcm1_frames_engine.inc"),

@@ -91,7 +91,7 @@ static int audio_process_span(sdv_engine *e, sdv_audio *t, const sdv_sample_pair
     /* 1. the tags */
     std::vector<uint64_t> tags;
     if (n_pairs > 0) {
-        RT_CHECK(rt::dzero(t->d_count, 4 * sizeof(uint32_t), s));
+        RT_CHECK(rt::dfill_bytes(t->d_count, 0, 4 * sizeof(uint32_t), s));
         sdva::TagArgs ta; ta.pairs = pairs; ta.n = (uint32_t)n_pairs; ta.count = t->d_count; ta.list = t->d_tags;
         RT_LAUNCH64(sdv_k_ap_tags, (n_pairs + 1023) / 1024, ta, s);
         uint32_t n_tags = 0;
@@ -172,9 +172,9 @@ static int audio_process_span(sdv_engine *e, sdv_audio *t, const sdv_sample_pair
         RT_CHECK(t->d_wins.reserve(n_slots, n_slots + n_slots / 8 + 64));
         RT_CHECK(t->d_win_base.reserve(n_st + 1, n_st + 1 + n_st / 2 + 16));
         RT_CHECK(rt::h2d(t->d_win_base, win_base.data(), (n_st + 1) * sizeof(uint32_t), s));
-        if (n_pairs == 0) RT_CHECK(rt::dzero(t->d_count + 1, sizeof(uint32_t), s));    /* has_mi (zeroed with the tag counter otherwise) */
+        if (n_pairs == 0) RT_CHECK(rt::dfill_bytes(t->d_count + 1, 0, sizeof(uint32_t), s));    /* has_mi (zeroed with the tag counter otherwise) */
         RT_CHECK(rt::h2d(t->d_st, st.data(), n_st * sizeof(sdva::Stretch), s));
-        RT_CHECK(rt::dzero(t->d_bad2, n2 * 64, s));
+        RT_CHECK(rt::dfill_bytes(t->d_bad2, 0, n2 * 64, s));
 
         /* 3. W and the bitmap */
         sdva::PrepArgs pa; pa.pairs = pairs; pa.carry = t->d_carry; pa.st = t->d_st; pa.n_st = (uint32_t)n_st; pa.total_w = total_w; pa.w = work;
@@ -195,7 +195,7 @@ static int audio_process_span(sdv_engine *e, sdv_audio *t, const sdv_sample_pair
             RT_CHECK(rt::d2h(res.data(), t->d_res, n_st * sizeof(sdva::StretchResult), s));
         } else {                                        /* stop() on a stalled worker: no turn runs, the window leaves as it is */
             memset(res.data(), 0, n_st * sizeof(sdva::StretchResult));
-            RT_CHECK(rt::dzero(t->d_res, n_st * sizeof(sdva::StretchResult), s));
+            RT_CHECK(rt::dfill_bytes(t->d_res, 0, n_st * sizeof(sdva::StretchResult), s));
         }
         size_t listed = 0;
         for (size_t k = 0; k < n_st; k++) {

@@ -3,38 +3,6 @@
  * state and the two launches of encode_device.h.  Included at the end of engine.inc, so by the one translation unit of either build.
  */
 
-namespace rt {
-#ifndef SDV_EMU
-/* threads of the raster launch: a grid stride walks the rest (encode_raster_body).  2048 workgroups of 256, as sdv_k_ingest has them. */
-static inline uint32_t encode_threads(uint64_t items) { const uint64_t wg = (items + 255) / 256; return 256u * (uint32_t)(wg < 2048 ? wg : 2048); }
-static inline status_t launch_encode_words(const sdv::EncodeWordsArgs &a, stream_t s)
-{
-    const uint64_t threads = a.n_lines + (uint64_t)a.width + 2 * sdv::ENC_TABLE_PAD;
-    hipLaunchKernelGGL(sdv_k_encode_words, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-static inline status_t launch_encode_raster(const sdv::EncodeRasterArgs &a, uint32_t threads, stream_t s)
-{
-    hipLaunchKernelGGL(sdv_k_encode_raster, dim3(threads / 256), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-#else
-/* Few threads: every test walks the stride, with carries from slots to rows to frames (the product's launch takes a second trip only in a call
- * of more than 2048 x 256 chunk slots: _more_than_one_trip, tests/test_encode.py). */
-static inline uint32_t encode_threads(uint64_t) { return 320; }
-static inline status_t launch_encode_words(const sdv::EncodeWordsArgs &a, stream_t)
-{
-    for (uint64_t t = 0; t < a.n_lines + (uint64_t)a.width + 2 * sdv::ENC_TABLE_PAD; t++) sdv::encode_words_body(a, t);
-    return 0;
-}
-static inline status_t launch_encode_raster(const sdv::EncodeRasterArgs &a, uint32_t threads, stream_t)
-{
-    for (uint32_t t = 0; t < threads; t++) sdv::encode_raster_body(a, t);
-    return 0;
-}
-#endif
-} // namespace rt
-
 enum { ENCODE_MAX_DIM = 32768, ENCODE_MAX_FRAMES = 1 << 24 };
 
 struct sdv_encoder {
@@ -135,7 +103,8 @@ int sdv_encode_frames(sdv_engine *e, const sdv_encode_desc *d, const int16_t *pc
     /* CTRL_COPY_MASK 8, CTRL_EN_Q_MASK 2 (set: no Q word, 16 bit), CTRL_EMPH_MASK 1 (set: no emphasis), stc007line.h:143-152 */
     w.ctrl_word = (uint16_t)((d->ctrl_flags & SDV_ENC_CTRL_COPY_PROHIBITED ? 8 : 0) | (d->resolution == SDV_ENC_16BIT ? 2 : 0) | (d->ctrl_flags & SDV_ENC_CTRL_EMPHASIS ? 0 : 1));
     w.ctrl = d->ctrl_block; w.res16 = d->resolution == SDV_ENC_16BIT; w.fresh = t->fresh;
-    RT_CHECK(rt::launch_encode_words(w, s));
+    const uint64_t word_threads = n_lines + (uint64_t)d->width + 2 * sdv::ENC_TABLE_PAD;      /* a line or an entry of the cell table each */
+    RT_CHECK(RT_LAUNCH_ITEMS(sdv_k_encode_words, sdv::encode_words_body, 0, word_threads, 256, s, w));
 
     sdv::EncodeRasterArgs a;
     a.lines = t->d_lines; a.cell_of = t->d_cell_of.p + sdv::ENC_TABLE_PAD;
@@ -148,10 +117,11 @@ int sdv_encode_frames(sdv_engine *e, const sdv_encode_desc *d, const int16_t *pc
     /* cells 15 pixels apart are at most 15 * 137 / span, rounded up, apart, and a step more at a window edge: beyond 31 the raster's window does not hold them */
     a.narrow = (15 * (int64_t)sdv::ENC_CELLS) / w.span + 2 > 31;
     a.slots = (d->width + 30) / 16;
-    const uint32_t threads = rt::encode_threads((uint64_t)n_frames * (uint64_t)d->height * (uint64_t)a.slots);
-    const uint32_t rows = threads / (uint32_t)a.slots;
-    a.step_c = (int)(threads % (uint32_t)a.slots); a.step_r = (int)(rows % (uint32_t)d->height); a.step_f = (int)(rows / (uint32_t)d->height);
-    RT_CHECK(rt::launch_encode_raster(a, threads, s));
+    /* threads of the raster launch: a grid stride walks the rest (encode_raster_body) */
+    const uint32_t threads = rt::grid_stride_threads((uint64_t)n_frames * (uint64_t)d->height * (uint64_t)a.slots);
+    const rt::StrideSteps st = rt::stride_steps(threads, (uint32_t)d->height, (uint32_t)a.slots);
+    a.step_f = st.step_f; a.step_r = st.step_r; a.step_c = st.step_c;
+    RT_CHECK(RT_LAUNCH_ITEMS(sdv_k_encode_raster, sdv::encode_raster_body, 0u, threads, 256, s, a));
 
     t->d_state.swap(t->d_state_next);
     t->video_standard = d->video_standard; t->resolution = d->resolution; t->ctrl_block = d->ctrl_block; t->fresh = false;

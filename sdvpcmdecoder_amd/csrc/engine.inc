@@ -4,7 +4,9 @@
  * Included by exactly one translation unit per build:
  *   - sdvpcm_hip.hip   (product; rt:: = HIP runtime, kernels launched on the GPU)
  *   - tests/emu/emu_engine.cpp (tests only; rt:: = malloc/memcpy + the SIMT emulator)
- * so that the chain-speculation logic below is the same code in both.
+ * so that the chain-speculation logic below is the same code in both.  What differs between the two - memory, copies, kernel launches, events,
+ * streams, the launch sizes - is namespace rt in runtime.inc; this file and the engines behind it name the build only for the __global__ wrappers
+ * of the kernels defined here, the device probe of sdv_engine_create and sdv_debug_k1_cycles.
  *
  * Chain speculation (DESIGN.md): the reference decodes a stream strictly line after line because
  * every good line re-tunes the binarizer for the next one (videotodigital.cpp:1369).  All of that
@@ -31,6 +33,7 @@
 
 #include "ingest_device.h"          /* sdv_k_ingest (sdv_ingest_frames, ingest_engine.inc) */
 #include "encode_device.h"          /* sdv_k_encode_words, sdv_k_encode_raster (sdv_encode_frames, encode_engine.inc) */
+#include "runtime.inc"              /* namespace rt: memory, copies, launches, events and streams, for either build */
 
 /* Developer aids (scheduler traces, cycle stamps, launch-shape overrides) are read from the environment only in builds made with
  * -DSDV_DEV_AIDS (build.py: SDVPCM_DEV_AIDS=1, and the test-only emulator build); the product library does not look at the environment. */
@@ -138,228 +141,23 @@ __global__ void sdv_k_anchor(sdv::AnchorArgs a)
 }
 #endif
 
-/* ---- runtime shim ---------------------------------------------------------------------------- */
-namespace rt {
-#ifndef SDV_EMU
-typedef hipStream_t stream_t;
-static inline const char *err_str(hipError_t e) { return hipGetErrorString(e); }
-typedef hipError_t status_t;
-static const status_t OK = hipSuccess;
-static inline hipError_t dmalloc(void **p, size_t n) { return hipMalloc(p, n); }
-static inline hipError_t dfree(void *p) { return hipFree(p); }
-static inline hipError_t hpin(void **p, size_t n) { return hipHostMalloc(p, n, hipHostMallocDefault); }      /* page-locked host memory: copies into it are asynchronous */
-static inline hipError_t hunpin(void *p) { return hipHostFree(p); }
-static inline hipError_t h2d(void *d, const void *h, size_t n, stream_t s) { return hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, s); }
-/* Synchronous read-back.  A copy into pageable memory costs ~35 us whatever its size (the runtime stages it); the counts, flags and states
- * the schedulers read several times per call go through a page-locked bounce buffer instead (~12 us) - one per host thread that ever reads
- * back (engines of different threads do not wait for each other), 1 MB, kept for the life of the process. */
-enum { BOUNCE_BYTES = 1 << 20 };
-/* The buffer belongs to the engine whose entry point is running on this thread (SDV_ON_DEVICE names it; allocated on first use under that engine's
- * device, freed by sdv_engine_destroy): host programs that call from short-lived threads leave nothing pinned behind. */
-struct BounceSlot { void *p; bool tried; };
-static thread_local BounceSlot *tls_bounce_slot = NULL;
-struct BounceScope {
-    BounceSlot *prev;
-    explicit BounceScope(BounceSlot *slot) : prev(tls_bounce_slot) { tls_bounce_slot = slot; }
-    ~BounceScope() { tls_bounce_slot = prev; }
-};
-static inline void *bounce()
+/* ---- launches of this file's kernels (runtime.inc: the two ways a kernel is launched) --------------- */
+/* The frame kernel's builds: lean, the one that settles its sweeps itself (a small round: the sweeps it misses are settled while it runs), with trajectory
+ * snapshots, without (no snapshots in this call: sdv_engine::plain_general).  dev_count_frames below mirrors the choice. */
+static inline rt::status_t launch_frames(const sdv::FrameArgs &a, rt::stream_t s, bool lean, int list_n = 0)
 {
-    BounceSlot *b = tls_bounce_slot;
-    if (!b) return NULL;
-    if (!b->p && !b->tried) { b->tried = true; if (hipHostMalloc(&b->p, BOUNCE_BYTES, hipHostMallocDefault) != hipSuccess) { b->p = NULL; (void)hipGetLastError(); } }
-    return b->p;
-}
-static inline hipError_t d2h(void *h, const void *d, size_t n, stream_t s)
-{
-    void *b = n > 0 && n <= (size_t)BOUNCE_BYTES ? bounce() : NULL;
-    if (b) {
-        hipError_t e = hipMemcpyAsync(b, d, n, hipMemcpyDeviceToHost, s); if (e != hipSuccess) return e;
-        e = hipStreamSynchronize(s); if (e != hipSuccess) return e;
-        memcpy(h, b, n);
-        return hipSuccess;
-    }
-    hipError_t e = hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, s); if (e != hipSuccess) return e; return hipStreamSynchronize(s);
-}
-static inline hipError_t dfill_bytes(void *p, int v, size_t n, stream_t s) { return hipMemsetAsync(p, v, n, s); }
-/* ... into memory that is page-locked itself (rt::hpin) */
-static inline hipError_t d2h_pinned(void *h, const void *d, size_t n, stream_t s) { hipError_t e = hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, s); if (e != hipSuccess) return e; return hipStreamSynchronize(s); }
-static inline hipError_t d2d(void *d, const void *s_, size_t n, stream_t s) { return hipMemcpyAsync(d, s_, n, hipMemcpyDeviceToDevice, s); }
-static inline hipError_t launch_frames(const sdv::FrameArgs &a, stream_t s, bool lean, int list_n = 0)
-{
-    int n = a.frame_list ? list_n : a.frame_hi - a.frame_lo;
-    if (n <= 0) return hipSuccess;
-    if (lean) hipLaunchKernelGGL(sdv_k_stc007_frames_lean, dim3((unsigned)n), dim3(64), 0, s, a);
-    else if (a.fat_levels) hipLaunchKernelGGL(sdv_k_stc007_frames_fat, dim3((unsigned)n), dim3(64 * (1 + sdv::FAT_WORKERS)), 0, s, a);   /* (a small round: the sweeps it misses are settled while it runs) */
-    else if (a.tc_hdr) hipLaunchKernelGGL(sdv_k_stc007_frames, dim3((unsigned)n), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL(sdv_k_stc007_frames_plain, dim3((unsigned)n), dim3(64), 0, s, a);       /* (no snapshots in this call: the build without them, sdv_engine::plain_general) */
-    return hipGetLastError();
-}
-/* the reference-level sweeps a round asked for: the levels (a wave per 64 levels of a line), then chain, vote and pick (a wave per line) */
-static inline hipError_t launch_sweeps(const sdv::SweepArgs &a, stream_t s)
-{
-    if (a.count <= 0) return hipSuccess;
-    hipLaunchKernelGGL(sdv_k_stc007_sweep_levels, dim3((unsigned)a.count * 4u), dim3(64), 0, s, a);
-    hipLaunchKernelGGL(sdv_k_stc007_sweep_pick, dim3((unsigned)a.count), dim3(64), 0, s, a);
-    return hipGetLastError();
-}
-static inline hipError_t launch_stc_lines(const sdv::LineArgs7 &a, stream_t s)
-{
-    if (a.n_lines == 0) return hipSuccess;
-    const unsigned grid = a.n_lines < 65536u ? a.n_lines : 65536u;         /* (a wave takes the lines grid apart: sdv_k_stc007_lines) */
-    hipLaunchKernelGGL(sdv_k_stc007_lines, dim3(grid), dim3(64), 0, s, a);
-    return hipGetLastError();
-}
-static inline hipError_t launch_deint(const sdvd::DeintArgs &a, stream_t s)
-{
-    if (a.n_blocks == 0) return hipSuccess;
-    hipLaunchKernelGGL(sdv_k_stc007_deint, dim3((unsigned)((a.n_blocks + 255) / 256)), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-static inline hipError_t launch_predict(const sdv::PredictArgs &a, stream_t s)
-{
-    int n = a.hi - a.first - (a.first_of ? 0 : 1);
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(sdv_k_predict, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-static inline hipError_t launch_double(const sdv::DoubleArgs &a, stream_t s)
-{
-    const unsigned per_row = (unsigned)((a.width + 3) / 4);
-    for (size_t r0 = 0; r0 < a.rows; r0 += 65535) {          /* grid.y holds 65 535 rows */
-        sdv::DoubleArgs b = a;
-        b.src = a.src + r0 * a.src_stride; b.dst = a.dst + r0 * a.dst_stride; b.rows = a.rows - r0 < 65535 ? a.rows - r0 : 65535;
-        hipLaunchKernelGGL(sdv_k_double_width, dim3((per_row + 255) / 256, (unsigned)b.rows), dim3(256), 0, s, b);
-    }
-    return hipGetLastError();
-}
-static inline hipError_t launch_hist_carry(const sdv::HistCarryArgs &a, stream_t s)
-{
-    if (a.n_anchors <= 0) return hipSuccess;
-    hipLaunchKernelGGL(sdv_k_hist_carry, dim3((unsigned)((a.n_anchors + 63) / 64)), dim3(64), 0, s, a);
-    return hipGetLastError();
-}
-static inline hipError_t launch_ref_patch(const sdv::RefPatchArgs &a, stream_t s)
-{
-    if (a.n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(sdv_k_ref_patch, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-static inline hipError_t launch_anchor(const sdv::AnchorArgs &a, stream_t s)
-{
-    if (a.n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(sdv_k_anchor, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-#else
-typedef void *stream_t;
-typedef int status_t;
-static const status_t OK = 0;
-static inline const char *err_str(int) { return "the emulated runtime refused"; }
-/* (tests: the fail_alloc_in-th allocation from now fails, once - sdv_emu_fail_alloc, tests/emu/emu_engine.cpp) */
-static int fail_alloc_in = 0;
-static inline int emu_alloc(void **p, size_t n) { if (fail_alloc_in > 0 && --fail_alloc_in == 0) { *p = NULL; return 1; } *p = malloc(n ? n : 1); return *p ? 0 : 1; }
-static inline int dmalloc(void **p, size_t n) { return emu_alloc(p, n); }
-static inline int dfree(void *p) { free(p); return 0; }
-static inline int hpin(void **p, size_t n) { return emu_alloc(p, n); }
-static inline int hunpin(void *p) { free(p); return 0; }
-static inline int h2d(void *d, const void *h, size_t n, stream_t) { memcpy(d, h, n); return 0; }
-static inline int d2h(void *h, const void *d, size_t n, stream_t) { memcpy(h, d, n); return 0; }
-static inline int d2h_pinned(void *h, const void *d, size_t n, stream_t) { memcpy(h, d, n); return 0; }
-static inline int dfill_bytes(void *p, int v, size_t n, stream_t) { memset(p, v, n); return 0; }
-static inline int d2d(void *d, const void *s_, size_t n, stream_t) { memcpy(d, s_, n); return 0; }
-static inline int launch_frames(const sdv::FrameArgs &a, stream_t, bool lean, int list_n = 0)
-{
-    sdv::FrameArgs args = a;
     const int n = a.frame_list ? list_n : a.frame_hi - a.frame_lo;
-    if (n <= 0) return 0;
-    if (lean) emu::launch((unsigned)n, [args]() { sdv_k_stc007_frames_lean(args); });
-    else if (a.fat_levels) emu::launch((unsigned)n, [args]() { sdv_k_stc007_frames_fat(args); });
-    else if (a.tc_hdr) emu::launch((unsigned)n, [args]() { sdv_k_stc007_frames(args); });
-    else emu::launch((unsigned)n, [args]() { sdv_k_stc007_frames_plain(args); });
-    return 0;
+    if (n <= 0) return rt::OK;
+    if (lean) return rt::launch_waves(sdv_k_stc007_frames_lean, (size_t)n, 1, a, s);
+    if (a.fat_levels) return rt::launch_waves(sdv_k_stc007_frames_fat, (size_t)n, 1 + sdv::FAT_WORKERS, a, s);
+    if (a.tc_hdr) return rt::launch_waves(sdv_k_stc007_frames, (size_t)n, 1, a, s);
+    return rt::launch_waves(sdv_k_stc007_frames_plain, (size_t)n, 1, a, s);
 }
-static inline int launch_sweeps(const sdv::SweepArgs &a, stream_t)
+static inline rt::status_t launch_predict(const sdv::PredictArgs &a, rt::stream_t s)
 {
-    sdv::SweepArgs args = a;
-    if (a.count <= 0) return 0;
-    emu::launch((unsigned)a.count * 4u, [args]() { sdv_k_stc007_sweep_levels(args); });
-    emu::launch((unsigned)a.count, [args]() { sdv_k_stc007_sweep_pick(args); });
-    return 0;
+    const int k0 = a.first + (a.first_of ? 0 : 1);
+    return RT_LAUNCH_ITEMS(sdv_k_predict, sdv::predict_body, k0, a.hi - k0, 256, s, a);
 }
-static inline int launch_stc_lines(const sdv::LineArgs7 &a, stream_t)
-{
-    sdv::LineArgs7 args = a;
-    if (a.n_lines == 0) return 0;
-    emu::launch(a.n_lines < 64u ? a.n_lines : 64u, [args]() { sdv_k_stc007_lines(args); });
-    return 0;
-}
-static inline int launch_deint(const sdvd::DeintArgs &a, stream_t)
-{
-    sdvd::DeintArgs args = a;
-    emu::launch((unsigned)((a.n_blocks + 63) / 64), [args]() { sdv_k_stc007_deint(args); });
-    return 0;
-}
-static inline int launch_predict(const sdv::PredictArgs &a, stream_t) { for (int k = a.first + (a.first_of ? 0 : 1); k < a.hi; k++) sdv::predict_body(a, k); return 0; }
-static inline int launch_anchor(const sdv::AnchorArgs &a, stream_t) { for (int i = 0; i < a.n; i++) sdv::anchor_body(a, i); return 0; }
-static inline int launch_hist_carry(const sdv::HistCarryArgs &a, stream_t) { for (int i = 0; i < a.n_anchors; i++) sdv::hist_carry_body(a, i); return 0; }
-static inline int launch_ref_patch(const sdv::RefPatchArgs &a, stream_t) { for (int i = 0; i < a.n; i++) sdv::ref_patch_body(a, i); return 0; }
-static inline int launch_double(const sdv::DoubleArgs &a, stream_t) { for (size_t r = 0; r < a.rows; r++) for (int x4 = 0; 4 * x4 < a.width; x4++) sdv::double_body(a, r, x4); return 0; }
-#endif
-#define RT_CHECK(expr) do { rt::status_t _e = (expr); if (_e != rt::OK) { set_error(e, std::string(#expr) + ": " + rt::err_str(_e)); return SDV_ERR_HIP; } } while (0)
-
-/* Device memory (DevBuf) and page-locked host memory (PinBuf) of the engines: grow-only, counted in elements, freed by the destructor - which must run
- * with the engine's device current (sdv_engine_destroy).  reserve(n) leaves a buffer of at least n elements whose old contents are gone; alloc_n is what
- * a growing buffer asks the runtime for (the call site's growth rule).  After a failure the buffer is empty: p == NULL and cap == 0 always go together. */
-struct DevMem { static status_t get(void **p, size_t bytes) { return dmalloc(p, bytes); } static void put(void *p) { (void)dfree(p); } };
-struct PinMem { static status_t get(void **p, size_t bytes) { return hpin(p, bytes); } static void put(void *p) { (void)hunpin(p); } };
-template <typename T, typename Mem> struct Buf {
-    T *p = NULL; size_t cap = 0;
-    Buf() = default;
-    Buf(const Buf &) = delete;
-    Buf &operator=(const Buf &) = delete;
-    ~Buf() { release(); }
-    operator T *() const { return p; }
-    void release() { if (p) Mem::put(p); p = NULL; cap = 0; }
-    void swap(Buf &o) { std::swap(p, o.p); std::swap(cap, o.cap); }
-    status_t reserve(size_t n, size_t alloc_n = 0)
-    {
-        if (n <= cap) return OK;
-        if (alloc_n < n) alloc_n = n;
-        release();
-        const status_t st = Mem::get((void **)&p, alloc_n * sizeof(T));
-        if (st != OK) { p = NULL; return st; }
-        cap = alloc_n;
-        return OK;
-    }
-};
-template <typename T> using DevBuf = Buf<T, DevMem>;
-template <typename T> using PinBuf = Buf<T, PinMem>;
-/* buffers that grow by one rule, in one statement: the first failure ends it */
-template <typename... B> static inline status_t reserve_all(size_t n, size_t alloc_n, B &...b) { status_t st = OK; (void)(((st = b.reserve(n, alloc_n)) == OK) && ...); return st; }
-} // namespace rt
-
-/* Every entry point runs on its engine's device and leaves the caller's current device as it found it. */
-struct DeviceGuard {
-#ifndef SDV_EMU
-    int prev; bool switched; hipError_t err;
-    explicit DeviceGuard(int device) : prev(-1), switched(false), err(hipSuccess)
-    {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != device) { err = hipSetDevice(device); switched = err == hipSuccess; }
-    }
-    ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-    hipError_t status() const { return err; }
-#else
-    explicit DeviceGuard(int) {}
-    int status() const { return 0; }
-#endif
-};
-#ifndef SDV_EMU
-#define SDV_ON_DEVICE(e) DeviceGuard device_guard_((e)->device); RT_CHECK(device_guard_.status()); rt::BounceScope bounce_scope_(&(e)->bounce)
-#else
-#define SDV_ON_DEVICE(e) DeviceGuard device_guard_((e)->device)
-#endif
 
 /* ---- engine ---------------------------------------------------------------------------------- */
 struct sdv_stitcher;                /* stitch stage state, stitch_engine.inc */
@@ -404,9 +202,7 @@ struct sdv_engine {
     /* statistics of the last call */
     sdv_run_info info = {};
     int profiling = 0;
-#ifndef SDV_EMU
-    rt::BounceSlot bounce = { NULL, false };        /* page-locked staging of the small synchronous read-backs (rt::d2h) */
-#endif
+    rt::BounceSlot bounce;          /* page-locked staging of the small synchronous read-backs (rt::d2h) */
     bool worn_tape = false;         /* most frames of the last sdv_binarize_frames call took lines through the general path */
     /* ... and hardly any of their decodes met the frame's last pass (a tape whose damage re-tunes the binarizer for good every few dozen lines): the general
      * kernel's build without the snapshots is a sixth faster there (stc007_device.h, kMeet).  Looked at again with the snapshots every eighth call. */
@@ -422,11 +218,8 @@ struct sdv_engine {
     sdv_audio *audio = NULL;
     sdv_vis *vis = NULL;
     sdv_encoder *enc = NULL;
-#ifndef SDV_EMU
-    hipEvent_t ev0, ev1;
-    bool have_events = false;
-    hipEvent_t ev_mark; bool have_mark = false;     /* behind the first round's read-back of sdv_binarize_frames when work of the next stage is queued behind it */
-#endif
+    rt::Timer timer;                /* sdv_set_profiling: the device time of a call's kernels */
+    rt::Event mark;                 /* behind the first round's read-back of sdv_binarize_frames when work of the next stage is queued behind it */
     bool binarize_settled_at_once = false;      /* the last sdv_binarize_frames call of the fused entry needed one round */
 #ifdef SDV_DEV_AIDS
     uint32_t dev_counts[16] = {};            /* developer builds: the launches of the last sdv_binarize_frames / sdv_binarize_lines call, by build (DevCount) */
@@ -435,7 +228,7 @@ struct sdv_engine {
 
 /* Developer builds count, per call, which builds of the frame kernel and the sweep kernels were launched and on how much work (sdv_dev_launch_counts):
  * tests prove with them that a tape reached the build it was made for.  Counted here, in the host code the HIP and the emulator builds share, with the
- * same choice rt::launch_frames makes. */
+ * same choice launch_frames makes. */
 enum DevCount { DEV_LEAN = 0, DEV_SNAP = 2, DEV_PLAIN = 4, DEV_FAT = 6, DEV_SWEEP_LEVELS = 8, DEV_SWEEP_PICK = 10, DEV_LINES = 12, DEV_N_COUNTS = 14 };
 #ifdef SDV_DEV_AIDS
 static inline void dev_reset_counts(sdv_engine *e) { memset(e->dev_counts, 0, sizeof(e->dev_counts)); }
@@ -480,7 +273,7 @@ sdv_engine *sdv_engine_create(int device)
     hipError_t err = hipGetDeviceCount(&count);
     if (err != hipSuccess || count <= 0) { set_error(NULL, "sdv_engine_create: no HIP device available (the decode engine has no CPU path)"); return NULL; }
     if (device < 0 || device >= count) { set_error(NULL, "sdv_engine_create: bad device index"); return NULL; }
-    { DeviceGuard g(device); if (g.status() != hipSuccess) { set_error(NULL, "sdv_engine_create: hipSetDevice failed"); return NULL; } }
+    { rt::DeviceGuard g(device); if (g.status() != rt::OK) { set_error(NULL, "sdv_engine_create: hipSetDevice failed"); return NULL; } }
 #endif
     sdv_engine *e = new sdv_engine();
     e->device = device;
@@ -493,21 +286,14 @@ sdv_engine *sdv_engine_create(int device)
 void sdv_engine_destroy(sdv_engine *e)
 {
     if (!e) return;
-    DeviceGuard device_guard_(e->device);
+    rt::DeviceGuard device_guard_(e->device);
     stitcher_free(e);
     pcm1_free(e);
     pcm16_free(e);
     audio_free(e);
     vis_free(e);
     encoder_free(e);
-#ifndef SDV_EMU
-    if (e->bounce.p) (void)hipHostFree(e->bounce.p);
-#endif
-#ifndef SDV_EMU
-    if (e->have_events) { (void)hipEventDestroy(e->ev0); (void)hipEventDestroy(e->ev1); }
-    if (e->have_mark) (void)hipEventDestroy(e->ev_mark);
-#endif
-    delete e;       /* (frees the buffers: the guard above is still in place) */
+    delete e;       /* (frees the buffers, the bounce buffer and the events: the guard above is still in place) */
 }
 
 const char *sdv_last_error(const sdv_engine *e) { return e ? e->last_error.c_str() : g_last_error.c_str(); }
@@ -530,7 +316,12 @@ int sdv_double_width(sdv_engine *e, const uint8_t *src, size_t src_row_stride, i
     if (width <= 0 || src_row_stride < (size_t)width || dst_row_stride < 2 * (size_t)width) { set_error(e, "bad line geometry"); return SDV_ERR_BAD_ARG; }
     SDV_ON_DEVICE(e);
     sdv::DoubleArgs a; a.src = src; a.src_stride = src_row_stride; a.width = width; a.rows = rows; a.dst = dst; a.dst_stride = dst_row_stride;
-    RT_CHECK(rt::launch_double(a, (rt::stream_t)stream));
+    const unsigned per_row = (unsigned)((width + 3) / 4);
+    for (size_t r0 = 0; r0 < rows; r0 += 65535) {            /* grid.y holds 65 535 rows */
+        sdv::DoubleArgs b = a;
+        b.src = a.src + r0 * a.src_stride; b.dst = a.dst + r0 * a.dst_stride; b.rows = rows - r0 < 65535 ? rows - r0 : 65535;
+        RT_CHECK(RT_LAUNCH_ROWS(sdv_k_double_width, sdv::double_body, b.rows, per_row, 256, (rt::stream_t)stream, b));
+    }
     return SDV_OK;
 }
 int sdv_set_frame_flags(sdv_engine *e, const uint8_t *flags, size_t n)
@@ -702,7 +493,9 @@ static int settle_sweep_chunks(sdv_engine *e, sdv::SweepArgs sa, int lo, int hi,
         const int cnt = hi - lo < CHUNK ? hi - lo : CHUNK;
         RT_CHECK(e->d_sweep_levels.reserve((size_t)cnt * 256, (size_t)CHUNK * 256));
         sa.memo = e->d_memo; sa.first = lo; sa.count = cnt; sa.levels = e->d_sweep_levels;
-        RT_CHECK(rt::launch_sweeps(sa, s));
+        /* the levels (a wave per 64 levels of a line), then chain, vote and pick (a wave per line) */
+        RT_LAUNCH64(sdv_k_stc007_sweep_levels, (size_t)cnt * 4u, sa, s);
+        RT_LAUNCH64(sdv_k_stc007_sweep_pick, (size_t)cnt, sa, s);
         dev_count(e, DEV_SWEEP_LEVELS, (size_t)cnt); dev_count(e, DEV_SWEEP_PICK, (size_t)cnt);
     }
     return SDV_OK;
@@ -741,7 +534,7 @@ int sdv_binarize_lines(sdv_engine *e, const uint8_t *luma, size_t row_stride, in
     for (int pass = 0;; pass++) {
         if (pass > 4) { set_error(e, "the sweeps of the lines did not settle"); return SDV_ERR_HIP; }
         dev_count(e, DEV_LINES, n_lines);
-        RT_CHECK(rt::launch_stc_lines(a, s));
+        RT_LAUNCH64(sdv_k_stc007_lines, a.n_lines < rt::STC_LINES_MAX_GRID ? a.n_lines : rt::STC_LINES_MAX_GRID, a, s);     /* (a wave takes the lines a grid apart) */
         int32_t count = 0;
         RT_CHECK(rt::d2h(&count, e->d_memo_count, sizeof(count), s));
         /* (the pool holds a request per line and more: a line asks for one sweep at most - one that did not fit would leave its line waiting for good) */
@@ -788,7 +581,7 @@ int sdv_deinterleave_blocks(sdv_engine *e, const sdv_deint_line *lines, size_t n
     if (st.res_mode > SDV_RES_MODE_16BIT) { set_error(e, "bad resolution mode"); return SDV_ERR_BAD_ARG; }
     SDV_ON_DEVICE(e);
     sdvd::DeintArgs a; a.lines = lines; a.n_blocks = n_blocks; a.st = st; a.out = out_blocks;
-    RT_CHECK(rt::launch_deint(a, (rt::stream_t)stream));
+    RT_CHECK(RT_LAUNCH_ITEMS(sdv_k_stc007_deint, sdvd::deint_body, 0, a.n_blocks, 256, (rt::stream_t)stream, a));
     return SDV_OK;
 }
 

@@ -6,43 +6,24 @@
  * values are the header's integer formulas, not libswscale's.
  */
 
-namespace rt {
-/* threads of a launch: a grid stride walks the rest (ingest_body).  2048 workgroups of 256 fill every CU of the MI355X eight times over. */
-#ifndef SDV_EMU
-static inline uint32_t ingest_threads(uint64_t items) { const uint64_t wg = (items + 255) / 256; return 256u * (uint32_t)(wg < 2048 ? wg : 2048); }
-template <int FAM, bool DBL> static inline status_t run_ingest(const sdv::IngestArgs &a, uint32_t threads, stream_t s)
+/* the build of sdv_k_ingest for a format family, with or without the doubling: `threads` threads, a grid stride walks the rest (ingest_body) */
+template <int FAM> static inline rt::status_t launch_ingest_fam(const sdv::IngestArgs &a, bool dbl, uint32_t threads, rt::stream_t s)
 {
-    hipLaunchKernelGGL((sdv_k_ingest<FAM, DBL>), dim3(threads / 256), dim3(256), 0, s, a);
-    return hipGetLastError();
+    if (dbl) return RT_LAUNCH_ITEMS((sdv_k_ingest<FAM, true>), (sdv::ingest_body<FAM, true>), 0u, threads, 256, s, a);
+    return RT_LAUNCH_ITEMS((sdv_k_ingest<FAM, false>), (sdv::ingest_body<FAM, false>), 0u, threads, 256, s, a);
 }
-#else
-/* Few threads: every test walks the stride, with carries from slots to rows to frames.  That is another launch size than the product's, so the split
- * into step_f / step_r / step_c below is made for other numbers here.  At the product's size a thread takes a second trip only in a call of more than
- * 2048 x 256 chunk slots: the last case of _tall_sources_and_many_rows (tests/test_ingest.py) is the one GPU test that has them. */
-static inline uint32_t ingest_threads(uint64_t) { return 320; }
-template <int FAM, bool DBL> static inline status_t run_ingest(const sdv::IngestArgs &a, uint32_t threads, stream_t)
-{
-    for (uint32_t t = 0; t < threads; t++) sdv::ingest_body<FAM, DBL>(a, t);
-    return 0;
-}
-#endif
-template <int FAM> static inline status_t run_ingest_fam(const sdv::IngestArgs &a, bool dbl, uint32_t threads, stream_t s)
-{
-    return dbl ? run_ingest<FAM, true>(a, threads, s) : run_ingest<FAM, false>(a, threads, s);
-}
-static inline status_t launch_ingest(const sdv::IngestArgs &a, int fam, bool dbl, uint32_t threads, stream_t s)
+static inline rt::status_t launch_ingest(const sdv::IngestArgs &a, int fam, bool dbl, uint32_t threads, rt::stream_t s)
 {
     switch (fam) {
-    case sdv::ING_GRAY8: return run_ingest_fam<sdv::ING_GRAY8>(a, dbl, threads, s);
-    case sdv::ING_UYVY: return run_ingest_fam<sdv::ING_UYVY>(a, dbl, threads, s);
-    case sdv::ING_YUYV: return run_ingest_fam<sdv::ING_YUYV>(a, dbl, threads, s);
-    case sdv::ING_V210: return run_ingest_fam<sdv::ING_V210>(a, dbl, threads, s);
-    case sdv::ING_GRAY10: return run_ingest_fam<sdv::ING_GRAY10>(a, dbl, threads, s);
-    case sdv::ING_RGB3: return run_ingest_fam<sdv::ING_RGB3>(a, dbl, threads, s);
-    default: return run_ingest_fam<sdv::ING_RGB4>(a, dbl, threads, s);
+    case sdv::ING_GRAY8: return launch_ingest_fam<sdv::ING_GRAY8>(a, dbl, threads, s);
+    case sdv::ING_UYVY: return launch_ingest_fam<sdv::ING_UYVY>(a, dbl, threads, s);
+    case sdv::ING_YUYV: return launch_ingest_fam<sdv::ING_YUYV>(a, dbl, threads, s);
+    case sdv::ING_V210: return launch_ingest_fam<sdv::ING_V210>(a, dbl, threads, s);
+    case sdv::ING_GRAY10: return launch_ingest_fam<sdv::ING_GRAY10>(a, dbl, threads, s);
+    case sdv::ING_RGB3: return launch_ingest_fam<sdv::ING_RGB3>(a, dbl, threads, s);
+    default: return launch_ingest_fam<sdv::ING_RGB4>(a, dbl, threads, s);
     }
 }
-} // namespace rt
 
 enum { INGEST_MAX_DIM = 32768, INGEST_MAX_LINES = 640 /* LINES_PER_FRAME_MAX */ };
 
@@ -140,10 +121,10 @@ int sdv_ingest_frames(sdv_engine *e, const sdv_ingest_desc *d, const void *src, 
     a.src_row_bytes = (uint32_t)g.row_bytes;
     a.slots = (g.out_w + 30) / 16;
     a.wt[0] = g.wt[0]; a.wt[1] = g.wt[1]; a.wt[2] = g.wt[2];
-    const uint32_t threads = rt::ingest_threads((uint64_t)n_frames * (uint64_t)g.out_h * (uint64_t)a.slots);
-    const uint32_t lines = threads / (uint32_t)a.slots;
-    a.step_c = (int)(threads % (uint32_t)a.slots); a.step_r = (int)(lines % (uint32_t)g.out_h); a.step_f = (int)(lines / (uint32_t)g.out_h);
-    RT_CHECK(rt::launch_ingest(a, g.fam, g.doubled != 0, threads, (rt::stream_t)stream));
+    const uint32_t threads = rt::grid_stride_threads((uint64_t)n_frames * (uint64_t)g.out_h * (uint64_t)a.slots);
+    const rt::StrideSteps st = rt::stride_steps(threads, (uint32_t)g.out_h, (uint32_t)a.slots);
+    a.step_f = st.step_f; a.step_r = st.step_r; a.step_c = st.step_c;
+    RT_CHECK(launch_ingest(a, g.fam, g.doubled != 0, threads, (rt::stream_t)stream));
     return SDV_OK;
 }
 

@@ -15,17 +15,11 @@
 #pragma once
 #include "markerless_chain_device.h"
 
-/* one of the model's kernels over the indices [lo, hi), a thread each (markerless_chain_device.h) */
+/* one of the model's kernels over the indices [lo, hi), a thread each (markerless_chain_device.h, SDV_CHAIN_KERNEL: under the emulator such a kernel is
+ * the loop over its range, so item i is its range [i, i + 1)) */
 template <class K, class A> static inline rt::status_t launch_chain_range(K kernel, const A &a, int lo, int hi, rt::stream_t s)
 {
-    if (hi <= lo) return rt::OK;
-#ifndef SDV_EMU
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((hi - lo + 255) / 256)), dim3(256), 0, s, a, lo, hi);
-    return hipGetLastError();
-#else
-    kernel(a, lo, hi);
-    return rt::OK;
-#endif
+    return RT_LAUNCH_ITEMS(kernel, ([&](const A &x, int i) { kernel(x, i, i + 1); }), lo, hi - lo, 256, s, a, lo, hi);
 }
 
 template <class Fmt>
@@ -72,12 +66,7 @@ static int markerless_binarize_frames(sdv_engine *e, const uint8_t *luma, size_t
     memset(&e->info, 0, sizeof(e->info));
     e->info.frames = (uint32_t)n;
     RT_CHECK(rt::h2d(d_in, &Fmt::chain(e), sizeof(State), s));
-#ifndef SDV_EMU
-    if (e->profiling) {
-        if (!e->have_events) { RT_CHECK(hipEventCreate(&e->ev0)); RT_CHECK(hipEventCreate(&e->ev1)); e->have_events = true; }
-        RT_CHECK(hipEventRecord(e->ev0, s));
-    }
-#endif
+    if (e->profiling) RT_CHECK(e->timer.start(s));
     /* the prescan lines of every frame */
     a.f.frame_list = NULL; a.f.frame_lo = 0; a.f.frame_hi = n;
     const bool insane = e->mode == SDV_MODE_INSANE;         /* its own build of the two kernels (pcm1_bin_device.h, process_line_p1) */
@@ -101,9 +90,7 @@ static int markerless_binarize_frames(sdv_engine *e, const uint8_t *luma, size_t
             if (insane) RT_LAUNCH64(Fmt::k_bin_insane, given_up.size(), a, s); else RT_LAUNCH64(Fmt::k_bin, given_up.size(), a, s);
             a.f.frame_list = NULL;
             e->info.frames_launched += (uint32_t)given_up.size(); e->info.frames_general += (uint32_t)given_up.size();
-#ifndef SDV_EMU
             RT_CHECK(rt::ssync(s));         /* (the list's source is this block's vector) */
-#endif
         }
     }
     std::vector<int> list, head_of, others, others_head;
@@ -168,14 +155,10 @@ static int markerless_binarize_frames(sdv_engine *e, const uint8_t *luma, size_t
         }
         e->info.rounds++; e->info.frames_launched += (uint32_t)list.size();
     }
-#ifndef SDV_EMU
     if (e->profiling) {
-        float ms = 0.f;
-        RT_CHECK(hipEventRecord(e->ev1, s)); RT_CHECK(hipEventSynchronize(e->ev1));
-        RT_CHECK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-        e->info.kernel_ms = ms;
+        RT_CHECK(e->timer.stop(s));
+        RT_CHECK(e->timer.elapsed_ms(&e->info.kernel_ms));      /* (once per call) */
     }
-#endif
     RT_CHECK(rt::d2h(&Fmt::chain(e), &d_out[n - 1], sizeof(State), s));
     return SDV_OK;
 }

@@ -6,39 +6,9 @@
  * conv_queue, output offsets), ctrl (all at once), flags (in order), emit (all at once).  The stitcher's stream state (padding and Control Bit histories) stays in device memory between the
  * kernels and between calls; a call that fails puts back the copy taken at its start.
  */
-/* The analysis of a batch does not depend on the decisions of the batch before it: in the product build it runs on a stream of its own,
- * ahead of the in-order kernels (which are single waves and leave the chip idle); the emulator build runs everything in order. */
-namespace rt16 {
-#ifndef SDV_EMU
-enum { MAX_EV = 64 };
-struct side_t { hipStream_t stream, mid, tail; hipEvent_t start, done[MAX_EV], chosen[MAX_EV], decided[MAX_EV], joined; bool ok; };
-static inline bool side_init(side_t &x)
-{
-    if (x.ok) return true;
-    if (hipStreamCreateWithFlags(&x.stream, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&x.tail, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&x.mid, hipStreamNonBlocking) != hipSuccess) return false;
-    if (hipEventCreateWithFlags(&x.start, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&x.joined, hipEventDisableTiming) != hipSuccess) return false;
-    for (int i = 0; i < MAX_EV; i++)
-        if (hipEventCreateWithFlags(&x.done[i], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&x.decided[i], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&x.chosen[i], hipEventDisableTiming) != hipSuccess) return false;
-    x.ok = true;
-    return true;
-}
-static inline void side_free(side_t &x)
-{
-    if (!x.ok) return;
-    (void)hipStreamSynchronize(x.stream); (void)hipStreamSynchronize(x.mid); (void)hipStreamSynchronize(x.tail);
-    (void)hipEventDestroy(x.start); (void)hipEventDestroy(x.joined);
-    for (int i = 0; i < MAX_EV; i++) { (void)hipEventDestroy(x.done[i]); (void)hipEventDestroy(x.decided[i]); (void)hipEventDestroy(x.chosen[i]); }
-    (void)hipStreamDestroy(x.stream); (void)hipStreamDestroy(x.mid); (void)hipStreamDestroy(x.tail);
-    x.ok = false;
-}
-#else
-enum { MAX_EV = 64 };
-struct side_t { int dummy; };
-#endif
-} // namespace rt16
-
+/* The analysis of a batch does not depend on the decisions of the batch before it: where streams run beside each other (rt::CONCURRENT, the product
+ * build) it runs on a stream of its own, ahead of the in-order kernels (which are single waves and leave the chip idle); the emulator build runs
+ * everything in order on the caller's stream. */
 struct sdv_pcm16_stitcher {
     sdv_pcm16x0_stitch_settings st;
     /* (made by new sdv_pcm16_stitcher(): everything that is not a buffer starts as zero) */
@@ -54,7 +24,9 @@ struct sdv_pcm16_stitcher {
     bool state_valid;
     rt::DevBuf<sdvp16::Sub> d_rem, d_rem_slots;       /* conv_queue's remainder: behind the last call (FRAME_SUBS entries) / behind every batch of the running call */
     rt::DevBuf<sdvp16::Ana16> d_ana; rt::DevBuf<sdvp16::Pick16> d_pick; rt::DevBuf<sdvp16::Choice16> d_choice; rt::DevBuf<sdvp16::Dec16> d_dec; rt::DevBuf<sdvp16::Ctrl16> d_ctrl; rt::DevBuf<sdvp16::Sub> d_fields;
-    rt16::side_t side;              /* a second stream for the analysis kernels, which run ahead of the in-order decisions (product build only) */
+    /* a second stream for the analysis kernels, which run ahead of the in-order decisions, and two for the chains behind them.  The last member: it goes
+     * first, and its going waits for the side streams - the buffers above go after that */
+    rt::SideStreams side;
 };
 #ifndef SDV_P16_ANA_BATCHES
 #define SDV_P16_ANA_BATCHES 3
@@ -76,10 +48,7 @@ static void pcm16_free(sdv_engine *e)
 {
     sdv_pcm16_stitcher *t = e->pcm16;
     if (!t) return;
-#ifndef SDV_EMU
-    rt16::side_free(t->side);       /* (waits for the side streams: the buffers go after that) */
-#endif
-    delete t;
+    delete t;       /* (rt::SideStreams waits for the side streams ahead of the buffers) */
     e->pcm16 = NULL;
 }
 
@@ -231,7 +200,7 @@ int sdv_pcm16x0_stitch_frames(sdv_engine *e, const sdv_pcm16x0_bin_rec *lines, s
         RT_CHECK(rt::h2d(t->d_blk_ofs, blk.data(), nblk * sizeof(uint32_t), s));
         const uint32_t stat0[4] = { 0, 0xFFFFFFFFu, 0, 0 };
         RT_CHECK(rt::h2d(t->d_stat, stat0, sizeof(stat0), s));
-        RT_CHECK(rt::dzero(t->d_marks, (n_seg + 1) * sizeof(uint32_t), s));
+        RT_CHECK(rt::dfill_bytes(t->d_marks, 0, (n_seg + 1) * sizeof(uint32_t), s));
         sa.seg_end = t->d_seg_end; sa.n_seg = (uint32_t)n_seg; sa.marks = t->d_marks; sa.write = 1;
         RT_LAUNCH64(sdv_k_pcm16_segments, nblk, sa, s);
     }
@@ -245,10 +214,10 @@ int sdv_pcm16x0_stitch_frames(sdv_engine *e, const sdv_pcm16x0_bin_rec *lines, s
         if (attempt > 0) { const uint32_t again[4] = { 0, 0xFFFFFFFFu, stat[2], 0 }; RT_CHECK(rt::h2d(t->d_stat, again, sizeof(again), s)); RT_CHECK(rt::ssync(s)); }
 
         /* 2. output offsets: a running sum the carry kernel of every batch takes on (a frame's count depends on what waits in conv_queue) */
-        RT_CHECK(rt::dzero(t->d_pair_ofs, sizeof(uint64_t), s));
-        RT_CHECK(rt::dzero(t->d_frasm_ofs, sizeof(uint32_t), s));
-        RT_CHECK(rt::dzero(t->d_vblk_ofs, sizeof(uint32_t), s));
-        RT_CHECK(rt::dzero(t->d_vline_ofs, sizeof(uint32_t), s));
+        RT_CHECK(rt::dfill_bytes(t->d_pair_ofs, 0, sizeof(uint64_t), s));
+        RT_CHECK(rt::dfill_bytes(t->d_frasm_ofs, 0, sizeof(uint32_t), s));
+        RT_CHECK(rt::dfill_bytes(t->d_vblk_ofs, 0, sizeof(uint32_t), s));
+        RT_CHECK(rt::dfill_bytes(t->d_vline_ofs, 0, sizeof(uint32_t), s));
 
         /* 3. the frames, a batch at a time; the buffers hold every batch of the call so that the analysis can run ahead */
         const size_t batch = n_seg < (size_t)SDV_P16_STITCH_BATCH ? n_seg : (size_t)SDV_P16_STITCH_BATCH;
@@ -276,8 +245,6 @@ int sdv_pcm16x0_stitch_frames(sdv_engine *e, const sdv_pcm16x0_bin_rec *lines, s
             const size_t b = b0 / batch;
             fa.rem_in = b == 0 ? t->d_rem : t->d_rem_slots + (b - 1) * sdvp16::FRAME_SUBS; fa.rem_out = t->d_rem_slots + b * sdvp16::FRAME_SUBS;
         };
-        bool ahead = false;
-#ifndef SDV_EMU
         /* The analysis is bound by what the chip holds at once (its LDS staging allows ~1 500 waves, a wave takes ~1.6 ms): it is launched
          * SDV_P16_ANA_BATCHES batches at a time - two fills of the chip - while the in-order kernels follow batch by batch. */
         /* (measured, 10 000 frames: SI 16.0 ms with three batches per launch, 15.2 ms with one - its in-order kernels are the longer chain and want to
@@ -286,7 +253,7 @@ int sdv_pcm16x0_stitch_frames(sdv_engine *e, const sdv_pcm16x0_bin_rec *lines, s
         if (const char *ab = dev_env("SDV_P16_ANA_BATCHES")) { const int v = atoi(ab); if (v >= 1 && v <= 64) ana_batches = (size_t)v; }      /* developer aid */
         /* With the padding hint (EI) the first batch is analysed alone and the rest waits for its decisions: a stream that starts cold has its
          * history after that batch, and everything behind it gets the short tables. */
-        const bool lead = hint_on && n_batches > 2 && n_batches <= (size_t)rt16::MAX_EV;
+        const bool lead = hint_on && n_batches > 2 && n_batches <= (size_t)rt::SIDE_EVENTS;
         const size_t n_ana = lead ? 1 + (n_batches - 1 + ana_batches - 1) / ana_batches : (n_batches + ana_batches - 1) / ana_batches;
         auto group_first = [&](size_t g) -> size_t { return lead ? (g == 0 ? 0 : 1 + (g - 1) * ana_batches) : g * ana_batches; };      /* its first batch */
         auto group_size = [&](size_t g) -> size_t { return lead && g == 0 ? 1 : ana_batches; };                                         /* batches */
@@ -296,61 +263,52 @@ int sdv_pcm16x0_stitch_frames(sdv_engine *e, const sdv_pcm16x0_bin_rec *lines, s
                 point_at(b0);
                 fa.n_batch = (uint32_t)(n_seg - b0 < want ? n_seg - b0 : want);
                 RT_LAUNCH64(sdv_k_pcm16_analyse, fa.n_batch, fa, t->side.stream);
-                RT_CHECK(hipEventRecord(t->side.done[g], t->side.stream));
+                RT_CHECK(rt::record(t->side.done[g], t->side.stream));
             }
             return SDV_OK;
         };
-        ahead = n_batches > 1 && n_ana <= (size_t)rt16::MAX_EV && !dev_env("SDV_P16_NO_SIDE_STREAM") && rt16::side_init(t->side);
+        const bool ahead = rt::CONCURRENT && n_batches > 1 && n_ana <= (size_t)rt::SIDE_EVENTS && !dev_env("SDV_P16_NO_SIDE_STREAM") && t->side.open();
+        const bool three_chains = ahead && n_batches <= (size_t)rt::SIDE_EVENTS;        /* (an event per batch) */
         if (ahead) {
             /* the analysis of every batch, back to back on the side stream, behind what this stream has done so far */
-            RT_CHECK(hipEventRecord(t->side.start, s));
-            RT_CHECK(hipStreamWaitEvent(t->side.stream, t->side.start, 0));
+            RT_CHECK(rt::record(t->side.start, s));
+            RT_CHECK(rt::wait(t->side.stream, t->side.start));
             { const int lrc = launch_groups(0, lead ? 1 : n_ana); if (lrc != SDV_OK) return lrc; }
         }
-#endif
         for (size_t b = 0; b < n_batches; b++) {
             point_at(b * batch);
             if (!ahead) RT_LAUNCH64(sdv_k_pcm16_analyse, fa.n_batch, fa, s);
-#ifndef SDV_EMU
             else if (lead ? (b == 0 || (b - 1) % ana_batches == 0) : b % ana_batches == 0)
-                RT_CHECK(hipStreamWaitEvent(s, t->side.done[lead ? (b == 0 ? 0 : 1 + (b - 1) / ana_batches) : b / ana_batches], 0));
-#endif
+                RT_CHECK(rt::wait(s, t->side.done[lead ? (b == 0 ? 0 : 1 + (b - 1) / ana_batches) : b / ana_batches]));
             RT_LAUNCH64(sdv_k_pcm16_choose, 1, fa, s);
             /* Three chains of in-order kernels on three members of the state, each on a stream of its own: the padding decisions (this stream: the next
              * batch's need nothing but the padding history), what follows from them per frame and conv_queue's remainder (finish, carry, ctrl), the Control
              * Bit history and the output (flags, emit).  The slowest chain sets the pace of a batch, not their sum. */
-            rt::stream_t s_mid = s, s_tail = s;
-#ifndef SDV_EMU
-            if (ahead && n_batches <= (size_t)rt16::MAX_EV) {
-                RT_CHECK(hipEventRecord(t->side.chosen[b], s));
-                RT_CHECK(hipStreamWaitEvent(t->side.mid, t->side.chosen[b], 0));
-                s_mid = t->side.mid; s_tail = t->side.tail;
-                if (lead && ahead && b == 0) {      /* the first batch's paddings are decided: the history stands, the analysis of all the others may start */
-                    RT_CHECK(hipStreamWaitEvent(t->side.stream, t->side.chosen[0], 0));
+            const rt::stream_t s_mid = three_chains ? t->side.mid : s, s_tail = three_chains ? t->side.tail : s;
+            if (three_chains) {
+                RT_CHECK(rt::record(t->side.chosen[b], s));
+                RT_CHECK(rt::wait(s_mid, t->side.chosen[b]));
+                if (lead && b == 0) {       /* the first batch's paddings are decided: the history stands, the analysis of all the others may start */
+                    RT_CHECK(rt::wait(t->side.stream, t->side.chosen[0]));
                     { const int lrc = launch_groups(1, n_ana); if (lrc != SDV_OK) return lrc; }
                     point_at(0);
                 }
             }
-#endif
             RT_LAUNCH64(sdv_k_pcm16_finish, (fa.n_batch + 63) / 64, fa, s_mid);
             RT_LAUNCH64(sdv_k_pcm16_carry, 1, fa, s_mid);
             RT_LAUNCH64(sdv_k_pcm16_ctrl, fa.n_batch, fa, s_mid);
-#ifndef SDV_EMU
-            if (s_tail != s) {
-                RT_CHECK(hipEventRecord(t->side.decided[b], s_mid));
-                RT_CHECK(hipStreamWaitEvent(s_tail, t->side.decided[b], 0));
+            if (three_chains) {
+                RT_CHECK(rt::record(t->side.decided[b], s_mid));
+                RT_CHECK(rt::wait(s_tail, t->side.decided[b]));
             }
-#endif
             RT_LAUNCH64(sdv_k_pcm16_flags, 1, fa, s_tail);
             RT_LAUNCH64(sdv_k_pcm16_emit, fa.n_batch, fa, s_tail);
             if (t->vis_lines) RT_LAUNCH64(sdv_k_pcm16_emit_lines, fa.n_batch, fa, s_tail);
         }
-#ifndef SDV_EMU
-        if (ahead && n_batches <= (size_t)rt16::MAX_EV) {      /* back to one stream */
-            RT_CHECK(hipEventRecord(t->side.joined, t->side.tail));
-            RT_CHECK(hipStreamWaitEvent(s, t->side.joined, 0));
+        if (three_chains) {     /* back to one stream */
+            RT_CHECK(rt::record(t->side.joined, t->side.tail));
+            RT_CHECK(rt::wait(s, t->side.joined));
         }
-#endif
     }
 
     /* 4. records after the last END_FRAME wait for the next call, like sub-lines in the reference's input queue */
@@ -361,9 +319,7 @@ int sdv_pcm16x0_stitch_frames(sdv_engine *e, const sdv_pcm16x0_bin_rec *lines, s
         RT_CHECK(rt::d2h(res, t->d_stat, sizeof(res), s));
         memcpy(stat, res, sizeof(stat)); tot_pairs = (uint64_t)res[4] | ((uint64_t)res[5] << 32); tot_frames = res[6]; last_end = res[7];
     } else RT_CHECK(rt::ssync(s));
-#ifdef SDV_EMU
-    if (getenv("SDV_P16_HINT_TRACE")) fprintf(stderr, "[p16 hint] attempt %d: hint %s, %zu frames, needs full tables: %u\n", attempt, hint_on ? "on" : "off", n_seg, stat[3]);
-#endif
+    if (dev_env("SDV_P16_HINT_TRACE")) fprintf(stderr, "[p16 hint] attempt %d: hint %s, %zu frames, needs full tables: %u\n", attempt, hint_on ? "on" : "off", n_seg, stat[3]);
     if (hint_on && stat[3] && !stat[0]) {       /* a frame needed more than the one padding: the histories back to where the call began, and once more */
         RT_CHECK(rt::d2d(t->d_state, t->d_state + 1, sizeof(sdvp16::State16), s));
         RT_CHECK(rt::ssync(s));

@@ -88,7 +88,7 @@ int sdv_pcm1_stitch_frames(sdv_engine *e, const sdv_pcm1_line_rec *lines, size_t
         RT_CHECK(rt::h2d(t->d_blk_ofs, blk.data(), nblk * sizeof(uint32_t), s));
         const uint32_t stat0[4] = { 0, 0xFFFFFFFFu, 0, 0 };
         RT_CHECK(rt::h2d(t->d_stat, stat0, sizeof(stat0), s));
-        RT_CHECK(rt::dzero(t->d_marks, (n_seg + 1) * sizeof(uint32_t), s));
+        RT_CHECK(rt::dfill_bytes(t->d_marks, 0, (n_seg + 1) * sizeof(uint32_t), s));
         sa.seg_end = t->d_seg_end; sa.n_seg = (uint32_t)n_seg; sa.marks = t->d_marks; sa.write = 1;
         RT_LAUNCH64(sdv_k_pcm1_segments, nblk, sa, s);
 
@@ -105,7 +105,7 @@ int sdv_pcm1_stitch_frames(sdv_engine *e, const sdv_pcm1_line_rec *lines, size_t
         fa.out_pairs = out_pairs; fa.pairs_cap = pairs_cap; fa.out_frames = out_frames; fa.frames_cap = (uint32_t)(frames_cap > 0xFFFFFFFFu ? 0xFFFFFFFFu : frames_cap);
         fa.stat = t->d_stat;
         rt::DevBuf<unsigned long long> d_timing;
-        if (dev_env("SDV_STITCH_TIMING")) { RT_CHECK(d_timing.reserve(n_seg * 8)); RT_CHECK(rt::dzero(d_timing, n_seg * 8 * sizeof(unsigned long long), s)); }
+        if (dev_env("SDV_STITCH_TIMING")) { RT_CHECK(d_timing.reserve(n_seg * 8)); RT_CHECK(rt::dfill_bytes(d_timing, 0, n_seg * 8 * sizeof(unsigned long long), s)); }
         fa.timing = d_timing;
         fa.cnt_out = NULL; fa.kept_out = NULL; fa.cnt_in = NULL; fa.kept_in = NULL; fa.hist = NULL;
         fa.out_blocks = t->vis_blocks; fa.blocks_cap = t->vis_blocks_cap; fa.out_asm = t->vis_lines; fa.asm_cap = t->vis_lines_cap;
@@ -239,7 +239,7 @@ extern "C" int sdv_pcm1_binarize_lines(sdv_engine *e, const uint8_t *luma, size_
         sdv_pcm1_stitcher *t = pcm1_get(e);
         RT_CHECK(t->d_line_list.reserve(n_lines + 4, n_lines + n_lines / 4 + 1024));
         a.counters = t->d_line_list; a.list = t->d_line_list + 4;
-        RT_CHECK(rt::dzero(a.counters, 4 * sizeof(int), s));
+        RT_CHECK(rt::dfill_bytes(a.counters, 0, 4 * sizeof(int), s));
         RT_LAUNCH64(sdv_k_pcm1_lines_lean, n_lines, a, s);
         if (e->mode == SDV_MODE_INSANE) RT_LAUNCH64(sdv_k_pcm1_lines_insane, full_grid, a, s); else RT_LAUNCH64(sdv_k_pcm1_lines, full_grid, a, s);
     } else {

@@ -121,15 +121,11 @@ struct Stc007FrameCall {
             rt::DevBuf<sdv::SweepMemo> bigger;      /* (the one buffer that grows with its contents; an early return frees it) */
             RT_CHECK(bigger.reserve((size_t)count + (size_t)count / 2 + 4096));
             RT_CHECK(rt::d2d(bigger, e->d_memo, (size_t)cap * sizeof(sdv::SweepMemo), s));
-#ifndef SDV_EMU
-            RT_CHECK(hipStreamSynchronize(s));
-#endif
+            RT_CHECK(rt::ssync(s));
             e->d_memo.swap(bigger);
             const int32_t c32 = cap;
             RT_CHECK(rt::h2d(d_count, &c32, sizeof(c32), s));
-#ifndef SDV_EMU
-            RT_CHECK(hipStreamSynchronize(s));      /* (the copy's source is on this stack frame) */
-#endif
+            RT_CHECK(rt::ssync(s));                 /* (the copy's source is on this stack frame) */
             a.memo = e->d_memo; a.memo_cap = (int32_t)e->d_memo.cap;
         }
         return SDV_OK;
@@ -139,19 +135,12 @@ struct Stc007FrameCall {
      * launches, end_round. */
     int begin_round(bool with_full)
     {
-#ifndef SDV_EMU
-        if (e->profiling) {
-            if (!e->have_events) { RT_CHECK(hipEventCreate(&e->ev0)); RT_CHECK(hipEventCreate(&e->ev1)); e->have_events = true; }
-            RT_CHECK(hipEventRecord(e->ev0, s));
-        }
-#endif
+        if (e->profiling) RT_CHECK(e->timer.start(s));
         return with_full ? prepare_memo() : SDV_OK;
     }
     int end_round(uint32_t launched, uint32_t general)
     {
-#ifndef SDV_EMU
-        if (e->profiling) { RT_CHECK(hipEventRecord(e->ev1, s)); timing_pending = true; }       /* read after the next synchronising copy */
-#endif
+        if (e->profiling) { RT_CHECK(e->timer.stop(s)); timing_pending = true; }       /* read after the next synchronising copy */
         /* the last frame's outgoing state travels with the flags: one read-back per round (the frame writes it there itself, v2d_store_state) */
         e->info.rounds++; e->info.frames_launched += launched; e->info.frames_general += general;
         return SDV_OK;
@@ -166,7 +155,7 @@ struct Stc007FrameCall {
         const bool fat = full && memo_ready && cold_frame && hi - lo == 1 && !dev_env("SDV_NO_FAT");
         if (fat) { a.fat_levels = e->d_sweep_levels; round_fat = true; }
         dev_count_frames(e, a, !full, hi - lo);
-        RT_CHECK(rt::launch_frames(a, s, !full));
+        RT_CHECK(launch_frames(a, s, !full));
         a.fat_levels = NULL;
         return end_round((uint32_t)(hi - lo), full ? (uint32_t)(hi - lo) : 0u);
     }
@@ -190,7 +179,7 @@ struct Stc007FrameCall {
         if (!list_lean.empty()) {
             a.frame_list = e->d_list_lean;
             dev_count_frames(e, a, true, (int)list_lean.size());
-            RT_CHECK(rt::launch_frames(a, s, true, (int)list_lean.size()));
+            RT_CHECK(launch_frames(a, s, true, (int)list_lean.size()));
             launched += (uint32_t)list_lean.size();
         }
         if (!list_full.empty()) {
@@ -201,7 +190,7 @@ struct Stc007FrameCall {
             const bool fat = memo_ready && sweeps_seen > 0 && list_full.size() <= (e->d_sweep_levels.cap / 256 < 512 ? e->d_sweep_levels.cap / 256 : (size_t)512) && !dev_env("SDV_NO_FAT");
             if (fat) { a.fat_levels = e->d_sweep_levels; round_fat = true; }
             dev_count_frames(e, a, false, (int)list_full.size());
-            RT_CHECK(rt::launch_frames(a, s, false, (int)list_full.size()));
+            RT_CHECK(launch_frames(a, s, false, (int)list_full.size()));
             a.fat_levels = NULL;
             launched += (uint32_t)list_full.size(); general += (uint32_t)list_full.size();
         }
@@ -211,15 +200,12 @@ struct Stc007FrameCall {
 
     int resolve_timing()
     {
-#ifndef SDV_EMU
         if (timing_pending) {
             float ms = 0.f;
-            RT_CHECK(hipEventSynchronize(e->ev1));
-            RT_CHECK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-            e->info.kernel_ms += ms;
+            RT_CHECK(e->timer.elapsed_ms(&ms));
+            e->info.kernel_ms += ms;        /* (the call's rounds add up) */
             timing_pending = false;
         }
-#endif
         return SDV_OK;
     }
 
@@ -228,24 +214,19 @@ struct Stc007FrameCall {
      * read-back only. */
     int read_flags(int first, const FusedHooks *ahead = NULL)
     {
+        const size_t bytes = tail_ofs + tail_bytes - (size_t)first;
         if (!ahead) {
-            RT_CHECK(rt::d2h_pinned(flag + first, e->d_flag + first, tail_ofs + tail_bytes - (size_t)first, s));
+            RT_CHECK(rt::d2h_pinned(flag + first, e->d_flag + first, bytes, s));
             return SDV_OK;
         }
-#ifndef SDV_EMU
-        if (!e->have_mark) { RT_CHECK(hipEventCreateWithFlags(&e->ev_mark, hipEventDisableTiming)); e->have_mark = true; }
-        RT_CHECK(hipMemcpyAsync(flag + first, e->d_flag + first, tail_ofs + tail_bytes - (size_t)first, hipMemcpyDeviceToHost, s));
-        RT_CHECK(hipEventRecord(e->ev_mark, s));
-#else
-        RT_CHECK(rt::d2h_pinned(flag + first, e->d_flag + first, tail_ofs + tail_bytes - (size_t)first, s));
-#endif
+        RT_CHECK(rt::d2h_async(flag + first, e->d_flag + first, bytes, s));
+        RT_CHECK(rt::record(e->mark, s));
         const int rc = ahead->after_first_round(ahead->after_ctx);
-#ifndef SDV_EMU
         /* (the flags' read-back is in flight into h_flag, and the stage behind may have queued kernels that write the caller's buffers: an error return
          * waits for all of it - the caller may free or reuse its memory the moment the call is back) */
-        if (rc != SDV_OK) { (void)hipStreamSynchronize(s); return rc; }
-        { const hipError_t ev_rc = hipEventSynchronize(e->ev_mark); if (ev_rc != hipSuccess) { (void)hipStreamSynchronize(s); set_error(e, std::string("hipEventSynchronize(e->ev_mark): ") + rt::err_str(ev_rc)); return SDV_ERR_HIP; } }
-#endif
+        if (rc != SDV_OK) { (void)rt::ssync(s); return rc; }
+        const rt::status_t ev_rc = rt::wait_host(e->mark);
+        if (ev_rc != rt::OK) { (void)rt::ssync(s); set_error(e, std::string("rt::wait_host(e->mark): ") + rt::err_str(ev_rc)); return SDV_ERR_HIP; }
         return rc;
     }
     /* A cold chain cannot be predicted: its first frame is decoded alone, with the full kernel (again while sweeps are owed to it: nothing is tuned, the
@@ -298,19 +279,19 @@ struct Stc007FrameCall {
         RoundLists d;
         { const int rc = upload_round_lists(p, &d); if (rc != SDV_OK) return rc; }
         sdv::AnchorArgs aa; aa.states_in = e->d_states_in; aa.states_out = e->d_states_out; aa.list = d.anchors; aa.n = (int)p.anchors.size(); aa.flag = e->d_flag;
-        RT_CHECK(rt::launch_anchor(aa, s));
+        RT_CHECK(RT_LAUNCH_ITEMS(sdv_k_anchor, sdv::anchor_body, 0, aa.n, 256, s, aa));
         if (!p.patches.empty()) {
             sdv::RefPatchArgs ra; ra.states_in = e->d_states_in; ra.patch = d.patches; ra.n = (int)p.patches.size();
-            RT_CHECK(rt::launch_ref_patch(ra, s));
+            RT_CHECK(RT_LAUNCH_ITEMS(sdv_k_ref_patch, sdv::ref_patch_body, 0, ra.n, 256, s, ra));
         }
         pa.first = first; pa.hi = hi; pa.first_of = d.first_of;
         if (use_skip) { RT_CHECK(rt::dfill_bytes(e->d_skip + first, 0, (size_t)(hi - first), s)); pa.skip = e->d_skip; }
-        RT_CHECK(rt::launch_predict(pa, s));
+        RT_CHECK(launch_predict(pa, s));
         pa.skip = NULL;
         if (p.any_moved && !p.anchors.empty() && !dev_env("SDV_SCHED_NO_CARRY")) {     /* the history moves on (sdv_k_hist_carry): frames it reaches are decoded in this round too */
             RT_CHECK(rt::dfill_bytes(e->d_patched + first, 0, (size_t)(hi - first), s));
             sdv::HistCarryArgs ha; ha.states_in = e->d_states_in; ha.refs = e->d_refs; ha.anchors = d.anchors; ha.n_anchors = (int)p.anchors.size(); ha.hi = hi; ha.patched = e->d_patched; ha.skip = use_skip ? e->d_skip.p : NULL;
-            RT_CHECK(rt::launch_hist_carry(ha, s));
+            RT_CHECK(RT_LAUNCH_ITEMS(sdv_k_hist_carry, sdv::hist_carry_body, 0, ha.n_anchors, 64, s, ha));
             RT_CHECK(rt::d2h_pinned(e->h_patched + first, e->d_patched + first, (size_t)(hi - first), s));
             const size_t reached = p.add_carried(e->h_patched);
             if (trace) fprintf(stderr, "[sched]   the history moved on into %zu more frames\n", reached);
@@ -379,7 +360,7 @@ static int stc007_binarize_frames_impl(sdv_engine *e, const uint8_t *luma, size_
     if (first < n) {
         pa.first = first; pa.hi = n; pa.first_of = NULL;
         if (states_owed) { a.predict_in_kernel = 1; a.base_frame = first; a.base = e->chain; }
-        else RT_CHECK(rt::launch_predict(pa, s));
+        else RT_CHECK(launch_predict(pa, s));
         rc = c.run_round_range(first, n, worn); if (rc != SDV_OK) return rc;
         a.predict_in_kernel = 0;
     }
@@ -401,7 +382,7 @@ static int stc007_binarize_frames_impl(sdv_engine *e, const uint8_t *luma, size_
             states_owed = false;
             RT_CHECK(rt::h2d(e->d_states_in, &e->chain, sizeof(sdv_v2d_state), s));
             pa.first = 0; pa.hi = n; pa.first_of = NULL;
-            RT_CHECK(rt::launch_predict(pa, s));
+            RT_CHECK(launch_predict(pa, s));
         }
         plan.take_flags(flag);
         plan.release_crowds();

@@ -17,20 +17,6 @@
 #include <algorithm>
 #include <cstdlib>
 
-namespace rt {
-#ifndef SDV_EMU
-#define RT_LAUNCH64(kernel, grid, args, stream) do { if ((grid) > 0) { hipLaunchKernelGGL(kernel, dim3((unsigned)(grid)), dim3(64), 0, (stream), (args)); RT_CHECK(hipGetLastError()); } } while (0)
-static inline hipError_t dzero(void *p, size_t n, stream_t s) { return hipMemsetAsync(p, 0, n, s); }
-static inline hipError_t ssync(stream_t s) { return hipStreamSynchronize(s); }
-static inline hipError_t d2h_async(void *h, const void *d, size_t n, stream_t s) { return hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, s); }
-#else
-#define RT_LAUNCH64(kernel, grid, args, stream) do { if ((grid) > 0) { auto _a = (args); emu::launch((unsigned)(grid), [_a]() { kernel(_a); }); } } while (0)
-static inline int dzero(void *p, size_t n, stream_t) { memset(p, 0, n); return 0; }
-static inline int ssync(stream_t) { return 0; }
-static inline int d2h_async(void *h, const void *d, size_t n, stream_t) { memcpy(h, d, n); return 0; }
-#endif
-} // namespace rt
-
 namespace sdvs {
 /* circarray<uint8_t, 65> (circbuffer.h:30-140) */
 struct Ring {
@@ -334,19 +320,9 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
     cfg.ignore_crc = st.use_ecc == 0; cfg.max_unch_14 = st.max_unch_14; cfg.max_unch_16 = st.max_unch_16;
     cfg.mask_seams = st.mask_seams != 0; cfg.broken_mask_dur = st.broke_mask; cfg.fix_cut_above = st.top_line_fix != 0;
     cfg.preset_sample_rate = st.sample_rate_preset;
-#ifdef SDV_EMU
-    const size_t max_waves = 2;
-#else
     /* as many waves as are resident at once: they share the turns through a work queue */
-    if (t->resident_waves == 0) {
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sdv_k_stitch_step, 64, 0) != hipSuccess || per_cu <= 0) per_cu = 8;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess || cus <= 0) cus = 256;
-        t->resident_waves = (size_t)per_cu * (size_t)cus;
-        if (t->resident_waves > 8192) t->resident_waves = 8192;
-    }
+    if (t->resident_waves == 0) t->resident_waves = rt::resident_waves(sdv_k_stitch_step, e->device);
     const size_t max_waves = t->resident_waves;
-#endif
     auto grow_seg = [&](size_t n_seg_need) -> int { return stitch_grow_seg(e, t, n_seg_need); };
     auto grow_ws = [&](size_t waves) -> int {
         RT_CHECK(t->d_ws.reserve(waves * sdvs::QCAP));
@@ -415,12 +391,7 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
         sdvs::AnalyzeArgs aa; aa.src = src; aa.seg_end = t->d_seg_end; aa.n_seg = (uint32_t)est_seg; aa.ctl = t->d_ctl; aa.cfg = cfg; aa.fl = t->d_fl; aa.brief = t->d_brief; aa.fields = t->d_fields;
         aa.timing = NULL;
         aa.direct = direct_now ? t->d_direct.p : NULL; aa.direct_ofs = t->direct_ofs; aa.direct_n = t->direct_n;
-#ifndef SDV_EMU
-        if (e->profiling && queue_now) {
-            if (!e->have_events) { RT_CHECK(hipEventCreate(&e->ev0)); RT_CHECK(hipEventCreate(&e->ev1)); e->have_events = true; }
-            RT_CHECK(hipEventRecord(e->ev0, s));
-        }
-#endif
+        if (e->profiling && queue_now) RT_CHECK(e->timer.start(s));
         if (queue_now) RT_LAUNCH64(sdv_k_stitch_analyze, est_seg, aa, s);
         sdvs::PredictStArgs pa; pa.fields = t->d_fields; pa.fl = t->d_fl; pa.out = t->d_chain[0]; pa.tmpl = t->d_chain0; pa.first = 0; pa.n = (uint32_t)(est_seg - 2);
         pa.ctl = t->d_ctl; pa.est_seg = (uint32_t)est_seg;
@@ -486,15 +457,10 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
         /* 2. frame-local analysis */
         sdvs::AnalyzeArgs aa; aa.src = src; aa.seg_end = t->d_seg_end; aa.n_seg = (uint32_t)n_seg; aa.ctl = NULL; aa.cfg = cfg; aa.fl = t->d_fl; aa.brief = t->d_brief; aa.fields = t->d_fields;
         aa.direct = NULL; aa.direct_ofs = 0; aa.direct_n = 0;
-#ifndef SDV_EMU
-        if (e->profiling) {
-            if (!e->have_events) { RT_CHECK(hipEventCreate(&e->ev0)); RT_CHECK(hipEventCreate(&e->ev1)); e->have_events = true; }
-            RT_CHECK(hipEventRecord(e->ev0, s));
-        }
-#endif
+        if (e->profiling) RT_CHECK(e->timer.start(s));
         aa.timing = NULL;
         rt::DevBuf<unsigned long long> d_atiming;
-        if (dev_env("SDV_STITCH_TIMING")) { RT_CHECK(d_atiming.reserve(n_seg * 8)); RT_CHECK(rt::dzero(d_atiming, n_seg * 8 * sizeof(unsigned long long), s)); aa.timing = d_atiming; }
+        if (dev_env("SDV_STITCH_TIMING")) { RT_CHECK(d_atiming.reserve(n_seg * 8)); RT_CHECK(rt::dfill_bytes(d_atiming, 0, n_seg * 8 * sizeof(unsigned long long), s)); aa.timing = d_atiming; }
         RT_LAUNCH64(sdv_k_stitch_analyze, n_seg, aa, s);
         if (aa.timing) {        /* developer aid: mean cycles per phase of the analysis of a frame */
             std::vector<unsigned long long> tm(n_seg * 8);
@@ -549,7 +515,7 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
                  (uint64_t)n_steps * t->guess_pairs <= (uint64_t)pairs_cap && (uint64_t)n_steps * t->guess_frasm <= (uint64_t)frames_cap;
     sp.direct_pairs = try_direct ? out_pairs : NULL; sp.direct_frasm = try_direct ? out_frames : NULL;
     rt::DevBuf<unsigned long long> d_timing;
-    if (dev_env("SDV_STITCH_TIMING")) { RT_CHECK(d_timing.reserve(n_steps * 8)); RT_CHECK(rt::dzero(d_timing, n_steps * 8 * sizeof(unsigned long long), s)); }
+    if (dev_env("SDV_STITCH_TIMING")) { RT_CHECK(d_timing.reserve(n_steps * 8)); RT_CHECK(rt::dfill_bytes(d_timing, 0, n_steps * 8 * sizeof(unsigned long long), s)); }
     sp.timing = d_timing;
     HT(3);
     bool plain = false;     /* every frame and every turn of the call like those of the last one: the two histories stay what they are, no replay needed */
@@ -601,7 +567,7 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
         RT_CHECK(rt::h2d(t->d_prob_order, prob_order.data(), n_steps, s));
         if (!prob_res_sent) { RT_CHECK(rt::h2d(t->d_prob_res, prob_res.data(), n_steps, s)); prob_res_sent = true; }
         sp.n_work = (uint32_t)nw; sp.first_round = 0;
-        RT_CHECK(rt::dzero(t->d_next_work, sizeof(uint32_t), s));
+        RT_CHECK(rt::dfill_bytes(t->d_next_work, 0, sizeof(uint32_t), s));
         RT_LAUNCH64(sdv_k_stitch_step, std::min(nw, waves_cap), sp, s);
         RT_CHECK(rt::d2h_pinned(info, t->d_info, n_steps * sizeof(sdvs::StepInfo), s));
         t->info.rounds++; t->info.steps_launched += (uint32_t)nw;
@@ -698,7 +664,7 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
         std::vector<uint32_t> aofs(n_steps), acnt(n_steps);
         if (t->line_out) {
             RT_CHECK(rt::reserve_all(n_steps, n_steps + n_steps / 4 + 16, t->d_asm_cnt, t->d_asm_ofs));
-            RT_CHECK(rt::dzero(t->d_next_work, sizeof(uint32_t), s));
+            RT_CHECK(rt::dfill_bytes(t->d_next_work, 0, sizeof(uint32_t), s));
             sp.asm_cnt = t->d_asm_cnt; sp.asm_lines = NULL; sp.asm_ofs = NULL; sp.blocks = NULL; sp.block_ofs = NULL;
             RT_LAUNCH64(sdv_k_stitch_step, std::min(n_steps, waves_cap), sp, s);
             RT_CHECK(rt::d2h(acnt.data(), t->d_asm_cnt, n_steps * sizeof(uint32_t), s));
@@ -721,7 +687,7 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
             RT_CHECK(rt::h2d(t->d_block_ofs, bofs.data(), n_steps * sizeof(uint32_t), s));
             sp.blocks = t->block_out; sp.block_ofs = t->d_block_ofs;
         }
-        RT_CHECK(rt::dzero(t->d_next_work, sizeof(uint32_t), s));
+        RT_CHECK(rt::dfill_bytes(t->d_next_work, 0, sizeof(uint32_t), s));
         RT_LAUNCH64(sdv_k_stitch_step, std::min(n_steps, waves_cap), sp, s);
         RT_CHECK(rt::ssync(s));             /* the host vectors above go out of scope with the call */
     }
@@ -729,15 +695,10 @@ static int stitch_frames_impl(sdv_engine *e, const sdv_line_rec *lines, size_t n
         t->guess_pairs = same ? info[0].n_pairs : 0; t->guess_frasm = same ? info[0].n_frasm : 0;
         if (all_bits & sdvs::SI_OVERFLOW) t->guess_pairs = t->guess_frasm = 0;
     }
-#ifndef SDV_EMU
     if (e->profiling) {
-        float ms = 0.f;
-        RT_CHECK(hipEventRecord(e->ev1, s));
-        RT_CHECK(hipEventSynchronize(e->ev1));
-        RT_CHECK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-        t->info.device_ms = ms;
+        RT_CHECK(e->timer.stop(s));
+        RT_CHECK(e->timer.elapsed_ms(&t->info.device_ms));      /* (once per call) */
     }
-#endif
 
     HT(5);
     /* 5. what the next call inherits */

@@ -96,7 +96,7 @@ int sdv_vis_render_lines(sdv_engine *e, int kind, const void *recs, size_t n_rec
     const size_t n_cells = (size_t)g.h * g.cells_per_row, stride = (n_cells + 31) / 32;
     RT_CHECK(t->d_frame_adv0.reserve((size_t)ends + 1, (size_t)ends + 1 + ends / 4));
     RT_CHECK(t->d_wmask.reserve((size_t)ends * stride, (size_t)ends * stride + (size_t)ends * stride / 4));
-    RT_CHECK(rt::dzero(t->d_wmask, (size_t)ends * stride * sizeof(uint32_t), s));
+    RT_CHECK(rt::dfill_bytes(t->d_wmask, 0, (size_t)ends * stride * sizeof(uint32_t), s));
     a.frame_adv0 = t->d_frame_adv0; a.n_frames = ends; a.out = out_canvases; a.wmask = t->d_wmask; a.wmask_stride = (uint32_t)stride; a.canvas = t->d_canvas[kind];
     VIS_LAUNCH(index, n_chunks);
     VIS_LAUNCH(draw, n_chunks);
@@ -136,7 +136,7 @@ static int vis_render_rows(sdv_engine *e, int kind, bool asm_lines, const void *
     RT_CHECK(t->d_last.reserve(n_cells * n_frames, n_cells * (n_frames + n_frames / 4 + 1)));
     RT_CHECK(rt::h2d(t->d_frame_ofs, ofs.data(), (n_frames + 1) * sizeof(uint32_t), s));
     RT_CHECK(rt::ssync(s));             /* the host vector goes out of scope with the call */
-    RT_CHECK(rt::dzero(t->d_wmask, n_frames * stride * sizeof(uint32_t), s));
+    RT_CHECK(rt::dfill_bytes(t->d_wmask, 0, n_frames * stride * sizeof(uint32_t), s));
     if (asm_lines) {
         sdvvis::AsmArgs b; b.lines = (const sdv_asm_line_rec *)blocks; b.frame_ofs = t->d_frame_ofs; b.n_frames = (uint32_t)n_frames; b.kind = kind; b.out = out_canvases;
         b.wmask = t->d_wmask; b.wmask_stride = (uint32_t)stride;

@@ -381,6 +381,39 @@ def test_gpu_full_size_round_trip(ei):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("ei", [False, True])
+def test_gpu_stitch_across_batches_equals_calls_of_one_batch(ei):
+    """2 x 1024 + 5 frames in one call are three internal batches (SDV_P16_STITCH_BATCH = 1024, pcm16_engine.inc): the analysis runs ahead on a side
+    stream and the in-order kernels follow on three streams, batch after batch (EI: the first batch is analysed alone, the padding hint).  The same
+    records in calls of 512 frames on another engine are one batch per call and no side stream.  Pairs, frame descriptors and counts are the same bytes."""
+    import torch
+    from sdvpcmdecoder_amd import Engine
+    n, period, per_call = 2 * 1024 + 5, 16, 512
+    kw = dict(seed=90 + ei, ei=ei, cut=(6, 9), tail_cut=(3, 4), rate_44100=True)
+    base, _ = p16.make_stream(period, **kw)
+    tiles = []
+    for t in range(n // period):
+        b = base.copy()
+        b["frame_number"] += period * t
+        tiles.append(b)
+    tiles.append(p16.make_stream(n % period, first_frame=1 + period * (n // period), **kw)[0])
+    recs = np.concatenate(tiles)
+    st = p16.default_settings(format=p16.FORMAT_EI if ei else p16.FORMAT_SI)
+    want_p, want_f = _gpu_run(Engine(0), recs, st, torch)
+    assert len(want_f) == n and len(want_p) == n * 1470
+    eng = Engine(0)
+    got_p, got_f = [], []
+    step = per_call // period * len(base)           # records of 512 frames: every call ends with an END_FRAME
+    for i, lo in enumerate(range(0, len(recs), step)):
+        p, f = _gpu_run(eng, recs[lo:lo + step], st, torch, configure=i == 0)
+        got_p.append(p.copy())
+        got_f.append(f.copy())
+    assert [len(f) for f in got_f] == [per_call] * (n // per_call) + [n % per_call]
+    pairs, frames = np.concatenate(got_p), np.concatenate(got_f)
+    assert pairs.tobytes() == want_p.tobytes() and frames.tobytes() == want_f.tobytes(), _diff(pairs, frames, want_p, want_f)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ei", [False, True])
 def test_gpu_video_to_audio(ei):
     """The whole PCM-16x0 path on the device - video frames -> sdv_pcm16x0_binarize_frames -> sdv_pcm16x0_stitch_frames - against the
     oracle's two halves chained on the CPU, and against the audio the tape was made from: a 486-row capture shows 243 of the 245 PCM

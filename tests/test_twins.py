@@ -87,14 +87,14 @@ COVERED_BY = {
     # refusals that are decided only after kernels have written into the caller's buffers (inside their stated capacity): nothing is made to run on the
     # GPU for the sake of a refusal unless the code shows that it comes first
     "test_stitch_kernel::test_emu_pipelined_call_reports_what_the_host_would_have_refused":
-        "emulator only: the refusal (stitch_engine.inc:516) is decided behind the read-back of a pipelined round whose turn kernel has already written the "
-        "caller's buffers (direct_pairs = out_pairs, stitch_engine.inc:434-436)",
+        "emulator only: the refusal (stitch_engine.inc:482) is decided behind the read-back of a pipelined round whose turn kernel has already written the "
+        "caller's buffers (direct_pairs = out_pairs, stitch_engine.inc:405-407)",
     "test_pcm1::test_emu_refuses_what_the_reference_never_finishes":
         "emulator only: FE_FOREIGN is read back (pcm1_engine.inc:140, :150) after the frame kernel has written pairs and descriptors to the caller (:120-124)",
     "test_pcm16::test_emu_refuses_what_the_reference_never_finishes":
-        "emulator only: FE_FOREIGN is read back (pcm16_engine.inc:361, :383) after the emit kernels have written pairs and descriptors to the caller (:345)",
+        "emulator only: FE_FOREIGN is read back (pcm16_engine.inc:319, :339) after the emit kernels have written pairs and descriptors to the caller (:305)",
     # argument checks of the per-line entries: host code ahead of any device work, the same in both builds; not among the call-by-call tests twinned so far
-    "test_stc_lines::test_emu_lines_refuse_bad_arguments": "emulator only: the checks of sdv_binarize_lines are the host's, ahead of its first launch (engine.inc:712-719)",
+    "test_stc_lines::test_emu_lines_refuse_bad_arguments": "emulator only: the checks of sdv_binarize_lines are the host's, ahead of its first launch (engine.inc:510-517)",
     "test_pcm1_front::test_emu_argument_checks": "emulator only: the checks of sdv_pcm1_binarize_lines are the host's, ahead of its launch (pcm1_engine.inc:221-227)",
     "test_pcm16_front::test_emu_lines_argument_checks":
         "emulator only: the checks of sdv_pcm16x0_binarize_lines are the host's, ahead of its launch (pcm16_frames_engine.inc:41-47); the rows nothing is preset for "
