@@ -29,6 +29,14 @@
  *       the control line, 490 / 588), top field first, black 30, white 200.  One frame more than the samples fill is made from no pairs: it plays
  *       the 112 lines of interleave delay out.  `emphasis` and `nocopy` set the bits of the control block (the samples are not pre-emphasised).
  *       Prints `n_frames width height`; `decode_tape wav <out.luma> 720 <height> <n_frames> <back.wav>` gives the samples back
+ *   decode_tape encode <in.wav> <out.luma> pcm1|pcm16si|pcm16ei [bff] [emphasis] [44100]
+ *       the same for the marker-less formats: -> sdv_encode_markerless_frames -> frames of a PCM-1 tape (492 rows: one Header line and the 245
+ *       data lines of either field) or of a PCM-1630 tape in the SI or EI interleave (490 rows), 720 pixels wide, data window 4 .. 716, black 30,
+ *       white 200, top field first or, with `bff`, bottom field first.  `emphasis` and `44100` set Control Bits of a PCM-16x0 tape (without
+ *       `44100` it says 44 056 Hz).  As many frames as the samples fill, the rest of the last one silence.  Prints `n_frames width height`
+ *   decode_tape frames <luma.raw> <width> <height> <n_frames> pcm1|pcm16si|pcm16ei tff|bff <pairs.out>
+ *       8-bit luma frames of a marker-less format -> sdv_decode_frames (NEW_FILE | END_FILE, no audio stage) -> PCMSamplePair records: what reads
+ *       the tapes of `encode` back
  *
  * Build (host code only, any C++ compiler): g++ -std=c++17 -O2 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude examples/decode_tape.cpp
  *        -Lsdvpcmdecoder_amd -lsdvpcm_hip -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$ORIGIN/../sdvpcmdecoder_amd' (build.py: build_example).
@@ -61,6 +69,22 @@ static bool write_file(const char *path, const void *p, size_t n)
     bool ok = fwrite(p, 1, n, f) == n;
     fclose(f);
     return ok;
+}
+/* the data chunk of a RIFF/WAVE file with 16-bit stereo PCM: where its pairs begin in `in`, and how many there are */
+static bool read_wav(const char *path, std::vector<uint8_t> &in, size_t *data_at, size_t *n_pairs)
+{
+    if (!read_file(path, in) || in.size() < 12 || memcmp(in.data(), "RIFF", 4) || memcmp(in.data() + 8, "WAVE", 4)) { fprintf(stderr, "cannot read %s as a WAV file\n", path); return false; }
+    size_t at = 12, data_len = 0; unsigned channels = 0, bits = 0;
+    *data_at = 0;
+    while (at + 8 <= in.size()) {
+        const size_t len = (size_t)in[at + 4] | (size_t)in[at + 5] << 8 | (size_t)in[at + 6] << 16 | (size_t)in[at + 7] << 24;
+        if (!memcmp(in.data() + at, "fmt ", 4) && at + 8 + 16 <= in.size()) { channels = in[at + 10] | in[at + 11] << 8; bits = in[at + 22] | in[at + 23] << 8; }
+        if (!memcmp(in.data() + at, "data", 4)) { *data_at = at + 8; data_len = len < in.size() - *data_at ? len : in.size() - *data_at; break; }
+        at += 8 + len + (len & 1);
+    }
+    if (!*data_at || channels != 2 || bits != 16) { fprintf(stderr, "%s: 16-bit stereo PCM is what a tape holds\n", path); return false; }
+    *n_pairs = data_len / 4;
+    return true;
 }
 template <class T> static int download(const T *dev, size_t n, const char *path)
 {
@@ -241,6 +265,70 @@ int main(int argc, char **argv)
         rc = download(d_luma, luma_bytes, argv[11]);
         printf("%d %d %d\n", out_w, out_h, doubled);
         (void)hipFree(d_video); (void)hipFree(d_luma);
+    } else if (mode == "frames" && argc == 9) {
+        const int width = atoi(argv[3]), height = atoi(argv[4]), n = atoi(argv[5]);
+        const std::string fmt = argv[6], order = argv[7];
+        const int pcm_type = fmt == "pcm1" ? SDV_PCM_PCM1 : fmt == "pcm16si" || fmt == "pcm16ei" ? SDV_PCM_PCM16X0 : -1;
+        if (pcm_type < 0 || (order != "tff" && order != "bff") || n <= 0) { fprintf(stderr, "usage: see the header of examples/decode_tape.cpp\n"); return 1; }
+        if (!read_file(argv[2], in) || in.size() != (size_t)width * height * n) { fprintf(stderr, "cannot read %s\n", argv[2]); return 1; }
+        const uint8_t field_order = order == "bff" ? 2 : 1;
+        SDV_OKAY(sdv_set_pcm_type(eng, pcm_type, 0));
+        SDV_OKAY(sdv_set_mode(eng, SDV_MODE_NORMAL));
+        size_t frame_bytes = 0;
+        if (pcm_type == SDV_PCM_PCM1) {
+            sdv_pcm1_stitch_settings st; sdv_default_pcm1_stitch_settings(&st);
+            st.field_order = field_order;
+            SDV_OKAY(sdv_set_pcm1_stitch_settings(eng, &st));
+            frame_bytes = sizeof(sdv_frame_asm_pcm1);
+        } else {
+            sdv_pcm16x0_stitch_settings st; sdv_default_pcm16x0_stitch_settings(&st);
+            st.format = fmt == "pcm16ei" ? SDV_P16_FORMAT_EI : SDV_P16_FORMAT_SI; st.field_order = field_order;
+            SDV_OKAY(sdv_set_pcm16x0_stitch_settings(eng, &st));
+            frame_bytes = sizeof(sdv_frame_asm_pcm16x0);
+        }
+        uint8_t *d_luma = NULL; void *d_frames = NULL;
+        const size_t pairs_cap = ((size_t)n + 2) * 2100 + 8192, frames_cap = (size_t)n + 16;
+        HIP_OK(hipMalloc((void **)&d_luma, in.size()));
+        HIP_OK(hipMalloc((void **)&d_pairs, pairs_cap * sizeof(sdv_sample_pair)));
+        HIP_OK(hipMalloc(&d_frames, frames_cap * frame_bytes));
+        HIP_OK(hipMemcpy(d_luma, in.data(), in.size(), hipMemcpyHostToDevice));
+        SDV_OKAY(sdv_decode_frames(eng, pcm_type, d_luma, (size_t)width, (size_t)width * height, width, height, n, 1, SDV_FLAG_NEW_FILE | SDV_FLAG_END_FILE,
+                                   d_pairs, pairs_cap, &n_pairs, d_frames, frames_cap, &n_frames, NULL, 0, 0, 0, NULL, 0, NULL, NULL, NULL));
+        HIP_OK(hipDeviceSynchronize());
+        rc = download(d_pairs, n_pairs, argv[8]);
+        printf("frames (%s, %s): %d frames -> %zu sample pairs, %zu frame descriptors\n", fmt.c_str(), order.c_str(), n, n_pairs, n_frames);
+        (void)hipFree(d_luma); (void)hipFree(d_frames);
+    } else if (mode == "encode" && argc >= 5 && (!strcmp(argv[4], "pcm1") || !strcmp(argv[4], "pcm16si") || !strcmp(argv[4], "pcm16ei"))) {
+        sdv_encode_markerless_desc d; memset(&d, 0, sizeof(d));
+        const bool pcm1 = !strcmp(argv[4], "pcm1");
+        d.format = pcm1 ? SDV_ENC_FMT_PCM1 : !strcmp(argv[4], "pcm16si") ? SDV_ENC_FMT_PCM16X0_SI : SDV_ENC_FMT_PCM16X0_EI;
+        d.header_lines = pcm1 ? 1 : 0;
+        d.black = 30; d.white = 200; d.width = 720; d.data_start = 4; d.data_stop = 716;
+        for (int i = 5; i < argc; i++) {
+            const std::string opt = argv[i];
+            if (opt == "bff") d.field_order = SDV_ENC_BFF;
+            else if (opt == "emphasis" && !pcm1) d.ctrl_flags |= SDV_ENC_ML_EMPHASIS;
+            else if (opt == "44100" && !pcm1) d.ctrl_flags |= SDV_ENC_ML_RATE_44100;
+            else { fprintf(stderr, "usage: see the header of examples/decode_tape.cpp\n"); return 1; }
+        }
+        size_t per_frame = 0; int lines_per_field = 0;
+        d.height = 2;                       /* (any: the geometry tells the lines of a field, the height follows from them) */
+        const int grc = sdv_encode_markerless_geometry(&d, &per_frame, &lines_per_field, NULL);
+        if (grc != SDV_OK) { fprintf(stderr, "sdv_encode_markerless_geometry = %d: %s\n", grc, sdv_last_error(NULL)); return 3; }
+        d.height = 2 * lines_per_field;
+        size_t data_at = 0, n_in = 0;
+        if (!read_wav(argv[2], in, &data_at, &n_in)) return 1;
+        const int n = n_in ? (int)((n_in + per_frame - 1) / per_frame) : 1;     /* (no delay to play out: a frame is made from its own pairs) */
+        const size_t frame_bytes = (size_t)d.width * d.height;
+        int16_t *d_pcm = NULL; uint8_t *d_luma = NULL;
+        HIP_OK(hipMalloc((void **)&d_pcm, n_in * 4 + 4));
+        HIP_OK(hipMalloc((void **)&d_luma, frame_bytes * n));
+        HIP_OK(hipMemcpy(d_pcm, in.data() + data_at, n_in * 4, hipMemcpyHostToDevice));
+        SDV_OKAY(sdv_encode_markerless_frames(eng, &d, d_pcm, n_in, n, d_luma, (size_t)d.width, frame_bytes, NULL));
+        HIP_OK(hipDeviceSynchronize());
+        rc = download(d_luma, frame_bytes * n, argv[3]);
+        printf("%d %d %d\n", n, d.width, d.height);
+        (void)hipFree(d_pcm); (void)hipFree(d_luma);
     } else if (mode == "encode" && argc >= 4) {
         sdv_encode_desc d; memset(&d, 0, sizeof(d));
         d.ctrl_block = 1; d.black = 30; d.white = 200; d.width = 720; d.data_start = 12; d.data_stop = 708;
@@ -258,18 +346,9 @@ int main(int argc, char **argv)
         const int grc = sdv_encode_geometry(&d, &per_frame, &lines_per_field, NULL);
         if (grc != SDV_OK) { fprintf(stderr, "sdv_encode_geometry = %d: %s\n", grc, sdv_last_error(NULL)); return 3; }
         d.height = 2 * lines_per_field;
-        /* the data chunk of a RIFF/WAVE file with 16-bit stereo PCM */
-        if (!read_file(argv[2], in) || in.size() < 12 || memcmp(in.data(), "RIFF", 4) || memcmp(in.data() + 8, "WAVE", 4)) { fprintf(stderr, "cannot read %s as a WAV file\n", argv[2]); return 1; }
-        size_t at = 12, data_at = 0, data_len = 0; unsigned channels = 0, bits = 0;
-        while (at + 8 <= in.size()) {
-            const size_t len = (size_t)in[at + 4] | (size_t)in[at + 5] << 8 | (size_t)in[at + 6] << 16 | (size_t)in[at + 7] << 24;
-            if (!memcmp(in.data() + at, "fmt ", 4) && at + 8 + 16 <= in.size()) { channels = in[at + 10] | in[at + 11] << 8; bits = in[at + 22] | in[at + 23] << 8; }
-            if (!memcmp(in.data() + at, "data", 4)) { data_at = at + 8; data_len = len < in.size() - data_at ? len : in.size() - data_at; break; }
-            at += 8 + len + (len & 1);
-        }
-        if (!data_at || channels != 2 || bits != 16) { fprintf(stderr, "%s: 16-bit stereo PCM is what a tape holds\n", argv[2]); return 1; }
-        const size_t n_in = data_len / 4;
-        const int n = (int)((n_in + per_frame - 1) / per_frame) + 1;           /* ... and the frame that plays the delay out */
+        size_t data_at = 0, n_in = 0;
+        if (!read_wav(argv[2], in, &data_at, &n_in)) return 1;
+        const int n = (int)((n_in + per_frame - 1) / per_frame) + 1;          /* ... and the frame that plays the delay out */
         const size_t frame_bytes = (size_t)d.width * d.height;
         int16_t *d_pcm = NULL; uint8_t *d_luma = NULL;
         HIP_OK(hipMalloc((void **)&d_pcm, n_in * 4 + 4));

@@ -20,14 +20,15 @@
 extern "C" {
 #endif
 
-#define SDV_ABI_VERSION 9   /* 2: output capacities on sdv_binarize_frames / sdv_pcm1_binarize_lines; 3: sdv_audio_process, sdv_wav_pack, sdv_wav_header, sdv_decode_frames (additions only);
+#define SDV_ABI_VERSION 10  /* 2: output capacities on sdv_binarize_frames / sdv_pcm1_binarize_lines; 3: sdv_audio_process, sdv_wav_pack, sdv_wav_header, sdv_decode_frames (additions only);
                              * 4: sdv_pcm16x0_binarize_lines, sdv_audio_stalled, sdv_set_frame_flags, sdv_double_width, sdv_vis_render_lines (additions); the calls that used to refuse PCM-16x0 frames of the wrong size and the
                              * AudioProcessor's dead ends now follow the reference; the PCM-16x0 stitch state blob grew by conv_queue's remainder;
                              * 5: sdv_run_info grew by frames_met (at its end), sdv_binarize_lines (addition);
                              * 6: sdv_deemphasis_coeffs, sdv_set_deemphasis, sdv_reset_deemphasis, sdv_audio_deemphasis (additions only);
                              * 7: sdv_resample_taps, sdv_set_resample, sdv_reset_resample, sdv_audio_resample_pending, sdv_audio_resample_room, sdv_audio_resample (additions only);
                              * 8: sdv_ingest_geometry, sdv_ingest_frames (additions only);
-                             * 9: sdv_encode_geometry, sdv_encode_frames, sdv_reset_encoder (additions only) */
+                             * 9: sdv_encode_geometry, sdv_encode_frames, sdv_reset_encoder (additions only);
+                             * 10: sdv_encode_markerless_geometry, sdv_encode_markerless_frames (additions only) */
 
 /* ---- status codes ---------------------------------------------------------------------------
  * 0..4 mirror Binarizer::LB_RET_* (binarizer.h:268-275); 16.. mirror STC007Deinterleaver::DI_RET_*
@@ -430,6 +431,61 @@ int sdv_encode_geometry(const sdv_encode_desc *d, size_t *pairs_per_frame, int *
 int sdv_encode_frames(sdv_engine *e, const sdv_encode_desc *d, const int16_t *pcm, size_t n_pairs, int n_frames,
                       uint8_t *dst, size_t dst_row_stride, size_t dst_frame_stride, void *stream);
 int sdv_reset_encoder(sdv_engine *e);
+
+/* ---- encode, the marker-less formats: 16-bit PCM -> Sony PCM-1 and PCM-1600/1610/1630 ("PCM-16x0") video frames, on the device -------------------
+ * The write side of the other two formats the frame entries read:
+ *   WAV -> sdv_encode_markerless_frames -> sdv_decode_frames -> the same samples (PCM-1: what its companding keeps of them).
+ * `pcm` is interleaved int16 L R as for sdv_encode_frames.  A frame of either format is made from its own 1470 pairs alone: frame f of a call takes
+ * the pairs 1470 f .. 1470 f + 1469, the first 735 of them the field that is first in time.  Where n_pairs is smaller the rest is silence; pairs
+ * beyond that count are not read.
+ *
+ * SDV_ENC_FMT_PCM1 (pcm1line.h:59-96, pcm1datablock.cpp:309-348, pcm1deinterleaver.cpp:150-278).
+ *   Word of a sample s, 13 bits: 0x1000 | ((s >> 2) & 0x0FFF) where -8192 <= s < 8192, else (s >> 4) & 0x0FFF; silence is 0x1000.  What comes back
+ *     is s & ~3 or s & ~15 - a truncation; dither is the caller's business.
+ *   Interleave.  A field is 735 sub-lines of one pair each, words L R; line j of its 245 data lines is the sub-lines 3 j, 3 j + 1, 3 j + 2, six words.
+ *     Pair n = 0 .. 734 of the field: itl = n / 92, p = n % 92, wp = p >> 1, even = p & 1; it sits on sub-line
+ *     92 itl + (((itl % 2 == 0) == (even == 1)) ? 0 : 46) + wp.  That is a bijection onto 0 .. 734; interleave block 7 holds 91 pairs.
+ *   CRC.  CRC-16/CCITT-FALSE (polynomial 0x1021, initial value 0xFFFF, no reflection) over the six inverted 13-bit words, MSB first, the result
+ *     inverted; a silent line's is 0xECBF.
+ *   Cells.  A line is 94 cells: the six words with 13 bits each and the 16 CRC bits, MSB first; no markers.
+ *   Header line.  Words 0x0666 0x0CCC 0x1999 0x1333 0x0666 0x0CCC, CRC field 0xCCCC (pcm1line.cpp:314-323).  header_lines = 0 .. 8 of them come
+ *     first in every field, the 245 data lines follow.  (Without one the decoder's first-line-duplicate rule takes the first line of a field for bad.)
+ * SDV_ENC_FMT_PCM16X0_SI / _EI (pcm16x0subline.h:90-100, pcm16x0datablock.h:38-91, pcm16x0datablock.cpp:1029-1155).
+ *   Blocks.  A frame is 490 blocks of three pairs, block b its pairs 3 b .. 3 b + 2; the words are the 16-bit samples as they are.
+ *   Sub-lines.  A frame has 1470 sub-lines of three words k = 0 .. 2, the first 735 the field first in time.  Sub-line s carries
+ *       SI: block 35 (s / 105) + s % 35, role (s % 105) / 35, odd = ((s % 35) % 2) == 1;
+ *       EI: block s % 490, role s / 490, odd = (block % 2) == 1.
+ *     With L and R of pair 3 block + k and l_first = ((k & 1) != 0) != odd, word k is: role 0: l_first ? L : R; role 1: L ^ R; role 2: l_first ? R : L.
+ *   CRC.  CRC-16/CCITT-FALSE over a sub-line's three words, MSB first.
+ *   Cells.  Line j of a field's 245 is its sub-lines 3 j .. 3 j + 2, 193 cells: sub-line 3 j on cells 0 .. 63 (three words, then the CRC, MSB first),
+ *     3 j + 1 on 64 .. 127, the Control Bit on cell 128, 3 j + 2 on 129 .. 192.
+ *   Control Bit.  1 on every line but the lines 35 i + 0 .. 35 i + 3 of a field, i = 0 .. 6, where it is 0 on 35 i + 0 with SDV_ENC_ML_EMPHASIS, on
+ *     35 i + 1 with SDV_ENC_ML_RATE_44100 (else the tape says 44056 Hz), on 35 i + 2 with the EI format, on 35 i + 3 with SDV_ENC_ML_CODE.
+ *     (SDV_ENC_ML_EMPHASIS only sets the bit: pre-emphasis of the samples is the caller's.)
+ * Frame.  lines_per_field = 245 + header_lines.  Rows, field order, top_line and the rows without a line are those of sdv_encode_frames.
+ * Raster.  As for sdv_encode_frames with the format's cell count: pixel x is `white` where data_start <= x < data_stop and cell
+ *   ((x - data_start) * CELLS) / (data_stop - data_start) is 1, CELLS = 94 (PCM-1) or 193 (PCM-16x0), else `black`.
+ *
+ * State.  None: a tape made in several calls equals the tape made in one, given calls that start on frame boundaries of the PCM.  The tape of
+ * sdv_encode_frames is neither read nor written; sdv_reset_encoder has nothing to do with these calls.
+ *
+ * sdv_encode_markerless_frames: the contract of sdv_encode_frames - device pointers of any alignment, all work on `stream`, asynchronous, nothing
+ * read back, on the engine's device whatever device is current, only the `width` bytes of every row written - and its refusals, before any launch
+ * and with the destination untouched: SDV_ERR_BAD_ARG for a null d, an unknown format, field order or control bit, n_frames < 0 or above 2^24,
+ * width or height outside 1 .. 32768, data_stop <= data_start, white <= black, the strides and the overlap as there; SDV_ERR_NULL_PCM,
+ * SDV_ERR_NULL_VIDEO.  Also SDV_ERR_BAD_ARG: header_lines > 8; header_lines != 0 with a PCM-16x0 format; ctrl_flags != 0 with PCM-1.
+ * n_frames == 0: SDV_OK, nothing done.  sdv_encode_markerless_geometry is host-only and needs no engine: the same codes for the same descriptor;
+ * *pairs_per_frame = 1470, *lines_per_field = 245 + header_lines, *row_bytes = width; any of the three may be NULL. */
+enum { SDV_ENC_FMT_PCM1 = 0, SDV_ENC_FMT_PCM16X0_SI = 1, SDV_ENC_FMT_PCM16X0_EI = 2 };
+enum { SDV_ENC_ML_EMPHASIS = 1 << 0, SDV_ENC_ML_RATE_44100 = 1 << 1, SDV_ENC_ML_CODE = 1 << 2 };   /* PCM-16x0 Control Bits */
+typedef struct sdv_encode_markerless_desc {
+    uint8_t format, field_order, black, white;        /* SDV_ENC_FMT_*, SDV_ENC_TFF / _BFF, the two levels */
+    uint8_t header_lines, ctrl_flags, _pad[2];        /* PCM-1: 0 .. 8 Header lines on top of every field; PCM-16x0: SDV_ENC_ML_* */
+    int32_t width, height, data_start, data_stop, top_line;
+} sdv_encode_markerless_desc;                         /* 28 bytes */
+int sdv_encode_markerless_geometry(const sdv_encode_markerless_desc *d, size_t *pairs_per_frame, int *lines_per_field, size_t *row_bytes);
+int sdv_encode_markerless_frames(sdv_engine *e, const sdv_encode_markerless_desc *d, const int16_t *pcm, size_t n_pairs, int n_frames,
+                                 uint8_t *dst, size_t dst_row_stride, size_t dst_frame_stride, void *stream);
 
 size_t sdv_records_per_frame(int height);
 /* records one sdv_binarize_frames call emits: n_frames * (height + 3), + 1 with SDV_FLAG_NEW_FILE, + height + 4 with SDV_FLAG_END_FILE */

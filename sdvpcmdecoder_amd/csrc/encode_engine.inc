@@ -1,6 +1,7 @@
 /*
  * encode_engine.inc - host side of sdv_encode_geometry / sdv_encode_frames / sdv_reset_encoder (include/sdvpcm.h): the checks, the tape's
  * state and the two launches of encode_device.h.  Included at the end of engine.inc, so by the one translation unit of either build.
+ * encode_check_buffers and encode_launch_raster also serve encode_markerless_engine.inc.
  */
 
 enum { ENCODE_MAX_DIM = 32768, ENCODE_MAX_FRAMES = 1 << 24 };
@@ -38,6 +39,51 @@ static int encode_geo(const sdv_encode_desc *d, EncodeGeo *g, std::string *why)
     return SDV_OK;
 }
 
+/* The pointers and strides of a call that makes n_frames frames of width x height from at most call_pairs pairs - the checks of sdv_encode_frames
+ * and sdv_encode_markerless_frames behind those of their descriptors.  *used_pairs: the pairs the call reads. */
+static int encode_check_buffers(sdv_engine *e, int width, int height, const int16_t *pcm, size_t n_pairs, uint64_t call_pairs, int n_frames,
+                                const uint8_t *dst, size_t dst_row_stride, size_t dst_frame_stride, size_t *used_pairs)
+{
+    if (!pcm && n_pairs > 0) { set_error(e, "null pcm"); return SDV_ERR_NULL_PCM; }
+    if (!dst) { set_error(e, "null video"); return SDV_ERR_NULL_VIDEO; }
+    const size_t max_stride = (size_t)1 << 32;          /* (keeps the spans below inside 64 bits) */
+    if (dst_row_stride > max_stride || (n_frames > 1 && dst_frame_stride > max_stride)) { set_error(e, "stride above 4 GiB"); return SDV_ERR_BAD_ARG; }
+    const size_t dst_frame = (size_t)(height - 1) * dst_row_stride + (size_t)width;
+    if (dst_row_stride < (size_t)width) { set_error(e, "dst_row_stride smaller than the " + std::to_string(width) + " bytes of a row"); return SDV_ERR_BAD_ARG; }
+    if (n_frames > 1 && dst_frame_stride < dst_frame) { set_error(e, "dst_frame_stride smaller than one frame"); return SDV_ERR_BAD_ARG; }
+    *used_pairs = n_pairs < call_pairs ? n_pairs : (size_t)call_pairs;
+    const uintptr_t s0 = (uintptr_t)pcm, s1 = s0 + 4 * *used_pairs;
+    const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (size_t)(n_frames - 1) * dst_frame_stride + dst_frame;
+    if (*used_pairs && s0 < d1 && d0 < s1) { set_error(e, "pcm and destination overlap"); return SDV_ERR_BAD_ARG; }
+    return SDV_OK;
+}
+
+/* what the raster shows: the packed lines and the cell table of `t`, lpft lines a field with `cells` cells each */
+struct EncodeRaster { int width, height, top_line, lpft, cells; int64_t span; bool bff; uint8_t black, white; };
+
+/* the raster launch of a call (encode_raster_body): the same for every format */
+static int encode_launch_raster(sdv_engine *e, sdv_encoder *t, const EncodeRaster &r, int n_frames, uint8_t *dst, size_t dst_row_stride, size_t dst_frame_stride,
+                                rt::stream_t s)
+{
+    sdv::EncodeRasterArgs a;
+    a.lines = t->d_lines; a.cell_of = t->d_cell_of.p + sdv::ENC_TABLE_PAD;
+    a.dst = dst; a.dst_row_stride = dst_row_stride; a.dst_frame_stride = dst_frame_stride;
+    a.n_frames = n_frames; a.width = r.width; a.height = r.height; a.line_rows = r.height & ~1;
+    a.lpft = r.lpft; a.bff = r.bff;
+    /* any top_line at or beyond these bounds leaves no row with a line, as the bound itself does: no overflow in the kernel */
+    a.top_line = r.top_line < -ENCODE_MAX_DIM ? -ENCODE_MAX_DIM : r.top_line > r.lpft ? r.lpft : r.top_line;
+    a.black4 = 0x01010101u * r.black; a.white4 = 0x01010101u * r.white;
+    /* cells 15 pixels apart are at most 15 * cells / span, rounded up, apart, and a step more at a window edge: beyond 31 the raster's window does not hold them */
+    a.narrow = (15 * (int64_t)r.cells) / r.span + 2 > 31;
+    a.slots = (r.width + 30) / 16;
+    /* threads of the raster launch: a grid stride walks the rest (encode_raster_body) */
+    const uint32_t threads = rt::grid_stride_threads((uint64_t)n_frames * (uint64_t)r.height * (uint64_t)a.slots);
+    const rt::StrideSteps st = rt::stride_steps(threads, (uint32_t)r.height, (uint32_t)a.slots);
+    a.step_f = st.step_f; a.step_r = st.step_r; a.step_c = st.step_c;
+    RT_CHECK(RT_LAUNCH_ITEMS(sdv_k_encode_raster, sdv::encode_raster_body, 0u, threads, 256, s, a));
+    return SDV_OK;
+}
+
 extern "C" {
 
 int sdv_encode_geometry(const sdv_encode_desc *d, size_t *pairs_per_frame, int *lines_per_field, size_t *row_bytes)
@@ -68,18 +114,10 @@ int sdv_encode_frames(sdv_engine *e, const sdv_encode_desc *d, const int16_t *pc
     EncodeGeo g; std::string why;
     const int rc = encode_geo(d, &g, &why);
     if (rc != SDV_OK) { set_error(e, why); return rc; }
-    if (!pcm && n_pairs > 0) { set_error(e, "null pcm"); return SDV_ERR_NULL_PCM; }
-    if (!dst) { set_error(e, "null video"); return SDV_ERR_NULL_VIDEO; }
-    const size_t max_stride = (size_t)1 << 32;          /* (keeps the spans below inside 64 bits) */
-    if (dst_row_stride > max_stride || (n_frames > 1 && dst_frame_stride > max_stride)) { set_error(e, "stride above 4 GiB"); return SDV_ERR_BAD_ARG; }
-    const size_t dst_frame = (size_t)(d->height - 1) * dst_row_stride + (size_t)d->width;
-    if (dst_row_stride < (size_t)d->width) { set_error(e, "dst_row_stride smaller than the " + std::to_string(d->width) + " bytes of a row"); return SDV_ERR_BAD_ARG; }
-    if (n_frames > 1 && dst_frame_stride < dst_frame) { set_error(e, "dst_frame_stride smaller than one frame"); return SDV_ERR_BAD_ARG; }
     const uint64_t n_fields = 2 * (uint64_t)n_frames, n_data = n_fields * (uint64_t)g.lpf, n_lines = n_fields * (uint64_t)g.lpft;
-    const size_t used_pairs = n_pairs < 3 * n_data ? n_pairs : (size_t)(3 * n_data);       /* the pairs the call reads */
-    const uintptr_t s0 = (uintptr_t)pcm, s1 = s0 + 4 * used_pairs;
-    const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (size_t)(n_frames - 1) * dst_frame_stride + dst_frame;
-    if (used_pairs && s0 < d1 && d0 < s1) { set_error(e, "pcm and destination overlap"); return SDV_ERR_BAD_ARG; }
+    size_t used_pairs = 0;                              /* the pairs the call reads */
+    const int rc_buf = encode_check_buffers(e, d->width, d->height, pcm, n_pairs, 3 * n_data, n_frames, dst, dst_row_stride, dst_frame_stride, &used_pairs);
+    if (rc_buf != SDV_OK) return rc_buf;
     sdv_encoder *t = e->enc;
     if (t && !t->fresh && (t->video_standard != d->video_standard || t->resolution != d->resolution || t->ctrl_block != d->ctrl_block)) {
         set_error(e, "video standard, resolution and control block stay as the tape began: sdv_reset_encoder starts another tape"); return SDV_ERR_BAD_ARG;
@@ -106,22 +144,9 @@ int sdv_encode_frames(sdv_engine *e, const sdv_encode_desc *d, const int16_t *pc
     const uint64_t word_threads = n_lines + (uint64_t)d->width + 2 * sdv::ENC_TABLE_PAD;      /* a line or an entry of the cell table each */
     RT_CHECK(RT_LAUNCH_ITEMS(sdv_k_encode_words, sdv::encode_words_body, 0, word_threads, 256, s, w));
 
-    sdv::EncodeRasterArgs a;
-    a.lines = t->d_lines; a.cell_of = t->d_cell_of.p + sdv::ENC_TABLE_PAD;
-    a.dst = dst; a.dst_row_stride = dst_row_stride; a.dst_frame_stride = dst_frame_stride;
-    a.n_frames = n_frames; a.width = d->width; a.height = d->height; a.line_rows = d->height & ~1;
-    a.lpft = g.lpft; a.bff = d->field_order == SDV_ENC_BFF;
-    /* any top_line at or beyond these bounds leaves no row with a line, as the bound itself does: no overflow in the kernel */
-    a.top_line = d->top_line < -ENCODE_MAX_DIM ? -ENCODE_MAX_DIM : d->top_line > g.lpft ? g.lpft : d->top_line;
-    a.black4 = 0x01010101u * d->black; a.white4 = 0x01010101u * d->white;
-    /* cells 15 pixels apart are at most 15 * 137 / span, rounded up, apart, and a step more at a window edge: beyond 31 the raster's window does not hold them */
-    a.narrow = (15 * (int64_t)sdv::ENC_CELLS) / w.span + 2 > 31;
-    a.slots = (d->width + 30) / 16;
-    /* threads of the raster launch: a grid stride walks the rest (encode_raster_body) */
-    const uint32_t threads = rt::grid_stride_threads((uint64_t)n_frames * (uint64_t)d->height * (uint64_t)a.slots);
-    const rt::StrideSteps st = rt::stride_steps(threads, (uint32_t)d->height, (uint32_t)a.slots);
-    a.step_f = st.step_f; a.step_r = st.step_r; a.step_c = st.step_c;
-    RT_CHECK(RT_LAUNCH_ITEMS(sdv_k_encode_raster, sdv::encode_raster_body, 0u, threads, 256, s, a));
+    const EncodeRaster r = { d->width, d->height, d->top_line, g.lpft, sdv::ENC_CELLS, w.span, d->field_order == SDV_ENC_BFF, d->black, d->white };
+    const int rc_raster = encode_launch_raster(e, t, r, n_frames, dst, dst_row_stride, dst_frame_stride, s);
+    if (rc_raster != SDV_OK) return rc_raster;
 
     t->d_state.swap(t->d_state_next);
     t->video_standard = d->video_standard; t->resolution = d->resolution; t->ctrl_block = d->ctrl_block; t->fresh = false;

@@ -33,6 +33,7 @@
 
 #include "ingest_device.h"          /* sdv_k_ingest (sdv_ingest_frames, ingest_engine.inc) */
 #include "encode_device.h"          /* sdv_k_encode_words, sdv_k_encode_raster (sdv_encode_frames, encode_engine.inc) */
+#include "encode_markerless_device.h"   /* sdv_k_mlenc_pcm1_words, sdv_k_mlenc_pcm16_words (sdv_encode_markerless_frames, encode_markerless_engine.inc) */
 #include "runtime.inc"              /* namespace rt: memory, copies, launches, events and streams, for either build */
 
 /* Developer aids (scheduler traces, cycle stamps, launch-shape overrides) are read from the environment only in builds made with
@@ -590,3 +591,4 @@ int sdv_deinterleave_blocks(sdv_engine *e, const sdv_deint_line *lines, size_t n
 #include "stc007_frames_engine.inc"  /* sdv_binarize_frames */
 #include "ingest_engine.inc"         /* sdv_ingest_geometry, sdv_ingest_frames */
 #include "encode_engine.inc"         /* sdv_encode_geometry, sdv_encode_frames, sdv_reset_encoder */
+#include "encode_markerless_engine.inc"  /* sdv_encode_markerless_geometry, sdv_encode_markerless_frames */

@@ -46,6 +46,8 @@ ENC_NTSC, ENC_PAL = 0, 1                               # SDV_ENC_*
 ENC_14BIT, ENC_16BIT = 0, 1
 ENC_TFF, ENC_BFF = 0, 1
 ENC_CTRL_COPY_PROHIBITED, ENC_CTRL_EMPHASIS = 1, 2
+ENC_FMT_PCM1, ENC_FMT_PCM16X0_SI, ENC_FMT_PCM16X0_EI = 0, 1, 2
+ENC_ML_EMPHASIS, ENC_ML_RATE_44100, ENC_ML_CODE = 1, 2, 4
 VIS_STC007_LINES, VIS_PCM1_LINES, VIS_PCM16X0_LINES, VIS_STC007_BLOCKS_NTSC, VIS_STC007_BLOCKS_PAL, VIS_STC007_ASM_NTSC, VIS_STC007_ASM_PAL = 0, 1, 2, 3, 4, 5, 6   # SDV_VIS_*
 
 
@@ -78,6 +80,16 @@ class EncodeDesc(C.Structure):
 
 
 assert C.sizeof(EncodeDesc) == 36
+
+
+class EncodeMarkerlessDesc(C.Structure):
+    """sdv_encode_markerless_desc"""
+    _fields_ = [("format", C.c_uint8), ("field_order", C.c_uint8), ("black", C.c_uint8), ("white", C.c_uint8),
+                ("header_lines", C.c_uint8), ("ctrl_flags", C.c_uint8), ("_pad", C.c_uint8 * 2),
+                ("width", C.c_int32), ("height", C.c_int32), ("data_start", C.c_int32), ("data_stop", C.c_int32), ("top_line", C.c_int32)]
+
+
+assert C.sizeof(EncodeMarkerlessDesc) == 28
 
 
 class DeintSettings(C.Structure):
@@ -169,6 +181,9 @@ def load_library(path: str | None = None):
     lib.sdv_encode_geometry.argtypes = [C.POINTER(EncodeDesc), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
     lib.sdv_encode_frames.argtypes = [C.c_void_p, C.POINTER(EncodeDesc), C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
     lib.sdv_reset_encoder.argtypes = [C.c_void_p]
+    lib.sdv_encode_markerless_geometry.argtypes = [C.POINTER(EncodeMarkerlessDesc), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
+    lib.sdv_encode_markerless_frames.argtypes = [C.c_void_p, C.POINTER(EncodeMarkerlessDesc), C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                 C.c_void_p]
     lib.sdv_vis_canvas_size.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.sdv_vis_reset.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.sdv_vis_render_lines.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
@@ -441,6 +456,43 @@ class Engine:
     def reset_encoder(self):
         """sdv_reset_encoder: the next encode_frames call starts a new tape."""
         self._check(self.lib.sdv_reset_encoder(self._h))
+
+    @staticmethod
+    def encode_markerless_desc(fmt="pcm1", bff: bool = False, header_lines: int = 0, emphasis: bool = False, rate_44100: bool = False, code: bool = False,
+                               width: int = 720, height: int = 490, data_start: int = 4, data_stop=None, top_line: int = 0, black: int = 30,
+                               white: int = 200) -> EncodeMarkerlessDesc:
+        """The descriptor of encode_markerless_frames' keywords.  fmt: "pcm1" / "pcm16x0_si" / "pcm16x0_ei" or an ENC_FMT_* value."""
+        formats = {"pcm1": ENC_FMT_PCM1, "pcm16x0_si": ENC_FMT_PCM16X0_SI, "pcm16x0_ei": ENC_FMT_PCM16X0_EI}
+        if isinstance(fmt, str) and fmt not in formats:
+            raise ValueError("fmt is one of " + ", ".join(sorted(formats)))
+        flags = (ENC_ML_EMPHASIS if emphasis else 0) | (ENC_ML_RATE_44100 if rate_44100 else 0) | (ENC_ML_CODE if code else 0)
+        return EncodeMarkerlessDesc(formats[fmt] if isinstance(fmt, str) else int(fmt), ENC_BFF if bff else ENC_TFF, black, white, header_lines, flags,
+                                    (C.c_uint8 * 2)(), width, height, data_start, width - 4 if data_stop is None else data_stop, top_line)
+
+    def encode_markerless_geometry(self, desc: EncodeMarkerlessDesc):
+        """sdv_encode_markerless_geometry: (pairs a frame consumes, lines per field, bytes of a row) of a descriptor; host only."""
+        pairs, lines, rb = C.c_size_t(0), C.c_int(0), C.c_size_t(0)
+        rc = self.lib.sdv_encode_markerless_geometry(C.byref(desc), C.byref(pairs), C.byref(lines), C.byref(rb))
+        if rc != 0:
+            raise RuntimeError(f"sdvpcm error {rc}: " + self.lib.sdv_last_error(None).decode())
+        return pairs.value, lines.value, rb.value
+
+    def encode_markerless_frames(self, pcm, n_frames: int, fmt="pcm1", stream=None, **kw):
+        """sdv_encode_markerless_frames: n_frames frames of a PCM-1 or PCM-16x0 tape -> (n_frames, height, width) uint8 CUDA tensor.
+        pcm: torch.int16 CUDA tensor (pairs, 2), interleaved L R; a frame takes 1470 pairs, pairs that lack are silence.  There is no state: the next
+        call goes on with pcm[1470 * n_frames:].  The keywords are those of encode_markerless_desc; data_stop defaults to width - 4.  PCM-1 wants
+        header_lines = 1 (and height 492) for a tape the decoder reads without a forced-bad first line."""
+        import torch
+        if not (pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous() and (pcm.dim() == 2 and pcm.shape[1] == 2 or pcm.numel() == 0)):
+            raise ValueError("pcm must be a contiguous torch.int16 CUDA tensor of shape (pairs, 2)")
+        desc = self.encode_markerless_desc(fmt, **kw)
+        self.encode_markerless_geometry(desc)
+        out = torch.empty((n_frames, desc.height, desc.width), dtype=torch.uint8, device=pcm.device)
+        n_pairs = pcm.numel() // 2
+        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else C.c_void_p(torch.cuda.current_stream(pcm.device).cuda_stream)
+        self._check(self.lib.sdv_encode_markerless_frames(self._h, C.byref(desc), C.c_void_p(pcm.data_ptr()) if n_pairs else None, n_pairs, n_frames,
+                                                          C.c_void_p(out.data_ptr()), desc.width, desc.height * desc.width, sptr))
+        return out
 
     # ---- visualiser feed (RenderPCM's canvas of binarized lines) ----
     def vis_canvas_size(self, kind: int):

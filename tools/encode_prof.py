@@ -1,8 +1,10 @@
 """sdv_encode_frames against a hipMemsetAsync of the bytes it writes (the floor of a write-only pass) and against synth.stc007_frames_torch, which
 made such batches until now: BASELINE's batch of 10 000 NTSC frames (720 x 486), 14 bit with the control block, resident; timed between HIP events
 on the engine's stream, 3 calls of warm-up, median of 20, the calls of a comparison alternating in one process.
-usage: encode_prof.py [n_frames] [reps] [--out FILE]
+usage: encode_prof.py [n_frames] [reps] [--out FILE] [--markerless all|pcm1,pcm16x0_si,pcm16x0_ei]
   -> one JSON line (also written to FILE).  What the figures mean is prose in profiles/encode_notes.md, written by whoever ran the tool.
+With --markerless: sdv_encode_markerless_frames for the formats named (PCM-1 with one Header line) beside sdv_encode_frames at the same geometry,
+720 x 490, the same method, all alternating in one process; every call's words step from a call with a picture of 1 x 1.
 The share of the raster kernel is taken from a call with the same frames and a picture of 1 x 1: its words step is the same, its raster step is
 10 000 bytes."""
 import ctypes as C
@@ -15,7 +17,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from sdvpcmdecoder_amd import Engine, EncodeDesc, synth  # noqa: E402
+from sdvpcmdecoder_amd import Engine, EncodeDesc, EncodeMarkerlessDesc, synth  # noqa: E402
 
 W, H = 720, 486
 
@@ -41,6 +43,11 @@ def main():
         at = argv.index("--out")
         out_path = argv[at + 1]
         del argv[at:at + 2]
+    formats = []
+    if "--markerless" in argv:
+        at = argv.index("--markerless")
+        formats = ["pcm1", "pcm16x0_si", "pcm16x0_ei"] if argv[at + 1] == "all" else argv[at + 1].split(",")
+        del argv[at:at + 2]
     n = int(argv[0]) if len(argv) > 0 else 10_000
     reps = int(argv[1]) if len(argv) > 1 else 20
     eng = Engine(0)
@@ -50,7 +57,7 @@ def main():
     hip.hipMemsetAsync.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
     nbytes = n * H * W
     pcm = torch.randint(-32768, 32768, (n * 1470, 2), dtype=torch.int16, device="cuda")
-    dst = torch.empty(nbytes + 64, dtype=torch.uint8, device="cuda")
+    dst = torch.empty(n * 490 * W + 64, dtype=torch.uint8, device="cuda")     # (room for the 490 rows of --markerless)
 
     # what it makes is what the repository's generator makes: two frames without the control block against synth.stc007_frames on the same words
     two = eng.encode_frames(pcm[:2 * 1470], 2, height=H, top_line=2).cpu().numpy()
@@ -69,7 +76,38 @@ def main():
     def fill():
         assert hip.hipMemsetAsync(dst.data_ptr(), 30, nbytes, sptr) == 0
 
+    def markerless(fmt, width=W, height=490):
+        """sdv_encode_markerless_frames: PCM-1 with one Header line, PCM-16x0 with the 44100 bit"""
+        d = EncodeMarkerlessDesc(fmt, 0, 30, 200, 1 if fmt == 0 else 0, 0 if fmt == 0 else 2, (C.c_uint8 * 2)(), width, height, 4, 716, 0)
+
+        def fn():
+            rc = lib.sdv_encode_markerless_frames(h, C.byref(d), C.c_void_p(pcm.data_ptr()), n * 1470, n, C.c_void_p(dst.data_ptr()), width, width * height, sptr)
+            assert rc == 0, lib.sdv_last_error(h)
+        return fn
+
     p = torch.cuda.get_device_properties(0)
+    if formats:
+        # the marker-less formats beside sdv_encode_frames at the same geometry, 720 x 490, all alternating in one process; the words step of each
+        # from a call with a picture of 1 x 1
+        names = {"pcm1": 0, "pcm16x0_si": 1, "pcm16x0_ei": 2}
+        nbytes = n * 490 * W
+        fns, keys = [encode(height=490), encode(1, 1)], ["encode", "encode_words_only"]
+        for nm in formats:
+            fns += [markerless(names[nm]), markerless(names[nm], 1, 1)]
+            keys += [nm, nm + "_words_only"]
+        res = {"n_frames": n, "reps": reps, "device": torch.cuda.get_device_name(0), "arch": p.gcnArchName, "cus": p.multi_processor_count, "bytes": nbytes,
+               "width": W, "height": 490}
+        for key, (ms, mn) in zip(keys, timed(fns, reps)):
+            res[key + "_ms"], res[key + "_ms_min"] = ms, mn
+        for nm in formats:
+            res[nm + "_over_encode"] = res[nm + "_ms"] / res["encode_ms"]
+            res[nm + "_raster_share"] = 1.0 - res[nm + "_words_only_ms"] / res[nm + "_ms"]
+        line = json.dumps(res)
+        print(line)
+        if out_path:
+            os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+            open(out_path, "w").write(line + "\n")
+        return
     res = {"n_frames": n, "reps": reps, "device": torch.cuda.get_device_name(0), "arch": p.gcnArchName, "cus": p.multi_processor_count, "bytes": nbytes}
     (e_ms, e_min), (f_ms, f_min), (w_ms, w_min), (m_ms, m_min) = timed([encode(), fill, encode(1, 1), encode(at=3)], reps)
     res.update({"encode_ms": e_ms, "encode_ms_min": e_min, "encode_gbps": nbytes / e_ms / 1e6, "memset_ms": f_ms, "memset_ms_min": f_min,
