@@ -23,17 +23,23 @@
  *       captured frames as the video decoder delivers them (pixfmt: gray8 uyvy422 yuyv422 v210 gray10le rgb24 bgr24 rgb0 bgr0; rows
  *       src_row_stride bytes apart, frames src_h rows apart) -> sdv_ingest_frames: crop, channel, 8-bit luma, 2x doubling -> the plane the
  *       other modes read (and, on the device, the plane the frame entries take); prints `out_w out_h doubled`
- *   decode_tape encode <in.wav> <out.luma> [pal] [16] [noctrl] [emphasis] [nocopy]
+ *   decode_tape encode <in.wav> <out.luma> [pal] [16] [noctrl] [emphasis] [nocopy] [from44100] [preemph]
  *       the way back: a 16-bit stereo PCM WAV file -> sdv_encode_frames -> 8-bit luma frames of an STC-007 tape (`16`: PCM-F1, 16 bit) as the
  *       other modes read them: 720 pixels wide, data window 12 .. 708, every line of both fields (NTSC 492 rows, PAL 590; with `noctrl`, without
  *       the control line, 490 / 588), top field first, black 30, white 200.  One frame more than the samples fill is made from no pairs: it plays
- *       the 112 lines of interleave delay out.  `emphasis` and `nocopy` set the bits of the control block (the samples are not pre-emphasised).
- *       Prints `n_frames width height`; `decode_tape wav <out.luma> 720 <height> <n_frames> <back.wav>` gives the samples back
- *   decode_tape encode <in.wav> <out.luma> pcm1|pcm16si|pcm16ei [bff] [emphasis] [44100]
+ *       the 112 lines of interleave delay out.  `emphasis` and `nocopy` set the bits of the control block (`emphasis` alone leaves the samples as they are).
+ *       Prints `n_frames width height`; `decode_tape wav <out.luma> 720 <height> <n_frames> <back.wav>` gives the samples back.
+ *       `from44100`: the file is an ordinary 44 100 Hz WAV and the tape runs at 44 056 Hz - its pairs are resampled before anything else
+ *       (sdv_pcm_resample, one call, flush = 1); a usage error with `pal`, whose tape runs at 44 100 Hz.  `preemph`: the pairs are pre-emphasised at
+ *       the tape's rate (sdv_pcm_preemphasis; 44 056 Hz, with `pal` 44 100 Hz) and the emphasis bit is set; `clipped N` on stderr says how many samples
+ *       that clipped.  `16 from44100 preemph`, then `decode_tape wav ... force 44100`, gives a 44 100 Hz file back
+ *   decode_tape encode <in.wav> <out.luma> pcm1|pcm16si|pcm16ei [bff] [emphasis] [44100] [from44100] [preemph]
  *       the same for the marker-less formats: -> sdv_encode_markerless_frames -> frames of a PCM-1 tape (492 rows: one Header line and the 245
  *       data lines of either field) or of a PCM-1630 tape in the SI or EI interleave (490 rows), 720 pixels wide, data window 4 .. 716, black 30,
  *       white 200, top field first or, with `bff`, bottom field first.  `emphasis` and `44100` set Control Bits of a PCM-16x0 tape (without
- *       `44100` it says 44 056 Hz).  As many frames as the samples fill, the rest of the last one silence.  Prints `n_frames width height`
+ *       `44100` it says 44 056 Hz).  As many frames as the samples fill, the rest of the last one silence.  Prints `n_frames width height`.
+ *       `from44100` and `preemph` as above: the tape's rate is 44 056 Hz, or 44 100 Hz for PCM-16x0 with `44100` (with which `from44100` is a usage
+ *       error); `preemph` sets the emphasis Control Bit of a PCM-16x0 tape - a PCM-1 tape has none, only its samples change
  *   decode_tape frames <luma.raw> <width> <height> <n_frames> pcm1|pcm16si|pcm16ei tff|bff <pairs.out>
  *       8-bit luma frames of a marker-less format -> sdv_decode_frames (NEW_FILE | END_FILE, no audio stage) -> PCMSamplePair records: what reads
  *       the tapes of `encode` back
@@ -85,6 +91,28 @@ static bool read_wav(const char *path, std::vector<uint8_t> &in, size_t *data_at
     if (!*data_at || channels != 2 || bits != 16) { fprintf(stderr, "%s: 16-bit stereo PCM is what a tape holds\n", path); return false; }
     *n_pairs = data_len / 4;
     return true;
+}
+/* `from44100` and `preemph` of the encode modes, on the file's pairs on the device: resampled to 44 056 Hz (one call, flush = 1), then pre-emphasised
+ * at the tape's rate.  *d_pcm and *n become what the encoder reads. */
+static int condition_pcm(sdv_engine *eng, int16_t **d_pcm, size_t *n, bool from44100, bool preemph, uint16_t tape_rate)
+{
+    if (from44100 && *n) {
+        const size_t cap = sdv_pcm_resample_room(eng, *n);
+        int16_t *d_out = NULL; size_t n_out = 0;
+        HIP_OK(hipMalloc((void **)&d_out, cap * 4 + 4));
+        SDV_OKAY(sdv_pcm_resample(eng, *d_pcm, *n, 1, d_out, cap, &n_out, NULL));
+        HIP_OK(hipDeviceSynchronize());
+        (void)hipFree(*d_pcm); *d_pcm = d_out; *n = n_out;
+    }
+    if (preemph && *n) {
+        int16_t *d_out = NULL; uint64_t clipped = 0;
+        HIP_OK(hipMalloc((void **)&d_out, *n * 4 + 4));
+        SDV_OKAY(sdv_pcm_preemphasis(eng, *d_pcm, *n, tape_rate, d_out, NULL));
+        SDV_OKAY(sdv_pcm_preemphasis_clipped(eng, NULL, &clipped));
+        if (clipped) fprintf(stderr, "clipped %llu\n", (unsigned long long)clipped);
+        (void)hipFree(*d_pcm); *d_pcm = d_out;
+    }
+    return 0;
 }
 template <class T> static int download(const T *dev, size_t n, const char *path)
 {
@@ -304,13 +332,17 @@ int main(int argc, char **argv)
         d.format = pcm1 ? SDV_ENC_FMT_PCM1 : !strcmp(argv[4], "pcm16si") ? SDV_ENC_FMT_PCM16X0_SI : SDV_ENC_FMT_PCM16X0_EI;
         d.header_lines = pcm1 ? 1 : 0;
         d.black = 30; d.white = 200; d.width = 720; d.data_start = 4; d.data_stop = 716;
+        bool from44100 = false, preemph = false;
         for (int i = 5; i < argc; i++) {
             const std::string opt = argv[i];
             if (opt == "bff") d.field_order = SDV_ENC_BFF;
             else if (opt == "emphasis" && !pcm1) d.ctrl_flags |= SDV_ENC_ML_EMPHASIS;
             else if (opt == "44100" && !pcm1) d.ctrl_flags |= SDV_ENC_ML_RATE_44100;
+            else if (opt == "from44100") from44100 = true;
+            else if (opt == "preemph") { preemph = true; if (!pcm1) d.ctrl_flags |= SDV_ENC_ML_EMPHASIS; }
             else { fprintf(stderr, "usage: see the header of examples/decode_tape.cpp\n"); return 1; }
         }
+        if (from44100 && (d.ctrl_flags & SDV_ENC_ML_RATE_44100)) { fprintf(stderr, "usage: from44100 is for a tape that runs at 44 056 Hz (see the header of examples/decode_tape.cpp)\n"); return 1; }
         size_t per_frame = 0; int lines_per_field = 0;
         d.height = 2;                       /* (any: the geometry tells the lines of a field, the height follows from them) */
         const int grc = sdv_encode_markerless_geometry(&d, &per_frame, &lines_per_field, NULL);
@@ -318,12 +350,13 @@ int main(int argc, char **argv)
         d.height = 2 * lines_per_field;
         size_t data_at = 0, n_in = 0;
         if (!read_wav(argv[2], in, &data_at, &n_in)) return 1;
-        const int n = n_in ? (int)((n_in + per_frame - 1) / per_frame) : 1;     /* (no delay to play out: a frame is made from its own pairs) */
-        const size_t frame_bytes = (size_t)d.width * d.height;
         int16_t *d_pcm = NULL; uint8_t *d_luma = NULL;
         HIP_OK(hipMalloc((void **)&d_pcm, n_in * 4 + 4));
-        HIP_OK(hipMalloc((void **)&d_luma, frame_bytes * n));
         HIP_OK(hipMemcpy(d_pcm, in.data() + data_at, n_in * 4, hipMemcpyHostToDevice));
+        { const int crc = condition_pcm(eng, &d_pcm, &n_in, from44100, preemph, (d.ctrl_flags & SDV_ENC_ML_RATE_44100) ? 44100 : 44056); if (crc) return crc; }
+        const int n = n_in ? (int)((n_in + per_frame - 1) / per_frame) : 1;     /* (no delay to play out: a frame is made from its own pairs) */
+        const size_t frame_bytes = (size_t)d.width * d.height;
+        HIP_OK(hipMalloc((void **)&d_luma, frame_bytes * n));
         SDV_OKAY(sdv_encode_markerless_frames(eng, &d, d_pcm, n_in, n, d_luma, (size_t)d.width, frame_bytes, NULL));
         HIP_OK(hipDeviceSynchronize());
         rc = download(d_luma, frame_bytes * n, argv[3]);
@@ -332,6 +365,7 @@ int main(int argc, char **argv)
     } else if (mode == "encode" && argc >= 4) {
         sdv_encode_desc d; memset(&d, 0, sizeof(d));
         d.ctrl_block = 1; d.black = 30; d.white = 200; d.width = 720; d.data_start = 12; d.data_stop = 708;
+        bool from44100 = false, preemph = false;
         for (int i = 4; i < argc; i++) {
             const std::string opt = argv[i];
             if (opt == "pal") d.video_standard = SDV_ENC_PAL;
@@ -339,8 +373,11 @@ int main(int argc, char **argv)
             else if (opt == "noctrl") d.ctrl_block = 0;
             else if (opt == "emphasis") d.ctrl_flags |= SDV_ENC_CTRL_EMPHASIS;
             else if (opt == "nocopy") d.ctrl_flags |= SDV_ENC_CTRL_COPY_PROHIBITED;
+            else if (opt == "from44100") from44100 = true;
+            else if (opt == "preemph") { preemph = true; d.ctrl_flags |= SDV_ENC_CTRL_EMPHASIS; }
             else { fprintf(stderr, "usage: see the header of examples/decode_tape.cpp\n"); return 1; }
         }
+        if (from44100 && d.video_standard == SDV_ENC_PAL) { fprintf(stderr, "usage: from44100 is for a tape that runs at 44 056 Hz (see the header of examples/decode_tape.cpp)\n"); return 1; }
         size_t per_frame = 0; int lines_per_field = 0;
         d.height = 2;                       /* (any: the geometry tells the lines of a field, the height follows from them) */
         const int grc = sdv_encode_geometry(&d, &per_frame, &lines_per_field, NULL);
@@ -348,12 +385,13 @@ int main(int argc, char **argv)
         d.height = 2 * lines_per_field;
         size_t data_at = 0, n_in = 0;
         if (!read_wav(argv[2], in, &data_at, &n_in)) return 1;
-        const int n = (int)((n_in + per_frame - 1) / per_frame) + 1;          /* ... and the frame that plays the delay out */
-        const size_t frame_bytes = (size_t)d.width * d.height;
         int16_t *d_pcm = NULL; uint8_t *d_luma = NULL;
         HIP_OK(hipMalloc((void **)&d_pcm, n_in * 4 + 4));
-        HIP_OK(hipMalloc((void **)&d_luma, frame_bytes * n));
         HIP_OK(hipMemcpy(d_pcm, in.data() + data_at, n_in * 4, hipMemcpyHostToDevice));
+        { const int crc = condition_pcm(eng, &d_pcm, &n_in, from44100, preemph, d.video_standard == SDV_ENC_PAL ? 44100 : 44056); if (crc) return crc; }
+        const int n = (int)((n_in + per_frame - 1) / per_frame) + 1;          /* ... and the frame that plays the delay out */
+        const size_t frame_bytes = (size_t)d.width * d.height;
+        HIP_OK(hipMalloc((void **)&d_luma, frame_bytes * n));
         SDV_OKAY(sdv_encode_frames(eng, &d, d_pcm, n_in, n, d_luma, (size_t)d.width, frame_bytes, NULL));
         HIP_OK(hipDeviceSynchronize());
         rc = download(d_luma, frame_bytes * n, argv[3]);

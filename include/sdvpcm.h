@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define SDV_ABI_VERSION 10  /* 2: output capacities on sdv_binarize_frames / sdv_pcm1_binarize_lines; 3: sdv_audio_process, sdv_wav_pack, sdv_wav_header, sdv_decode_frames (additions only);
+#define SDV_ABI_VERSION 11  /* 2: output capacities on sdv_binarize_frames / sdv_pcm1_binarize_lines; 3: sdv_audio_process, sdv_wav_pack, sdv_wav_header, sdv_decode_frames (additions only);
                              * 4: sdv_pcm16x0_binarize_lines, sdv_audio_stalled, sdv_set_frame_flags, sdv_double_width, sdv_vis_render_lines (additions); the calls that used to refuse PCM-16x0 frames of the wrong size and the
                              * AudioProcessor's dead ends now follow the reference; the PCM-16x0 stitch state blob grew by conv_queue's remainder;
                              * 5: sdv_run_info grew by frames_met (at its end), sdv_binarize_lines (addition);
@@ -28,7 +28,9 @@ extern "C" {
                              * 7: sdv_resample_taps, sdv_set_resample, sdv_reset_resample, sdv_audio_resample_pending, sdv_audio_resample_room, sdv_audio_resample (additions only);
                              * 8: sdv_ingest_geometry, sdv_ingest_frames (additions only);
                              * 9: sdv_encode_geometry, sdv_encode_frames, sdv_reset_encoder (additions only);
-                             * 10: sdv_encode_markerless_geometry, sdv_encode_markerless_frames (additions only) */
+                             * 10: sdv_encode_markerless_geometry, sdv_encode_markerless_frames (additions only);
+                             * 11: sdv_preemphasis_coeffs, sdv_reset_preemphasis, sdv_pcm_preemphasis, sdv_pcm_preemphasis_clipped, sdv_pcm_resample_taps, sdv_reset_pcm_resample,
+                             * sdv_pcm_resample_pending, sdv_pcm_resample_room, sdv_pcm_resample (additions only) */
 
 /* ---- status codes ---------------------------------------------------------------------------
  * 0..4 mirror Binarizer::LB_RET_* (binarizer.h:268-275); 16.. mirror STC007Deinterleaver::DI_RET_*
@@ -396,7 +398,7 @@ int sdv_ingest_frames(sdv_engine *e, const sdv_ingest_desc *d, const void *src, 
  *   (SDV_ENC_CTRL_EMPHASIS ? 0 : 1) (stc007line.h:104-152, getters stc007line.cpp:361-443); CRC and cells as for a data line.  The bit that
  *   says "no P word" cannot be asked for.  tc_hour .. tc_field are the time code of the first field after a reset; it advances by one field per
  *   field, carries into the seconds at 60 (NTSC) or 50 (PAL) fields, on into minutes and hours, and the hours wrap at 16.  tc_index and
- *   ctrl_flags are taken from every call's descriptor.  (SDV_ENC_CTRL_EMPHASIS only sets the bit: pre-emphasis of the samples is the caller's.)
+ *   ctrl_flags are taken from every call's descriptor.  (SDV_ENC_CTRL_EMPHASIS only sets the bit: sdv_pcm_preemphasis pre-emphasises the samples.)
  * Frame.  lines_per_field = lpf + ctrl_block.  Row 2 r of frame f shows line top_line + r of the field that is first in time (field 2 f of the
  *   tape), row 2 r + 1 the same line of the other field; with SDV_ENC_BFF the two swap.  A row whose line does not exist (below 0, at or beyond
  *   lines_per_field) is `black` throughout, and so is the last row of an odd height.
@@ -461,7 +463,7 @@ int sdv_reset_encoder(sdv_engine *e);
  *     3 j + 1 on 64 .. 127, the Control Bit on cell 128, 3 j + 2 on 129 .. 192.
  *   Control Bit.  1 on every line but the lines 35 i + 0 .. 35 i + 3 of a field, i = 0 .. 6, where it is 0 on 35 i + 0 with SDV_ENC_ML_EMPHASIS, on
  *     35 i + 1 with SDV_ENC_ML_RATE_44100 (else the tape says 44056 Hz), on 35 i + 2 with the EI format, on 35 i + 3 with SDV_ENC_ML_CODE.
- *     (SDV_ENC_ML_EMPHASIS only sets the bit: pre-emphasis of the samples is the caller's.)
+ *     (SDV_ENC_ML_EMPHASIS only sets the bit: sdv_pcm_preemphasis pre-emphasises the samples.)
  * Frame.  lines_per_field = 245 + header_lines.  Rows, field order, top_line and the rows without a line are those of sdv_encode_frames.
  * Raster.  As for sdv_encode_frames with the format's cell count: pixel x is `white` where data_start <= x < data_stop and cell
  *   ((x - data_start) * CELLS) / (data_stop - data_start) is 1, CELLS = 94 (PCM-1) or 193 (PCM-16x0), else `black`.
@@ -1028,6 +1030,65 @@ size_t sdv_audio_resample_room(const sdv_engine *e, size_t n_pairs);
  * SDV_ERR_NULL_BLOCK).  n_pairs == 0 with flush != 0 closes the open segment and emits its tail. */
 int sdv_audio_resample(sdv_engine *e, const sdv_sample_pair *pairs, size_t n_pairs, int flush,
                        sdv_sample_pair *out_pairs, size_t out_cap, size_t *n_out, void *stream);
+
+/* ---- ahead of the encoders: pre-emphasis and 44 100 -> 44 056 Hz on interleaved int16 PCM (no reference equivalent) ---------------------
+ * What a user who holds an ordinary 44 100 Hz WAV file needs in front of sdv_encode_frames / sdv_encode_markerless_frames.  Both stages work on the
+ * plain interleaved int16 L R the encoders read - no service pairs, no per-pair rate, no segments - and neither reads anything back.  Buffers are
+ * device pointers, 4-byte aligned (a WAV's data chunk is), and the output never overlaps the input: SDV_ERR_BAD_ARG with an sdv_last_error text
+ * and the state untouched otherwise.  Calls of one stream go to one HIP stream.
+ *
+ * sdv_pcm_preemphasis: the 15/50 us network, the exact inverse of sdv_audio_deemphasis.  With b0, b1, a1 = sdv_deemphasis_coeffs(sample_rate) -
+ * the same rate rule: 44056 stays, anything else reads 44100 - c = { 1 / b0, a1 / b0, b1 / b0 }, computed in double on the host
+ * (sdv_preemphasis_coeffs; at 44056 Hz 1 / b0 = 2.3283, gain 1 at DC and T1 / T2 = 3.333 at fs / 2, the pole at -b1 / b0 = 0.1386).
+ * Per channel the stream is walked in order with a state that is idle or running (fs, x_prev, y_prev), all arithmetic in double:
+ *   - a pair that finds the state idle, or running at another fs, starts the filter: x_prev = y_prev = x, the word stays (no click - and
+ *     de-emphasis after pre-emphasis is the identity before rounding);
+ *   - any other pair: y = c0 x + c1 x_prev - c2 y_prev, x_prev = x, y_prev = y (unrounded, unclamped); the word is y rounded to the nearest
+ *     integer (halves to even) and clamped to -32768 .. 32767.  A word the clamp changed counts as clipped.
+ * The state and the counter of clipped words live in the engine, on the device, from one call of a stream to the next; sdv_engine_create and
+ * sdv_reset_preemphasis leave the state idle and the counter 0.  The counter is a sum of integers: it does not depend on the order of the work.
+ * On the device a lane takes its state from the SDV_PREEMPH_WARMUP pairs in front of its own (0.139^32 = 3e-28 of full scale is what older
+ * pairs are owed): a word differs from the walk above only where y lies within about 1e-9 of a half. */
+#define SDV_PREEMPH_TILE 1024       /* pairs per tile of the device's work (the tiles of a call start at its first pair) */
+#define SDV_PREEMPH_WARMUP 32       /* pairs in front of a lane's own its state is taken from */
+/* c0, c1, c2 for this sample_rate.  Host memory, no engine. */
+void sdv_preemphasis_coeffs(uint16_t sample_rate, double c[3]);
+int sdv_reset_preemphasis(sdv_engine *e);
+/* n_pairs pairs from `pcm` to `out_pcm`, asynchronous on `stream`.  n_pairs == 0: SDV_OK, nothing done.  Null buffers with n_pairs != 0:
+ * SDV_ERR_NULL_LINES / SDV_ERR_NULL_BLOCK.  Any overlap of the two buffers (the call is not made in place: PCM is 4 bytes a pair) and a buffer
+ * that is not 4-byte aligned are refused. */
+int sdv_pcm_preemphasis(sdv_engine *e, const int16_t *pcm, size_t n_pairs, uint16_t sample_rate, int16_t *out_pcm, void *stream);
+/* Synchronises `stream`; *count = the samples clipped since the engine was made or sdv_reset_preemphasis, both channels summed. */
+int sdv_pcm_preemphasis_clipped(sdv_engine *e, void *stream, uint64_t *count);
+
+/* sdv_pcm_resample: 44 100 Hz PCM to the 44 100 / 1.001 Hz of STC-007 / PCM-F1 on NTSC video, PCM-1 and PCM-16x0 without SDV_ENC_ML_RATE_44100 - the
+ * inverse of sdv_audio_resample's ratio, SDV_PCM_RESAMPLE_L / SDV_PCM_RESAMPLE_M.  Prototype and window are that stage's - a Kaiser-windowed sinc,
+ * beta = 12.0, 64 taps on each side - on another phase grid.  For phase p = 0 .. 999 and k = 0 .. 127, all in double:
+ *   d = (k - 63) - p / 1000,  g[p][k] = sinc(d) I0(12 sqrt(1 - (d / 64)^2)) / I0(12),  h[p][k] = g[p][k] / sum_k g[p][k]
+ * so every phase has gain 1 at DC (a DC input comes out exactly); h[p][k] = h[1000 - p][127 - k] for p >= 1; max sum |h| = 3.144: outputs clamp.
+ * The cutoff is not scaled by 1000 / 1001: that would move it by 22 Hz, against a transition band of about 2.7 kHz.
+ * A stream of n >= 1 pairs x[0 .. n-1] yields n_out = floor((1000 n - 1) / 1001) + 1 outputs.  For m = 0 .. n_out - 1:
+ *   i0 = floor(1001 m / 1000), p = (1001 m) mod 1000, per channel y = sum_k h[p][k] x[clamp(i0 - 63 + k, 0, n - 1)], summed in the order of k;
+ *   the word is y rounded to the nearest integer (halves to even) and clamped to -32768 .. 32767.
+ * Streaming.  Without flush a call emits the outputs whose i0 + 64 is below the number of pairs the stream has seen; the rest wait in the
+ * engine (the stream's last 127 pairs, on the device).  flush != 0 closes the stream - the next call starts a new one at m = 0 - and
+ * n_pairs == 0 with flush emits the tail.  The concatenated output of any split of a stream into calls equals the output of one call.
+ * The counters (pairs seen, outputs emitted, 64 bit) live on the host: *n_out is known before the launch, the call is asynchronous on `stream`
+ * and reads nothing back.  A word differs from a sequential float64 evaluation only where y lies within about 1e-9 of a half. */
+#define SDV_PCM_RESAMPLE_L 1000
+#define SDV_PCM_RESAMPLE_M 1001
+/* h[phase][0 .. 127] (phase 0 .. 999; anything else: zeros).  Host memory, no engine. */
+void sdv_pcm_resample_taps(int phase, double taps[128]);
+/* No open stream, nothing pending. */
+int sdv_reset_pcm_resample(sdv_engine *e);
+/* Pairs of the open stream that still owe outputs (at most 64; 0 behind a flush). */
+size_t sdv_pcm_resample_pending(const sdv_engine *e);
+/* An upper bound of *n_out for the next call with n_pairs pairs, with or without flush. */
+size_t sdv_pcm_resample_room(const sdv_engine *e, size_t n_pairs);
+/* n_pairs pairs from `pcm`, *n_out pairs to `out_pcm`.  Refused before any launch, with the state untouched (SDV_ERR_BAD_ARG unless noted): out_cap
+ * below sdv_pcm_resample_room(e, n_pairs), any overlap of the buffers, a buffer that is not 4-byte aligned, and - with n_pairs != 0 - null
+ * buffers (SDV_ERR_NULL_LINES / SDV_ERR_NULL_BLOCK). */
+int sdv_pcm_resample(sdv_engine *e, const int16_t *pcm, size_t n_pairs, int flush, int16_t *out_pcm, size_t out_cap, size_t *n_out, void *stream);
 
 /* ---- the workers back to back: video frames -> PCMSamplePair (-> masked PCMSamplePair) in one call ------------------- */
 /* SURVEY 8b's "sdv_decode_frames": the format's VideoToDigital worker, its data stitcher and - on request - the AudioProcessor, one

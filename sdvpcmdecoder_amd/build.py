@@ -33,6 +33,8 @@ KERNEL_SOURCES = {
     "sdv_k_ingest": ("ingest_device.h", "ingest_engine.inc"),
     "sdv_k_encode": ("encode_device.h", "encode_engine.inc"),
     "sdv_k_mlenc": ("encode_device.h", "encode_markerless_device.h", "encode_engine.inc", "encode_markerless_engine.inc"),
+    "sdv_k_preemph": ("pcm_preemph_device.h", "pcm_condition_engine.inc"),
+    "sdv_k_pcmrs": ("pcm_preemph_device.h", "pcm_resample_device.h", "pcm_condition_engine.inc"),
     "sdv_k_pcm16_frames_bin": ("stc007_device.h", "pcm1_bin_device.h", "pcm16_bin_device.h", "pcm16_frames_device.h", "markerless_chain_device.h", "markerless_frames_engine.inc", "pcm16_frames_engine.inc"),
 }
 

@@ -34,6 +34,8 @@
 #include "ingest_device.h"          /* sdv_k_ingest (sdv_ingest_frames, ingest_engine.inc) */
 #include "encode_device.h"          /* sdv_k_encode_words, sdv_k_encode_raster (sdv_encode_frames, encode_engine.inc) */
 #include "encode_markerless_device.h"   /* sdv_k_mlenc_pcm1_words, sdv_k_mlenc_pcm16_words (sdv_encode_markerless_frames, encode_markerless_engine.inc) */
+#include "pcm_preemph_device.h"     /* sdv_k_preemph (sdv_pcm_preemphasis, pcm_condition_engine.inc) */
+#include "pcm_resample_device.h"    /* sdv_k_pcmrs (sdv_pcm_resample, pcm_condition_engine.inc) */
 #include "runtime.inc"              /* namespace rt: memory, copies, launches, events and streams, for either build */
 
 /* Developer aids (scheduler traces, cycle stamps, launch-shape overrides) are read from the environment only in builds made with
@@ -167,6 +169,7 @@ struct sdv_pcm16_stitcher;          /* PCM-16x0 back half, pcm16_engine.inc */
 struct sdv_audio;                   /* AudioProcessor, audio_engine.inc */
 struct sdv_vis;                     /* visualiser canvases, vis_engine.inc */
 struct sdv_encoder;                 /* the tape sdv_encode_frames writes, encode_engine.inc */
+struct sdv_pcm_cond;                /* pre-emphasis and 44 100 -> 44 056 Hz ahead of the encoders, pcm_condition_engine.inc */
 struct sdv_engine;
 static void stitcher_free(sdv_engine *e);
 static void pcm1_free(sdv_engine *e);
@@ -174,6 +177,7 @@ static void pcm16_free(sdv_engine *e);
 static void audio_free(sdv_engine *e);
 static void vis_free(sdv_engine *e);
 static void encoder_free(sdv_engine *e);
+static void pcm_cond_free(sdv_engine *e);
 struct sdv_engine {
     int device = 0;
     std::string last_error;
@@ -219,6 +223,7 @@ struct sdv_engine {
     sdv_audio *audio = NULL;
     sdv_vis *vis = NULL;
     sdv_encoder *enc = NULL;
+    sdv_pcm_cond *cond = NULL;
     rt::Timer timer;                /* sdv_set_profiling: the device time of a call's kernels */
     rt::Event mark;                 /* behind the first round's read-back of sdv_binarize_frames when work of the next stage is queued behind it */
     bool binarize_settled_at_once = false;      /* the last sdv_binarize_frames call of the fused entry needed one round */
@@ -294,6 +299,7 @@ void sdv_engine_destroy(sdv_engine *e)
     audio_free(e);
     vis_free(e);
     encoder_free(e);
+    pcm_cond_free(e);
     delete e;       /* (frees the buffers, the bounce buffer and the events: the guard above is still in place) */
 }
 
@@ -592,3 +598,4 @@ int sdv_deinterleave_blocks(sdv_engine *e, const sdv_deint_line *lines, size_t n
 #include "ingest_engine.inc"         /* sdv_ingest_geometry, sdv_ingest_frames */
 #include "encode_engine.inc"         /* sdv_encode_geometry, sdv_encode_frames, sdv_reset_encoder */
 #include "encode_markerless_engine.inc"  /* sdv_encode_markerless_geometry, sdv_encode_markerless_frames */
+#include "pcm_condition_engine.inc"  /* sdv_pcm_preemphasis, sdv_pcm_resample */

@@ -293,6 +293,21 @@ def load_library(path: str | None = None):
     lib.sdv_audio_resample_room.argtypes = [C.c_void_p, C.c_size_t]
     lib.sdv_audio_resample.restype = C.c_int
     lib.sdv_audio_resample.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
+    lib.sdv_preemphasis_coeffs.argtypes = [C.c_uint16, C.POINTER(C.c_double)]
+    lib.sdv_preemphasis_coeffs.restype = None
+    lib.sdv_reset_preemphasis.argtypes = [C.c_void_p]
+    lib.sdv_pcm_preemphasis.restype = C.c_int
+    lib.sdv_pcm_preemphasis.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint16, C.c_void_p, C.c_void_p]
+    lib.sdv_pcm_preemphasis_clipped.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.sdv_pcm_resample_taps.argtypes = [C.c_int, C.POINTER(C.c_double)]
+    lib.sdv_pcm_resample_taps.restype = None
+    lib.sdv_reset_pcm_resample.argtypes = [C.c_void_p]
+    lib.sdv_pcm_resample_pending.restype = C.c_size_t
+    lib.sdv_pcm_resample_pending.argtypes = [C.c_void_p]
+    lib.sdv_pcm_resample_room.restype = C.c_size_t
+    lib.sdv_pcm_resample_room.argtypes = [C.c_void_p, C.c_size_t]
+    lib.sdv_pcm_resample.restype = C.c_int
+    lib.sdv_pcm_resample.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
     lib.sdv_decode_frames.restype = C.c_int
     lib.sdv_decode_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint,
                                       C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t,
@@ -493,6 +508,78 @@ class Engine:
         self._check(self.lib.sdv_encode_markerless_frames(self._h, C.byref(desc), C.c_void_p(pcm.data_ptr()) if n_pairs else None, n_pairs, n_frames,
                                                           C.c_void_p(out.data_ptr()), desc.width, desc.height * desc.width, sptr))
         return out
+
+    # ---- ahead of the encoders: pre-emphasis and 44 100 -> 44 056 Hz on (pairs, 2) int16 PCM: beyond the reference ----------------------
+    @staticmethod
+    def _check_pcm(t, name):
+        import torch
+        if not (t.is_cuda and t.dtype == torch.int16 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 2):
+            raise ValueError(name + " must be a contiguous torch.int16 CUDA tensor of shape (pairs, 2)")
+
+    def preemphasis_coeffs(self, rate: int):
+        """(c0, c1, c2) of the pre-emphasis network at a rate (44056, anything else reads 44100)."""
+        c = (C.c_double * 3)()
+        self.lib.sdv_preemphasis_coeffs(int(rate), c)
+        return tuple(c)
+
+    def reset_preemphasis(self):
+        """The filter forgets the stream it was on (the next pair starts it, its word stays); the counter of clipped samples is 0."""
+        self._check(self.lib.sdv_reset_preemphasis(self._h))
+
+    def pcm_preemphasis(self, pcm, sample_rate: int, out=None, stream=None):
+        """The 15/50 us network, the inverse of audio_deemphasis, over one burst of a PCM stream: (n, 2) int16 -> (n, 2) int16 on the device,
+        asynchronous on the stream.  sample_rate: the tape's, 44056 or 44100.  out: a buffer that does not overlap `pcm`; the filter state and
+        the counter of clipped samples stay in the engine from call to call."""
+        import torch
+        self._check_pcm(pcm, "pcm")
+        n = pcm.shape[0]
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.int16, device=pcm.device)
+        self._check_pcm(out, "out")
+        if out.shape[0] < n:
+            raise ValueError("out holds fewer pairs than pcm")
+        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else C.c_void_p(torch.cuda.current_stream(pcm.device).cuda_stream)
+        self._check(self.lib.sdv_pcm_preemphasis(self._h, C.c_void_p(pcm.data_ptr()) if n else None, n, int(sample_rate),
+                                                 C.c_void_p(out.data_ptr()) if n else None, sptr))
+        return out[:n]
+
+    def preemphasis_clipped(self, stream=None) -> int:
+        """Samples the pre-emphasis clipped since the engine was made or reset_preemphasis, both channels summed; waits for the stream."""
+        import torch
+        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        n = C.c_uint64(0)
+        self._check(self.lib.sdv_pcm_preemphasis_clipped(self._h, sptr, C.byref(n)))
+        return int(n.value)
+
+    def pcm_resample_taps(self, phase: int):
+        """The 128 taps of a phase (0 .. 999) of pcm_resample, as a tuple of floats."""
+        c = (C.c_double * 128)()
+        self.lib.sdv_pcm_resample_taps(int(phase), c)
+        return tuple(c)
+
+    def reset_pcm_resample(self):
+        """No open stream, nothing pending."""
+        self._check(self.lib.sdv_reset_pcm_resample(self._h))
+
+    def pcm_resample_pending(self) -> int:
+        return int(self.lib.sdv_pcm_resample_pending(self._h))
+
+    def pcm_resample(self, pcm, flush=False, out=None, stream=None):
+        """One burst of a 44 100 Hz PCM stream through the 1000 / 1001 resampler: (n, 2) int16 -> (n_out, 2) int16 at 44 056 Hz on the device,
+        asynchronous on the stream.  Without flush the last 64 pairs wait in the engine for the next call; flush closes the stream.  out: a buffer
+        of at least sdv_pcm_resample_room pairs that does not overlap `pcm`."""
+        import torch
+        self._check_pcm(pcm, "pcm")
+        n = pcm.shape[0]
+        room = int(self.lib.sdv_pcm_resample_room(self._h, n))
+        if out is None:
+            out = torch.empty((room, 2), dtype=torch.int16, device=pcm.device)
+        self._check_pcm(out, "out")
+        sptr = C.c_void_p(stream.cuda_stream) if stream is not None else C.c_void_p(torch.cuda.current_stream(pcm.device).cuda_stream)
+        n_out = C.c_size_t(0)
+        self._check(self.lib.sdv_pcm_resample(self._h, C.c_void_p(pcm.data_ptr()) if n else None, n, 1 if flush else 0,
+                                              C.c_void_p(out.data_ptr()) if out.shape[0] else None, out.shape[0], C.byref(n_out), sptr))
+        return out[:n_out.value]
 
     # ---- visualiser feed (RenderPCM's canvas of binarized lines) ----
     def vis_canvas_size(self, kind: int):
