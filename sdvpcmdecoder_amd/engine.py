@@ -9,138 +9,19 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-import numpy as np
+from . import abi
+from .abi import (  # noqa: F401  (what this module defined before abi.py: importable from here as before)
+    LINE_DTYPE, STATS_DTYPE, DEINT_LINE_DTYPE, BLOCK_DTYPE, PAIR_DTYPE, AUDIO_PURGE_DTYPE,
+    BinPreset, IngestDesc, EncodeDesc, EncodeMarkerlessDesc, DeintSettings, StitchSettings, Pcm1StitchSettings, Pcm16x0StitchSettings, StitchInfo, RunInfo,
+    PCM_PCM1, PCM_PCM16X0, PCM_STC007, TYPE_M2, MODE_DRAFT, MODE_FAST, MODE_NORMAL, MODE_INSANE, FLAG_NEW_FILE, FLAG_DOUBLED, FLAG_END_FILE, FRAME_EMPTY,
+    DEEMPH_OFF, DEEMPH_AUTO, DEEMPH_FORCE, RESAMPLE_OFF, RESAMPLE_TO_44100,
+    PIX_GRAY8, PIX_UYVY422, PIX_YUYV422, PIX_V210, PIX_GRAY10LE, PIX_RGB24, PIX_BGR24, PIX_RGB0, PIX_BGR0, PIX_FORMATS, COLOR_BW, COLOR_R, COLOR_G, COLOR_B,
+    INGEST_DOUBLE_OFF, INGEST_DOUBLE_ON, INGEST_DOUBLE_AUTO, ENC_NTSC, ENC_PAL, ENC_14BIT, ENC_16BIT, ENC_TFF, ENC_BFF, ENC_CTRL_COPY_PROHIBITED, ENC_CTRL_EMPHASIS,
+    ENC_FMT_PCM1, ENC_FMT_PCM16X0_SI, ENC_FMT_PCM16X0_EI, ENC_ML_EMPHASIS, ENC_ML_RATE_44100, ENC_ML_CODE,
+    VIS_STC007_LINES, VIS_PCM1_LINES, VIS_PCM16X0_LINES, VIS_STC007_BLOCKS_NTSC, VIS_STC007_BLOCKS_PAL, VIS_STC007_ASM_NTSC, VIS_STC007_ASM_PAL)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_PKG, "libsdvpcm_hip.so")
-
-LINE_DTYPE = np.dtype([("frame_number", "<u4"), ("line_number", "<u2"), ("words", "<u2", (9,)),
-                       ("calc_crc", "<u2"), ("data_start", "<i2"), ("data_stop", "<i2"),
-                       ("marker_start_bg_coord", "<u2"), ("marker_start_ed_coord", "<u2"),
-                       ("marker_stop_ed_coord", "<u2"),
-                       ("black_level", "u1"), ("white_level", "u1"), ("ref_low", "u1"), ("ref_level", "u1"),
-                       ("ref_high", "u1"), ("hysteresis_depth", "u1"), ("shift_stage", "u1"),
-                       ("service_type", "u1"), ("mark_st_stage", "u1"), ("mark_ed_stage", "u1"),
-                       ("flags", "u1"), ("word_state", "u1")])
-STATS_DTYPE = np.dtype([("frame_id", "<u4"), ("line_length", "<u2"), ("lines_odd", "<u2"), ("lines_even", "<u2"),
-                        ("lines_pcm_odd", "<u2"), ("lines_pcm_even", "<u2"), ("lines_bad_odd", "<u2"),
-                        ("lines_bad_even", "<u2"), ("lines_dup_odd", "<u2"), ("lines_dup_even", "<u2"),
-                        ("data_start", "<i2"), ("data_stop", "<i2"), ("data_from_doubled", "u1"),
-                        ("data_not_sure", "u1"), ("_pad", "u1", (4,))])
-assert LINE_DTYPE.itemsize == 48 and STATS_DTYPE.itemsize == 32
-
-# enums of include/sdvpcm.h
-PCM_PCM1, PCM_PCM16X0, PCM_STC007 = 0, 1, 2
-TYPE_M2 = 3                      # VideoToDigital::TYPE_M2 (videotodigital.h:77)
-MODE_DRAFT, MODE_FAST, MODE_NORMAL, MODE_INSANE = 0, 1, 2, 3
-FLAG_NEW_FILE, FLAG_DOUBLED, FLAG_END_FILE = 1, 2, 4
-DEEMPH_OFF, DEEMPH_AUTO, DEEMPH_FORCE = 0, 1, 2       # sdv_set_deemphasis
-RESAMPLE_OFF, RESAMPLE_TO_44100 = 0, 1                # sdv_set_resample
-FRAME_EMPTY = 1                 # sdv_set_frame_flags: SDV_FRAME_EMPTY
-PIX_GRAY8, PIX_UYVY422, PIX_YUYV422, PIX_V210, PIX_GRAY10LE, PIX_RGB24, PIX_BGR24, PIX_RGB0, PIX_BGR0 = range(9)      # SDV_PIX_*
-PIX_FORMATS = {"gray8": PIX_GRAY8, "uyvy422": PIX_UYVY422, "yuyv422": PIX_YUYV422, "v210": PIX_V210, "gray10le": PIX_GRAY10LE,
-               "rgb24": PIX_RGB24, "bgr24": PIX_BGR24, "rgb0": PIX_RGB0, "bgr0": PIX_BGR0}
-COLOR_BW, COLOR_R, COLOR_G, COLOR_B = 0, 1, 2, 3       # SDV_COLOR_* (vid_preset_t::COLOR_*)
-INGEST_DOUBLE_OFF, INGEST_DOUBLE_ON, INGEST_DOUBLE_AUTO = 0, 1, 2
-ENC_NTSC, ENC_PAL = 0, 1                               # SDV_ENC_*
-ENC_14BIT, ENC_16BIT = 0, 1
-ENC_TFF, ENC_BFF = 0, 1
-ENC_CTRL_COPY_PROHIBITED, ENC_CTRL_EMPHASIS = 1, 2
-ENC_FMT_PCM1, ENC_FMT_PCM16X0_SI, ENC_FMT_PCM16X0_EI = 0, 1, 2
-ENC_ML_EMPHASIS, ENC_ML_RATE_44100, ENC_ML_CODE = 1, 2, 4
-VIS_STC007_LINES, VIS_PCM1_LINES, VIS_PCM16X0_LINES, VIS_STC007_BLOCKS_NTSC, VIS_STC007_BLOCKS_PAL, VIS_STC007_ASM_NTSC, VIS_STC007_ASM_PAL = 0, 1, 2, 3, 4, 5, 6   # SDV_VIS_*
-
-
-class BinPreset(C.Structure):
-    """bin_preset_t (binarizer.h:163-186)"""
-    _fields_ = [(n, C.c_uint8) for n in ("max_black_lvl", "min_white_lvl", "min_contrast", "min_ref_lvl",
-                                          "max_ref_lvl", "min_valid_crcs", "mark_max_dist", "left_bit_pick",
-                                          "right_bit_pick", "en_force_coords", "en_coord_search",
-                                          "en_first_line_dup", "en_good_no_marker", "_pad")] + \
-               [("horiz_start", C.c_int16), ("horiz_stop", C.c_int16)]
-
-
-class IngestDesc(C.Structure):
-    """sdv_ingest_desc"""
-    _fields_ = [("pix_fmt", C.c_uint8), ("colors", C.c_uint8), ("double_width", C.c_uint8), ("_pad", C.c_uint8),
-                ("crop_left", C.c_uint16), ("crop_right", C.c_uint16), ("crop_top", C.c_uint16), ("crop_bottom", C.c_uint16),
-                ("src_width", C.c_int32), ("src_height", C.c_int32)]
-
-
-assert C.sizeof(IngestDesc) == 20
-
-
-class EncodeDesc(C.Structure):
-    """sdv_encode_desc"""
-    _fields_ = [("video_standard", C.c_uint8), ("resolution", C.c_uint8), ("ctrl_block", C.c_uint8), ("ctrl_flags", C.c_uint8),
-                ("field_order", C.c_uint8), ("black", C.c_uint8), ("white", C.c_uint8), ("_pad", C.c_uint8),
-                ("tc_index", C.c_uint8), ("tc_hour", C.c_uint8), ("tc_minute", C.c_uint8), ("tc_second", C.c_uint8), ("tc_field", C.c_uint8),
-                ("_pad2", C.c_uint8 * 3),
-                ("width", C.c_int32), ("height", C.c_int32), ("data_start", C.c_int32), ("data_stop", C.c_int32), ("top_line", C.c_int32)]
-
-
-assert C.sizeof(EncodeDesc) == 36
-
-
-class EncodeMarkerlessDesc(C.Structure):
-    """sdv_encode_markerless_desc"""
-    _fields_ = [("format", C.c_uint8), ("field_order", C.c_uint8), ("black", C.c_uint8), ("white", C.c_uint8),
-                ("header_lines", C.c_uint8), ("ctrl_flags", C.c_uint8), ("_pad", C.c_uint8 * 2),
-                ("width", C.c_int32), ("height", C.c_int32), ("data_start", C.c_int32), ("data_stop", C.c_int32), ("top_line", C.c_int32)]
-
-
-assert C.sizeof(EncodeMarkerlessDesc) == 28
-
-
-class DeintSettings(C.Structure):
-    """STC007Deinterleaver settings (stc007deinterleaver.h:151-161)"""
-    _fields_ = [("res_mode", C.c_uint8), ("ignore_crc", C.c_uint8), ("force_ecc_check", C.c_uint8),
-                ("en_p_code", C.c_uint8), ("en_q_code", C.c_uint8), ("en_cwd", C.c_uint8), ("_pad", C.c_uint8 * 2)]
-
-
-DEINT_LINE_DTYPE = np.dtype([("frame_number", "<u4"), ("line_number", "<u2"), ("words", "<u2", (8,)),
-                             ("word_crc_ok", "u1"), ("flags", "u1")])
-BLOCK_DTYPE = np.dtype([("w_frame", "<u4", (8,)), ("w_line", "<u2", (8,)), ("words", "<u2", (8,)),
-                        ("line_crc", "u1"), ("cwd_fixed", "u1"), ("word_valid", "u1"), ("resolution", "u1"),
-                        ("audio_state", "u1"), ("cwd_applied", "u1"), ("sample_rate", "<u2")])
-assert DEINT_LINE_DTYPE.itemsize == 24 and BLOCK_DTYPE.itemsize == 72
-
-
-class StitchSettings(C.Structure):
-    """STC007DataStitcher settings (slots stc007datastitcher.h:331-350)"""
-    _fields_ = [("video_standard", C.c_uint8), ("field_order", C.c_uint8), ("enable_p", C.c_uint8), ("enable_q", C.c_uint8),
-                ("enable_cwd", C.c_uint8), ("m2_format", C.c_uint8), ("resolution_preset", C.c_uint8), ("max_unch_14", C.c_uint8),
-                ("max_unch_16", C.c_uint8), ("use_ecc", C.c_uint8), ("mask_seams", C.c_uint8), ("broke_mask", C.c_uint8),
-                ("top_line_fix", C.c_uint8), ("_pad", C.c_uint8), ("sample_rate_preset", C.c_uint16)]
-
-
-class Pcm1StitchSettings(C.Structure):
-    """PCM1DataStitcher settings (slots pcm1datastitcher.h:183-190)"""
-    _fields_ = [("field_order", C.c_uint8), ("auto_offset", C.c_uint8), ("use_ecc", C.c_uint8), ("odd_offset", C.c_int8),
-                ("even_offset", C.c_int8), ("_pad", C.c_uint8 * 3)]
-
-
-class Pcm16x0StitchSettings(C.Structure):
-    """PCM16X0DataStitcher settings (slots pcm16x0datastitcher.h:304-314)"""
-    _fields_ = [("format", C.c_uint8), ("field_order", C.c_uint8), ("p_correction", C.c_uint8), ("use_ecc", C.c_uint8),
-                ("mask_seams", C.c_uint8), ("broke_mask", C.c_uint8), ("sample_rate_preset", C.c_uint16)]
-
-
-class StitchInfo(C.Structure):
-    _fields_ = [("steps", C.c_uint32), ("rounds", C.c_uint32), ("steps_launched", C.c_uint32), ("pipelined", C.c_uint32),
-                ("device_ms", C.c_float), ("direct_frames", C.c_uint32)]
-
-
-PAIR_DTYPE = np.dtype([("audio_word", "<i2", (2,)), ("sample_flags", "u1", (2,)), ("sample_rate", "<u2"),
-                       ("emphasis", "u1"), ("service_type", "u1"), ("_pad", "<u2")])
-assert PAIR_DTYPE.itemsize == 12 and C.sizeof(StitchSettings) == 16
-
-
-class RunInfo(C.Structure):
-    _fields_ = [("frames", C.c_uint32), ("rounds", C.c_uint32), ("frames_launched", C.c_uint32), ("frames_general", C.c_uint32),
-                ("kernel_ms", C.c_float), ("sweeps", C.c_uint32), ("frames_met", C.c_uint32)]
-
-
 _lib = None
 
 
@@ -160,164 +41,10 @@ def load_library(path: str | None = None):
     if not os.path.exists(p):
         raise RuntimeError(f"{p} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
-    lib = C.CDLL(p)
-    lib.sdv_engine_create.restype = C.c_void_p
-    lib.sdv_engine_create.argtypes = [C.c_int]
-    lib.sdv_engine_destroy.argtypes = [C.c_void_p]
-    lib.sdv_last_error.restype = C.c_char_p
-    lib.sdv_last_error.argtypes = [C.c_void_p]
-    lib.sdv_abi_version.restype = C.c_int
-    lib.sdv_default_bin_preset.argtypes = [C.POINTER(BinPreset)]
-    lib.sdv_set_mode.argtypes = [C.c_void_p, C.c_int]
-    lib.sdv_set_bin_preset.argtypes = [C.c_void_p, C.POINTER(BinPreset)]
-    lib.sdv_set_check_line_dup.argtypes = [C.c_void_p, C.c_int]
-    lib.sdv_set_pcm_type.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    lib.sdv_reset_stream.argtypes = [C.c_void_p]
-    lib.sdv_set_frame_flags.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.sdv_needs_double_width.argtypes = [C.c_int]
-    lib.sdv_double_width.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.sdv_ingest_geometry.argtypes = [C.POINTER(IngestDesc), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
-    lib.sdv_ingest_frames.argtypes = [C.c_void_p, C.POINTER(IngestDesc), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
-    lib.sdv_encode_geometry.argtypes = [C.POINTER(EncodeDesc), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
-    lib.sdv_encode_frames.argtypes = [C.c_void_p, C.POINTER(EncodeDesc), C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
-    lib.sdv_reset_encoder.argtypes = [C.c_void_p]
-    lib.sdv_encode_markerless_geometry.argtypes = [C.POINTER(EncodeMarkerlessDesc), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
-    lib.sdv_encode_markerless_frames.argtypes = [C.c_void_p, C.POINTER(EncodeMarkerlessDesc), C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t,
-                                                 C.c_void_p]
-    lib.sdv_vis_canvas_size.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    lib.sdv_vis_reset.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    lib.sdv_vis_render_lines.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
-    lib.sdv_vis_render_blocks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.sdv_set_stitch_block_output.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.sdv_stitch_block_count.restype = C.c_size_t
-    lib.sdv_stitch_block_count.argtypes = [C.c_void_p]
-    for nm in ("sdv_set_pcm1_stitch_block_output", "sdv_set_pcm1_stitch_line_output", "sdv_set_pcm16x0_stitch_block_output", "sdv_set_pcm16x0_stitch_line_output"):
-        getattr(lib, nm).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    for nm in ("sdv_pcm1_stitch_block_count", "sdv_pcm1_stitch_line_count", "sdv_pcm16x0_stitch_block_count", "sdv_pcm16x0_stitch_line_count"):
-        getattr(lib, nm).restype = C.c_size_t
-        getattr(lib, nm).argtypes = [C.c_void_p]
-    lib.sdv_set_stitch_line_output.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.sdv_stitch_line_count.restype = C.c_size_t
-    lib.sdv_stitch_line_count.argtypes = [C.c_void_p]
-    lib.sdv_stitch_line_counts.restype = C.c_size_t
-    lib.sdv_stitch_line_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.sdv_vis_render_asm_lines.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.sdv_get_run_info.argtypes = [C.c_void_p, C.POINTER(RunInfo)]
-    lib.sdv_set_profiling.argtypes = [C.c_void_p, C.c_int]
-    lib.sdv_get_chain_state.argtypes = [C.c_void_p, C.c_void_p]
-    lib.sdv_set_chain_state.argtypes = [C.c_void_p, C.c_void_p]
-    lib.sdv_records_per_frame.restype = C.c_size_t
-    lib.sdv_records_per_frame.argtypes = [C.c_int]
-    lib.sdv_binarize_frames.restype = C.c_int
-    lib.sdv_binarize_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
-                                        C.c_uint32, C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.sdv_binarize_records.restype = C.c_size_t
-    lib.sdv_binarize_records.argtypes = [C.c_int, C.c_int, C.c_uint]
-    lib.sdv_pcm1_binarize_frames.restype = C.c_int
-    lib.sdv_pcm1_binarize_frames.argtypes = lib.sdv_binarize_frames.argtypes
-    lib.sdv_pcm16x0_binarize_frames.restype = C.c_int
-    lib.sdv_pcm16x0_binarize_frames.argtypes = lib.sdv_binarize_frames.argtypes
-    lib.sdv_pcm16x0_binarize_records.restype = C.c_size_t
-    lib.sdv_pcm16x0_binarize_records.argtypes = [C.c_int, C.c_int, C.c_uint]
-    if hasattr(lib, "sdv_binarize_lines"):      # (SDVPCM_LIB may name a build of an earlier ABI: tuning comparisons across rounds)
-        lib.sdv_binarize_lines.restype = C.c_int
-        lib.sdv_binarize_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint16, C.c_uint16,
-                                           C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.sdv_pcm1_binarize_lines.restype = C.c_int
-    lib.sdv_pcm1_binarize_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint16,
-                                            C.c_uint16, C.c_uint, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.sdv_pcm16x0_binarize_lines.restype = C.c_int
-    lib.sdv_pcm16x0_binarize_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint16,
-                                               C.c_uint16, C.c_uint, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    lib.sdv_default_deint_settings.argtypes = [C.POINTER(DeintSettings)]
-    lib.sdv_deinterleave_blocks.restype = C.c_int
-    lib.sdv_deinterleave_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(DeintSettings), C.c_void_p, C.c_size_t,
-                                            C.c_void_p]
-    lib.sdv_default_stitch_settings.argtypes = [C.POINTER(StitchSettings)]
-    lib.sdv_set_stitch_settings.argtypes = [C.c_void_p, C.POINTER(StitchSettings)]
-    lib.sdv_reset_stitcher.argtypes = [C.c_void_p]
-    lib.sdv_get_stitch_info.argtypes = [C.c_void_p, C.POINTER(StitchInfo)]
-    lib.sdv_default_pcm1_stitch_settings.argtypes = [C.POINTER(Pcm1StitchSettings)]
-    lib.sdv_set_pcm1_stitch_settings.argtypes = [C.c_void_p, C.POINTER(Pcm1StitchSettings)]
-    lib.sdv_pcm1_stitch_frames.restype = C.c_int
-    lib.sdv_pcm1_stitch_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
-                                           C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
-    lib.sdv_pcm1_bin_to_line_recs.restype = C.c_int
-    lib.sdv_pcm1_bin_to_line_recs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    lib.sdv_default_pcm16x0_stitch_settings.argtypes = [C.POINTER(Pcm16x0StitchSettings)]
-    lib.sdv_set_pcm16x0_stitch_settings.argtypes = [C.c_void_p, C.POINTER(Pcm16x0StitchSettings)]
-    lib.sdv_pcm16x0_stitch_frames.restype = C.c_int
-    lib.sdv_pcm16x0_stitch_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
-                                              C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
-    lib.sdv_stitch_frames.restype = C.c_int
-    lib.sdv_stitch_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
-                                      C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
-    lib.sdv_stitch_state_size.restype = C.c_size_t
-    lib.sdv_get_stitch_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.sdv_set_stitch_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.sdv_saturate_stitch_stats.argtypes = [C.c_void_p]
-    lib.sdv_pcm16x0_chain_state_size.restype = C.c_size_t
-    lib.sdv_get_pcm16x0_chain_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.sdv_set_pcm16x0_chain_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.sdv_pcm16x0_stitch_state_size.restype = C.c_size_t
-    lib.sdv_get_pcm16x0_stitch_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.sdv_set_pcm16x0_stitch_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.sdv_saturate_pcm16x0_stitch_stats.argtypes = [C.c_void_p]
-    lib.sdv_set_audio_masking.argtypes = [C.c_void_p, C.c_int]
-    lib.sdv_reset_audio.argtypes = [C.c_void_p]
-    lib.sdv_audio_pending.restype = C.c_size_t
-    lib.sdv_audio_pending.argtypes = [C.c_void_p]
-    lib.sdv_audio_stalled.restype = C.c_int
-    lib.sdv_audio_stalled.argtypes = [C.c_void_p]
-    lib.sdv_audio_next_index.restype = C.c_uint64
-    lib.sdv_audio_next_index.argtypes = [C.c_void_p]
-    lib.sdv_audio_process.restype = C.c_int
-    lib.sdv_audio_process.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t,
-                                      C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.c_void_p]
-    lib.sdv_wav_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    lib.sdv_wav_header.argtypes = [C.c_void_p, C.c_uint64, C.c_uint16]
-    lib.sdv_wav_header.restype = None
-    lib.sdv_deemphasis_coeffs.argtypes = [C.c_uint16, C.POINTER(C.c_double)]
-    lib.sdv_deemphasis_coeffs.restype = None
-    lib.sdv_set_deemphasis.argtypes = [C.c_void_p, C.c_int]
-    lib.sdv_reset_deemphasis.argtypes = [C.c_void_p]
-    lib.sdv_audio_deemphasis.restype = C.c_int
-    lib.sdv_audio_deemphasis.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    lib.sdv_resample_taps.argtypes = [C.c_int, C.POINTER(C.c_double)]
-    lib.sdv_resample_taps.restype = None
-    lib.sdv_set_resample.argtypes = [C.c_void_p, C.c_int]
-    lib.sdv_reset_resample.argtypes = [C.c_void_p]
-    lib.sdv_audio_resample_pending.restype = C.c_size_t
-    lib.sdv_audio_resample_pending.argtypes = [C.c_void_p]
-    lib.sdv_audio_resample_room.restype = C.c_size_t
-    lib.sdv_audio_resample_room.argtypes = [C.c_void_p, C.c_size_t]
-    lib.sdv_audio_resample.restype = C.c_int
-    lib.sdv_audio_resample.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
-    lib.sdv_preemphasis_coeffs.argtypes = [C.c_uint16, C.POINTER(C.c_double)]
-    lib.sdv_preemphasis_coeffs.restype = None
-    lib.sdv_reset_preemphasis.argtypes = [C.c_void_p]
-    lib.sdv_pcm_preemphasis.restype = C.c_int
-    lib.sdv_pcm_preemphasis.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint16, C.c_void_p, C.c_void_p]
-    lib.sdv_pcm_preemphasis_clipped.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
-    lib.sdv_pcm_resample_taps.argtypes = [C.c_int, C.POINTER(C.c_double)]
-    lib.sdv_pcm_resample_taps.restype = None
-    lib.sdv_reset_pcm_resample.argtypes = [C.c_void_p]
-    lib.sdv_pcm_resample_pending.restype = C.c_size_t
-    lib.sdv_pcm_resample_pending.argtypes = [C.c_void_p]
-    lib.sdv_pcm_resample_room.restype = C.c_size_t
-    lib.sdv_pcm_resample_room.argtypes = [C.c_void_p, C.c_size_t]
-    lib.sdv_pcm_resample.restype = C.c_int
-    lib.sdv_pcm_resample.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
-    lib.sdv_decode_frames.restype = C.c_int
-    lib.sdv_decode_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint,
-                                      C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t,
-                                      C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.c_void_p]
+    lib = abi.bind(C.CDLL(p))
     if path is None:
         _lib = lib
     return lib
-
-
-AUDIO_PURGE_DTYPE = __import__("numpy").dtype([("first_pair", "<u8"), ("tag_index", "<u4"), ("kind", "u1"), ("_pad", "u1", (3,))])
 
 
 class Engine:

@@ -20,8 +20,7 @@ The frames a rank needs beyond its range: `warmup` frames before it and one fram
 stitcher turn needs); the last rank appends the end-of-file frame instead."""
 from __future__ import annotations
 
-
-PCM_STC007 = 2          # sdv_set_pcm_type / sdv_decode_frames: the STC-007 chain (sdvpcmdecoder_amd.engine.PCM_STC007)
+from .abi import PCM_STC007          # sdv_set_pcm_type / sdv_decode_frames: the STC-007 chain
 
 
 def shard_bounds(n_frames: int, rank: int, world: int):

@@ -14,6 +14,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from .abi import PCM1_LINE_DTYPE, PCM16X0_BIN_DTYPE  # noqa: F401  (sdv_pcm1_line_rec, sdv_pcm16x0_bin_rec)
+
 BITS_IN_LINE = 137
 WORD_MASK = 0x3FFF
 
@@ -288,10 +290,6 @@ def interleave_stream_f1(audio16: np.ndarray) -> np.ndarray:
 
 
 # ---- PCM-1 line streams (records of the PCM-1 back half, sdv_pcm1_line_rec) -----------------------------------------
-PCM1_LINE_DTYPE = np.dtype([("frame_number", "<u4"), ("line_number", "<u2"), ("words", "<u2", (7,)), ("calc_crc", "<u2"),
-                            ("ref_level", "u1"), ("picked_bits_left", "u1"), ("picked_bits_right", "u1"), ("service_type", "u1"),
-                            ("flags", "u1"), ("_pad", "u1", (5,))])
-assert PCM1_LINE_DTYPE.itemsize == 32
 
 
 def pcm1_crc_words(words6):
@@ -305,7 +303,6 @@ def pcm1_crc_words(words6):
             top = ((crc >> 15) & 1) ^ bit
             crc = ((crc << 1) & 0xFFFF) ^ (top * 0x1021)
     return ((~crc) & 0xFFFF).astype(np.uint16)
-
 
 
 def pcm1_line_bits(words7: np.ndarray) -> np.ndarray:
@@ -474,13 +471,6 @@ def pcm1_frames(n_frames: int, seed: int = 0, width: int = 720, height: int = 48
 
 
 # ---- PCM-16x0 (Sony PCM-1610/1620/1630): 193 bit cells per line = 3 sub-lines of 3 x 16 bit + CRCC, one control bit ----------
-PCM16X0_BIN_DTYPE = np.dtype([("frame_number", "<u4"), ("line_number", "<u2"), ("words", "<u2", (4,)), ("calc_crc", "<u2"),
-                              ("data_start", "<i2"), ("data_stop", "<i2"), ("queue_order", "<u2"),
-                              ("black_level", "u1"), ("white_level", "u1"), ("ref_low", "u1"), ("ref_level", "u1"), ("ref_high", "u1"),
-                              ("hysteresis_depth", "u1"), ("shift_stage", "u1"), ("service_type", "u1"),
-                              ("picked_bits_left", "u1"), ("picked_bits_right", "u1"), ("flags", "u1"), ("line_part", "u1"),
-                              ("control_bit", "u1"), ("_pad", "u1")])
-assert PCM16X0_BIN_DTYPE.itemsize == 36
 
 
 def pcm16x0_crc_words(words3):

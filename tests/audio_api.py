@@ -5,15 +5,15 @@ import hashlib
 
 import numpy as np
 
+from sdvpcmdecoder_amd import abi
 from stitch_api import PAIR_DTYPE
+from sdvpcmdecoder_amd.abi import (SF_BLOCK_OK, SF_WORD_VALID, SF_WORD_FIXED, SF_WORD_MASKED, DROP_IGNORE, DROP_MUTE_BLOCK, DROP_MUTE_WORD,  # noqa: F401
+                                   DROP_HOLD_BLOCK, DROP_HOLD_WORD, DROP_INTER_LIN_BLOCK, DROP_INTER_LIN_WORD)
 
-PURGE_DTYPE = np.dtype([("first_pair", "<u8"), ("tag_index", "<u4"), ("kind", "u1"), ("_pad", "u1", (3,))])
-assert PAIR_DTYPE.itemsize == 12 and PURGE_DTYPE.itemsize == 16
+PURGE_DTYPE = abi.AUDIO_PURGE_DTYPE
 
-SF_BLOCK_OK, SF_WORD_VALID, SF_WORD_FIXED, SF_WORD_MASKED = 1, 2, 4, 8
-SRV_NEW_FILE, SRV_END_FILE = 1, 2
-DROP_IGNORE, DROP_MUTE_BLOCK, DROP_MUTE_WORD, DROP_HOLD_BLOCK, DROP_HOLD_WORD, DROP_INTER_LIN_BLOCK, DROP_INTER_LIN_WORD = range(7)
-PURGE_NEW_FILE, PURGE_END_FILE, PURGE_STOP = 1, 2, 3
+SRV_NEW_FILE, SRV_END_FILE = abi.PAIR_SRV_NEW_FILE, abi.PAIR_SRV_END_FILE
+PURGE_NEW_FILE, PURGE_END_FILE, PURGE_STOP = abi.AP_PURGE_NEW_FILE, abi.AP_PURGE_END_FILE, abi.AP_PURGE_STOP
 
 
 def tag(kind):
@@ -318,23 +318,6 @@ def wav_files(lib, prefix, out, purges):
 
 def digest(out, purges, masked):
     return hashlib.sha256(out.tobytes() + np.ascontiguousarray(purges).tobytes() + str(masked).encode()).hexdigest()
-
-
-def bind_product(lib):
-    """argtypes of the audio entry points of the C-ABI (product library or its emulator build)."""
-    lib.sdv_set_audio_masking.argtypes = [C.c_void_p, C.c_int]
-    lib.sdv_reset_audio.argtypes = [C.c_void_p]
-    lib.sdv_audio_pending.restype = C.c_size_t
-    lib.sdv_audio_pending.argtypes = [C.c_void_p]
-    lib.sdv_audio_next_index.restype = C.c_uint64
-    lib.sdv_audio_next_index.argtypes = [C.c_void_p]
-    lib.sdv_audio_process.restype = C.c_int
-    lib.sdv_audio_process.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t,
-                                      C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.c_void_p]
-    lib.sdv_wav_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    lib.sdv_wav_header.argtypes = [C.c_void_p, C.c_uint64, C.c_uint16]
-    lib.sdv_wav_header.restype = None
-    return lib
 
 
 def emu_audio(lib, eng, pairs, stop, out_cap=None, purges_cap=None):

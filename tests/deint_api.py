@@ -1,18 +1,13 @@
 """ctypes helpers for the deinterleave stage (oracle / reference / emulator / product share the PODs)."""
 import ctypes as C
 import numpy as np
+from sdvpcmdecoder_amd import abi
 
-DEINT_LINE_DTYPE = np.dtype([("frame_number", "<u4"), ("line_number", "<u2"), ("words", "<u2", (8,)),
-                             ("word_crc_ok", "u1"), ("flags", "u1")])
-BLOCK_DTYPE = np.dtype([("w_frame", "<u4", (8,)), ("w_line", "<u2", (8,)), ("words", "<u2", (8,)),
-                        ("line_crc", "u1"), ("cwd_fixed", "u1"), ("word_valid", "u1"), ("resolution", "u1"),
-                        ("audio_state", "u1"), ("cwd_applied", "u1"), ("sample_rate", "<u2")])
-assert DEINT_LINE_DTYPE.itemsize == 24 and BLOCK_DTYPE.itemsize == 72
+DEINT_LINE_DTYPE = abi.DEINT_LINE_DTYPE
+BLOCK_DTYPE = abi.BLOCK_DTYPE
 
 
-class DeintSettings(C.Structure):
-    _fields_ = [("res_mode", C.c_uint8), ("ignore_crc", C.c_uint8), ("force_ecc_check", C.c_uint8),
-                ("en_p_code", C.c_uint8), ("en_q_code", C.c_uint8), ("en_cwd", C.c_uint8), ("_pad", C.c_uint8 * 2)]
+DeintSettings = abi.DeintSettings
 
 
 def settings(res_mode=1, ignore_crc=0, force=1, p=1, q=1, cwd=0):

@@ -19,6 +19,7 @@ import numpy as np
 
 import audio_api as A
 import engine_api as ea
+from sdvpcmdecoder_amd import abi
 from stitch_api import PAIR_DTYPE
 
 GUARD = 256             # records behind every device output buffer
@@ -252,7 +253,6 @@ class Calls:
         dtype = pf.BIN1_DTYPE if hasattr(pf, "BIN1_DTYPE") else pf.BIN16_DTYPE
         if configure:
             lib.sdv_set_mode(eng, mode)
-            lib.sdv_set_bin_preset.argtypes = [C.c_void_p, C.POINTER(libs.BinPreset)]
             lib.sdv_set_bin_preset(eng, C.byref(pf._preset(st)))
             lib.sdv_set_check_line_dup(eng, st.get("check_line_dup", 1))
         luma = np.ascontiguousarray(luma)
@@ -320,36 +320,7 @@ DEVICE = Calls(Device())
 
 
 # ---- the two libraries behind one set of argument types --------------------------------------------------------------------------------------
-def bind_all(lib):
-    """Every entry point the twinned bodies call, on either build."""
-    VP, SZ, I = C.c_void_p, C.c_size_t, C.c_int
-    A.bind_product(ea.bind(lib))
-    lib.sdv_set_pcm16x0_stitch_settings.argtypes = [VP, VP]
-    stitch = [VP, VP, SZ, VP, SZ, C.POINTER(SZ), VP, SZ, C.POINTER(SZ), VP]
-    for nm in ("sdv_stitch_frames", "sdv_pcm1_stitch_frames", "sdv_pcm16x0_stitch_frames"):
-        getattr(lib, nm).restype, getattr(lib, nm).argtypes = I, stitch
-    for nm in ("sdv_set_stitch_block_output", "sdv_set_stitch_line_output", "sdv_set_pcm1_stitch_block_output", "sdv_set_pcm1_stitch_line_output",
-               "sdv_set_pcm16x0_stitch_block_output", "sdv_set_pcm16x0_stitch_line_output"):
-        getattr(lib, nm).restype, getattr(lib, nm).argtypes = I, [VP, VP, SZ]
-    for nm in ("sdv_stitch_block_count", "sdv_stitch_line_count", "sdv_pcm1_stitch_block_count", "sdv_pcm1_stitch_line_count",
-               "sdv_pcm16x0_stitch_block_count", "sdv_pcm16x0_stitch_line_count"):
-        getattr(lib, nm).restype, getattr(lib, nm).argtypes = SZ, [VP]
-    lib.sdv_stitch_line_counts.restype, lib.sdv_stitch_line_counts.argtypes = SZ, [VP, VP, SZ]
-    lib.sdv_audio_stalled.restype, lib.sdv_audio_stalled.argtypes = I, [VP]
-    lib.sdv_vis_render_lines.restype, lib.sdv_vis_render_lines.argtypes = I, [VP, I, VP, SZ, VP, SZ, C.POINTER(SZ), VP]
-    lib.sdv_vis_reset.restype, lib.sdv_vis_reset.argtypes = I, [VP, I, VP]
-    lib.sdv_vis_canvas_size.restype, lib.sdv_vis_canvas_size.argtypes = I, [I, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    for nm in ("sdv_vis_render_blocks", "sdv_vis_render_asm_lines"):
-        getattr(lib, nm).restype, getattr(lib, nm).argtypes = I, [VP, I, VP, SZ, VP, SZ, VP, SZ, VP]
-    lib.sdv_set_frame_flags.restype, lib.sdv_set_frame_flags.argtypes = I, [VP, VP, SZ]
-    frames = [VP, VP, SZ, SZ, I, I, I, C.c_uint32, C.c_uint, VP, SZ, VP, SZ, VP]
-    for nm in ("sdv_binarize_frames", "sdv_pcm1_binarize_frames", "sdv_pcm16x0_binarize_frames"):
-        getattr(lib, nm).restype, getattr(lib, nm).argtypes = I, frames
-    lib.sdv_decode_frames.restype = I
-    lib.sdv_decode_frames.argtypes = [VP, I, VP, SZ, SZ, I, I, I, C.c_uint32, C.c_uint, VP, SZ, C.POINTER(SZ), VP, SZ, C.POINTER(SZ), VP, SZ,
-                                      I, I, VP, SZ, C.POINTER(SZ), C.POINTER(C.c_uint64), VP]
-    lib.sdv_set_pcm_type.argtypes = [VP, I, I]
-    return lib
+bind_all = abi.bind          # every entry point the twinned bodies call, on either build
 
 
 _product = None

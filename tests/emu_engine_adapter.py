@@ -12,10 +12,6 @@ import stitch_api as sa
 class EmuEngine:
     def __init__(self, lib, mode=2):
         self.lib = ea.bind(lib)
-        self.lib.sdv_stitch_state_size.restype = C.c_size_t
-        self.lib.sdv_get_stitch_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        self.lib.sdv_set_stitch_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        self.lib.sdv_saturate_stitch_stats.argtypes = [C.c_void_p]
         self.h = C.c_void_p(self.lib.sdv_engine_create(0))
         self.lib.sdv_set_mode(self.h, mode)
 
@@ -43,10 +39,6 @@ class EmuEngine:
         """sdv_decode_frames on host memory: (pairs, frame descriptors, frame stats) like Engine.decode_frames."""
         import stitch_api as sa
         lib = self.lib
-        lib.sdv_decode_frames.restype = C.c_int
-        lib.sdv_decode_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint,
-                                          C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t,
-                                          C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.c_void_p]
         assert pcm_type == 2, "the adapter's fused call: STC-007"
         luma = np.ascontiguousarray(luma)
         n, hgt, w = luma.shape
@@ -107,7 +99,6 @@ class EmuEngine:
         import pcm1_api as p1
         recs = np.ascontiguousarray(recs)
         out = np.zeros(len(recs), dtype=p1.LINE1_DTYPE)
-        self.lib.sdv_pcm1_bin_to_line_recs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         assert self.lib.sdv_pcm1_bin_to_line_recs(self.h, recs.ctypes.data, len(recs), out.ctypes.data, None) == 0
         return out
 
@@ -120,7 +111,6 @@ class EmuEngine:
         return pairs.copy(), frames.copy()
 
     def set_pcm16x0_stitch_settings(self, st):
-        self.lib.sdv_set_pcm16x0_stitch_settings.argtypes = [C.c_void_p, C.c_void_p]
         assert self.lib.sdv_set_pcm16x0_stitch_settings(self.h, C.byref(st)) == 0
 
     def pcm16x0_stitch_frames(self, recs):
@@ -129,10 +119,8 @@ class EmuEngine:
         return pairs.copy(), frames.copy()
 
     def _blob(self, size_fn, get_fn):
-        size_fn.restype = C.c_size_t
         n = size_fn()
         buf = C.create_string_buffer(n)
-        get_fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         assert get_fn(self.h, buf, n) == 0
         return buf.raw
 
@@ -140,16 +128,13 @@ class EmuEngine:
         return self._blob(self.lib.sdv_pcm16x0_chain_state_size, self.lib.sdv_get_pcm16x0_chain_state)
 
     def set_pcm16x0_chain_state(self, b):
-        self.lib.sdv_set_pcm16x0_chain_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         assert self.lib.sdv_set_pcm16x0_chain_state(self.h, C.create_string_buffer(b, len(b)), len(b)) == 0
 
     def get_pcm16x0_stitch_state(self):
         return self._blob(self.lib.sdv_pcm16x0_stitch_state_size, self.lib.sdv_get_pcm16x0_stitch_state)
 
     def set_pcm16x0_stitch_state(self, b):
-        self.lib.sdv_set_pcm16x0_stitch_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         assert self.lib.sdv_set_pcm16x0_stitch_state(self.h, C.create_string_buffer(b, len(b)), len(b)) == 0
 
     def saturate_pcm16x0_stitch_stats(self):
-        self.lib.sdv_saturate_pcm16x0_stitch_stats.argtypes = [C.c_void_p]
         assert self.lib.sdv_saturate_pcm16x0_stitch_stats(self.h) == 0

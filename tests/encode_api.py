@@ -8,27 +8,19 @@ import ctypes as C
 import numpy as np
 
 import device_calls as dc
-from sdvpcmdecoder_amd import synth
+from sdvpcmdecoder_amd import abi, synth
 
-NTSC, PAL = 0, 1
-BIT14, BIT16 = 0, 1
-TFF, BFF = 0, 1
-COPY_PROHIBITED, EMPHASIS = 1, 2
-OK, BAD_ARG, NULL_VIDEO, NULL_PCM = 0, -1, 1, 2
+NTSC, PAL = abi.ENC_NTSC, abi.ENC_PAL
+BIT14, BIT16 = abi.ENC_14BIT, abi.ENC_16BIT
+TFF, BFF = abi.ENC_TFF, abi.ENC_BFF
+COPY_PROHIBITED, EMPHASIS = abi.ENC_CTRL_COPY_PROHIBITED, abi.ENC_CTRL_EMPHASIS
+OK, BAD_ARG, NULL_VIDEO, NULL_PCM = abi.OK, abi.ERR_BAD_ARG, abi.ERR_NULL_VIDEO, abi.ERR_NULL_PCM
 LPF = {NTSC: 245, PAL: 294}
 FPS = {NTSC: 60, PAL: 50}
 FILL, TAIL = 0x5A, 64           # what a destination buffer holds before the call; bytes behind its stated span
 
 
-class Desc(C.Structure):
-    _fields_ = [("video_standard", C.c_uint8), ("resolution", C.c_uint8), ("ctrl_block", C.c_uint8), ("ctrl_flags", C.c_uint8),
-                ("field_order", C.c_uint8), ("black", C.c_uint8), ("white", C.c_uint8), ("_pad", C.c_uint8),
-                ("tc_index", C.c_uint8), ("tc_hour", C.c_uint8), ("tc_minute", C.c_uint8), ("tc_second", C.c_uint8), ("tc_field", C.c_uint8),
-                ("_pad2", C.c_uint8 * 3),
-                ("width", C.c_int32), ("height", C.c_int32), ("data_start", C.c_int32), ("data_stop", C.c_int32), ("top_line", C.c_int32)]
-
-
-assert C.sizeof(Desc) == 36
+Desc = abi.EncodeDesc
 
 
 def desc(std=NTSC, res=BIT14, ctrl=0, ctrl_flags=0, order=TFF, black=30, white=200, tc=(0, 0, 0, 0, 0), width=720, height=486,
@@ -38,16 +30,7 @@ def desc(std=NTSC, res=BIT14, ctrl=0, ctrl_flags=0, order=TFF, black=30, white=2
                 data_start, data_stop, top_line)
 
 
-def bind(lib):
-    VP, SZ, I = C.c_void_p, C.c_size_t, C.c_int
-    lib.sdv_encode_geometry.restype, lib.sdv_encode_geometry.argtypes = I, [C.POINTER(Desc), C.POINTER(SZ), C.POINTER(I), C.POINTER(SZ)]
-    lib.sdv_encode_frames.restype, lib.sdv_encode_frames.argtypes = I, [VP, C.POINTER(Desc), VP, SZ, I, VP, SZ, SZ, VP]
-    lib.sdv_reset_encoder.restype, lib.sdv_reset_encoder.argtypes = I, [VP]
-    lib.sdv_abi_version.restype = I
-    lib.sdv_last_error.restype, lib.sdv_last_error.argtypes = C.c_char_p, [VP]
-    lib.sdv_engine_create.restype, lib.sdv_engine_create.argtypes = VP, [I]
-    lib.sdv_engine_destroy.argtypes = [VP]
-    return lib
+bind = abi.bind
 
 
 def emu(emu_lib):

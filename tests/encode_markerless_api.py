@@ -8,51 +8,35 @@ import ctypes as C
 import numpy as np
 
 import device_calls as dc
-from sdvpcmdecoder_amd import synth
+from sdvpcmdecoder_amd import abi, synth
 
-PCM1, SI, EI = 0, 1, 2
-TFF, BFF = 0, 1
-EMPHASIS, RATE_44100, CODE = 1, 2, 4
-OK, BAD_ARG, NULL_VIDEO, NULL_PCM = 0, -1, 1, 2
+PCM1, SI, EI = abi.ENC_FMT_PCM1, abi.ENC_FMT_PCM16X0_SI, abi.ENC_FMT_PCM16X0_EI
+TFF, BFF = abi.ENC_TFF, abi.ENC_BFF
+EMPHASIS, RATE_44100, CODE = abi.ENC_ML_EMPHASIS, abi.ENC_ML_RATE_44100, abi.ENC_ML_CODE
+OK, BAD_ARG, NULL_VIDEO, NULL_PCM = abi.OK, abi.ERR_BAD_ARG, abi.ERR_NULL_VIDEO, abi.ERR_NULL_PCM
 CELLS = {PCM1: 94, SI: 193, EI: 193}
 PAIRS_PER_FRAME, FIELD_PAIRS, LINES = 1470, 735, 245
 HEADER_WORDS = (0x0666, 0x0CCC, 0x1999, 0x1333, 0x0666, 0x0CCC, 0xCCCC)
 FILL, TAIL = 0x5A, 64           # what a destination buffer holds before the call; bytes behind its stated span
 
 
-class Desc(C.Structure):
-    _fields_ = [("format", C.c_uint8), ("field_order", C.c_uint8), ("black", C.c_uint8), ("white", C.c_uint8),
-                ("header_lines", C.c_uint8), ("ctrl_flags", C.c_uint8), ("_pad", C.c_uint8 * 2),
-                ("width", C.c_int32), ("height", C.c_int32), ("data_start", C.c_int32), ("data_stop", C.c_int32), ("top_line", C.c_int32)]
-
-
-assert C.sizeof(Desc) == 28
+Desc = abi.EncodeMarkerlessDesc
 
 
 def desc(fmt=PCM1, order=TFF, black=30, white=200, header=0, ctrl_flags=0, width=720, height=490, data_start=4, data_stop=716, top_line=0):
     return Desc(fmt, order, black, white, header, ctrl_flags, (C.c_uint8 * 2)(), width, height, data_start, data_stop, top_line)
 
 
-def bind(lib):
-    VP, SZ, I = C.c_void_p, C.c_size_t, C.c_int
-    lib.sdv_encode_markerless_geometry.restype, lib.sdv_encode_markerless_geometry.argtypes = I, [C.POINTER(Desc), C.POINTER(SZ), C.POINTER(I), C.POINTER(SZ)]
-    lib.sdv_encode_markerless_frames.restype, lib.sdv_encode_markerless_frames.argtypes = I, [VP, C.POINTER(Desc), VP, SZ, I, VP, SZ, SZ, VP]
-    lib.sdv_abi_version.restype = I
-    lib.sdv_last_error.restype, lib.sdv_last_error.argtypes = C.c_char_p, [VP]
-    lib.sdv_engine_create.restype, lib.sdv_engine_create.argtypes = VP, [I]
-    lib.sdv_engine_destroy.argtypes = [VP]
-    return lib
+bind = abi.bind
 
 
 def emu(emu_lib):
-    """the emulator build through device_calls' handle, with the marker-less encode entries (and encode_api's) bound"""
-    import encode_api
-    return bind(encode_api.bind(dc.emu_lib_of(emu_lib)))
+    """the emulator build through device_calls' handle, with every entry bound"""
+    return bind(dc.emu_lib_of(emu_lib))
 
 
 def product():
-    import encode_api
-    return bind(encode_api.bind(dc.product_lib()))
+    return bind(dc.product_lib())
 
 
 def geometry(lib, d):

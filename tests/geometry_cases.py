@@ -19,12 +19,12 @@ import pcm1_frames_api as p1f
 import pcm16_frames_api as p16f
 import pcm1_front_api as p1l
 import pcm16_front_api as p16l
-from sdvpcmdecoder_amd import synth
+from sdvpcmdecoder_amd import abi, synth
 
 PX_BYTES = 2048             # SDV_PX_BYTES (stc007_device.h): the widest line the marker-less entry points take, the LDS row of stage_row
-BAD_ARG = -1                # SDV_ERR_BAD_ARG
+BAD_ARG = abi.ERR_BAD_ARG
 GUARD = 0xA5                # what the records behind the ones a call may write are filled with
-PCM1, PCM16X0, STC007 = 0, 1, 2
+PCM1, PCM16X0, STC007 = abi.PCM_PCM1, abi.PCM_PCM16X0, abi.PCM_STC007
 N_FRAMES = 3
 TIGHT = "tight"             # gap: frame_stride = (h - 1) * row_stride + w, the smallest the entry points take (= -pad)
 
@@ -270,25 +270,7 @@ def first_difference(got, want):
 
 
 # ---- the entry points on host memory (the emulator build), strides passed through ---------------------------------------------------------------
-_FRAMES_ARGS = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                C.c_void_p]
-_LINES_ARGS = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint16, C.c_uint16, C.c_uint, C.c_int, C.c_void_p, C.c_size_t]
-_DECODE_ARGS = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint,
-                C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t,
-                C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.c_void_p]
-
-
-def bind(lib):
-    for fmt in FORMATS.values():
-        f = getattr(lib, fmt.frames_entry); f.restype = C.c_int; f.argtypes = _FRAMES_ARGS
-        f = getattr(lib, fmt.lines_entry); f.restype = C.c_int
-        f.argtypes = _LINES_ARGS + ([C.c_void_p] if fmt.recs_per_line == 1 else [C.c_void_p, C.c_void_p])
-        f = getattr(lib, fmt.count_fn); f.restype = C.c_size_t; f.argtypes = [C.c_int, C.c_int, C.c_uint]
-    lib.sdv_decode_frames.restype = C.c_int
-    lib.sdv_decode_frames.argtypes = _DECODE_ARGS
-    lib.sdv_set_pcm_type.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    lib.sdv_set_pcm16x0_stitch_settings.argtypes = [C.c_void_p, C.c_void_p]
-    return ea.bind(lib)
+bind = abi.bind
 
 
 def emu_configure(lib, eng, mode):

@@ -7,38 +7,27 @@ import ctypes as C
 import numpy as np
 
 import device_calls as dc
+from sdvpcmdecoder_amd import abi
 
-GRAY8, UYVY422, YUYV422, V210, GRAY10LE, RGB24, BGR24, RGB0, BGR0 = range(9)
-FORMATS = {"gray8": GRAY8, "uyvy422": UYVY422, "yuyv422": YUYV422, "v210": V210, "gray10le": GRAY10LE,
-           "rgb24": RGB24, "bgr24": BGR24, "rgb0": RGB0, "bgr0": BGR0}
+FORMATS = abi.PIX_FORMATS
+GRAY8, UYVY422, YUYV422, V210, GRAY10LE = abi.PIX_GRAY8, abi.PIX_UYVY422, abi.PIX_YUYV422, abi.PIX_V210, abi.PIX_GRAY10LE
+RGB24, BGR24, RGB0, BGR0 = abi.PIX_RGB24, abi.PIX_BGR24, abi.PIX_RGB0, abi.PIX_BGR0
 RGB_FORMATS = (RGB24, BGR24, RGB0, BGR0)
-BW, R, G, B = range(4)
-OFF, ON, AUTO = range(3)
-OK, BAD_ARG, UNSUPPORTED, NULL_VIDEO, NULL_PCM = 0, -1, -4, 1, 2
+BW, R, G, B = abi.COLOR_BW, abi.COLOR_R, abi.COLOR_G, abi.COLOR_B
+OFF, ON, AUTO = abi.INGEST_DOUBLE_OFF, abi.INGEST_DOUBLE_ON, abi.INGEST_DOUBLE_AUTO
+OK, BAD_ARG, UNSUPPORTED, NULL_VIDEO, NULL_PCM = abi.OK, abi.ERR_BAD_ARG, abi.ERR_UNSUPPORTED, abi.ERR_NULL_VIDEO, abi.ERR_NULL_PCM
 MAX_LINES = 640                 # LINES_PER_FRAME_MAX
 FILL, TAIL = 0x5A, 64           # what a destination buffer holds before the call; bytes behind its stated span
 
 
-class Desc(C.Structure):
-    _fields_ = [("pix_fmt", C.c_uint8), ("colors", C.c_uint8), ("double_width", C.c_uint8), ("_pad", C.c_uint8),
-                ("crop_left", C.c_uint16), ("crop_right", C.c_uint16), ("crop_top", C.c_uint16), ("crop_bottom", C.c_uint16),
-                ("src_width", C.c_int32), ("src_height", C.c_int32)]
+Desc = abi.IngestDesc
 
 
 def desc(fmt, w, h, crop=(0, 0, 0, 0), colors=BW, double=OFF):
     return Desc(fmt, colors, double, 0, crop[0], crop[1], crop[2], crop[3], w, h)
 
 
-def bind(lib):
-    VP, SZ, I = C.c_void_p, C.c_size_t, C.c_int
-    lib.sdv_ingest_geometry.restype, lib.sdv_ingest_geometry.argtypes = I, [C.POINTER(Desc), C.POINTER(I), C.POINTER(I), C.POINTER(I), C.POINTER(SZ)]
-    lib.sdv_ingest_frames.restype, lib.sdv_ingest_frames.argtypes = I, [VP, C.POINTER(Desc), VP, SZ, SZ, I, VP, SZ, SZ, VP]
-    lib.sdv_needs_double_width.restype, lib.sdv_needs_double_width.argtypes = I, [I]
-    lib.sdv_abi_version.restype = I
-    lib.sdv_last_error.restype, lib.sdv_last_error.argtypes = C.c_char_p, [VP]
-    lib.sdv_engine_create.restype, lib.sdv_engine_create.argtypes = VP, [I]
-    lib.sdv_engine_destroy.argtypes = [VP]
-    return lib
+bind = abi.bind
 
 
 def emu(emu_lib):

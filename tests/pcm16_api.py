@@ -6,35 +6,21 @@ import hashlib
 import numpy as np
 
 import libs
-from sdvpcmdecoder_amd import synth
+from sdvpcmdecoder_amd import abi, synth
 from stitch_api import PAIR_DTYPE
+from sdvpcmdecoder_amd.abi import SRV_NEW_FILE, SRV_END_FILE, SRV_FILLER, SRV_END_FIELD, SRV_END_FRAME, FA16_SILENCE, FA16_PADDING_OK  # noqa: F401
 
-SUB_DTYPE = synth.PCM16X0_BIN_DTYPE
-FRASM16_DTYPE = np.dtype([("frame_number", "<u4"),
-                          ("odd_std_lines", "<u2"), ("even_std_lines", "<u2"), ("odd_data_lines", "<u2"), ("even_data_lines", "<u2"),
-                          ("odd_valid_lines", "<u2"), ("even_valid_lines", "<u2"),
-                          ("odd_top_data", "<u2"), ("odd_bottom_data", "<u2"), ("even_top_data", "<u2"), ("even_bottom_data", "<u2"),
-                          ("odd_sample_rate", "<u2"), ("even_sample_rate", "<u2"),
-                          ("blocks_total", "<u2"), ("blocks_drop", "<u2"), ("samples_drop", "<u2"),
-                          ("odd_top_padding", "<u2"), ("odd_bottom_padding", "<u2"), ("even_top_padding", "<u2"), ("even_bottom_padding", "<u2"),
-                          ("blocks_broken", "<u2"), ("blocks_fix_bp", "<u2"), ("blocks_fix_p", "<u2"), ("blocks_fix_cwd", "<u2"),
-                          ("field_order", "u1"), ("odd_ref", "u1"), ("even_ref", "u1"), ("service_type", "u1"), ("flags", "u1"), ("_pad", "u1")])
+SUB_DTYPE = abi.PCM16X0_BIN_DTYPE
+FRASM16_DTYPE = abi.FRAME_ASM_PCM16X0_DTYPE
 BLOCK16_DTYPE = np.dtype([("frame_number", "<u4"), ("start_line", "<u2"), ("stop_line", "<u2"), ("queue_order", "<u2"),
                           ("start_part", "u1"), ("stop_part", "u1"), ("words", "<u2", (3, 3)), ("word_crc", "u1", (3, 3)), ("word_valid", "u1", (3, 3)),
                           ("picked_left", "u1", (3,)), ("picked_crc", "u1", (3,)), ("audio_state", "u1", (3,)), ("order_even", "u1"), ("ret", "u1"), ("_pad", "u1")])
-assert SUB_DTYPE.itemsize == 36 and FRASM16_DTYPE.itemsize == 56 and BLOCK16_DTYPE.itemsize == 60, (FRASM16_DTYPE.itemsize, BLOCK16_DTYPE.itemsize)
+assert BLOCK16_DTYPE.itemsize == 60        # the oracle's own block record, not one of the C-ABI
 
-SRV_NEW_FILE, SRV_END_FILE, SRV_FILLER, SRV_END_FIELD, SRV_END_FRAME = 1, 2, 3, 4, 5
-FORMAT_SI, FORMAT_EI = 1, 2
-FA16_SILENCE, FA16_PADDING_OK, FA16_EI = 16, 32, 64
+FORMAT_SI, FORMAT_EI, FA16_EI = abi.P16_FORMAT_SI, abi.P16_FORMAT_EI, abi.FA16_EI_FORMAT
 
 
-class Pcm16Settings(C.Structure):
-    _fields_ = [("format", C.c_uint8), ("field_order", C.c_uint8), ("p_correction", C.c_uint8), ("use_ecc", C.c_uint8),
-                ("mask_seams", C.c_uint8), ("broke_mask", C.c_uint8), ("sample_rate_preset", C.c_uint16)]
-
-
-assert C.sizeof(Pcm16Settings) == 8
+Pcm16Settings = abi.Pcm16x0StitchSettings
 
 
 def default_settings(**kw):
@@ -166,9 +152,7 @@ def run_cpu(lib, prefix, recs, st, pair_cap=None, frame_cap=None, overflow_ok=Fa
 
 
 # ---- what the stitcher hands to the visualiser (sdv_set_pcm16x0_stitch_block_output): sdv_pcm16x0_block_rec --------------------------------------
-VBLOCK16_DTYPE = np.dtype([("words", "<u2", (3, 3)), ("word_crc", "<u2"), ("word_valid", "<u2"), ("picked_left", "u1"), ("picked_crc", "u1"),
-                           ("audio_state", "u1", (3,)), ("flags", "u1"), ("sample_rate", "<u2"), ("_pad", "u1", (2,))])
-assert VBLOCK16_DTYPE.itemsize == 32
+VBLOCK16_DTYPE = abi.PCM16X0_BLOCK_DTYPE
 VIS_GOLDEN = ("si_bad10", "si_picked_forced", "ei_bad10", "si_file_marks")
 
 

@@ -5,10 +5,10 @@ import ctypes as C
 import numpy as np
 
 import libs
-from sdvpcmdecoder_amd import synth
+from sdvpcmdecoder_amd import abi, synth
+from sdvpcmdecoder_amd.abi import LF_COORDS_SWEEPED, LF_BY_EXT_TUNE, LF_BW_SET, LF_COORDS_SET, LF_FORCED_BAD, LF_CRC_VALID  # noqa: F401
 
-BIN16_DTYPE = synth.PCM16X0_BIN_DTYPE
-LF_COORDS_SWEEPED, LF_BY_EXT_TUNE, LF_BW_SET, LF_COORDS_SET, LF_FORCED_BAD, LF_CRC_VALID = 2, 4, 8, 16, 32, 64
+BIN16_DTYPE = abi.PCM16X0_BIN_DTYPE
 PARTS = (1, 2, 3)          # Binarizer::PART_PCM16X0_LEFT / _MIDDLE / _RIGHT
 
 
@@ -135,8 +135,7 @@ def make_case(name):
 
 
 # ---- the per-pass contract of sdv_pcm16x0_binarize_lines ---------------------------------------------------------------------------
-STATE_DTYPE = np.dtype([("black", "u1"), ("white", "u1"), ("ref", "u1"), ("sweep_flag", "u1"), ("start", "<i2"), ("stop", "<i2"), ("doubled", "u1"), ("_pad", "u1")])
-assert STATE_DTYPE.itemsize == 10
+STATE_DTYPE = abi.BIN_STATE_SHORT_DTYPE
 
 
 def run_lines_with_states(lib, prefix, luma, states, mode=1, coord_search=True, preset=None, doubled=False, first_line=1, frame=1):
@@ -230,12 +229,7 @@ def run_engine_lines(lib, eng, luma, states=None, mode=1, coord_search=True, pre
     """sdv_pcm16x0_binarize_lines on host buffers (the emulator build); one launch for all rows, pass `part` of row i preset with
     states[3 i + part].  -> (rc, records, scan_done behind each pass)"""
     f = lib.sdv_pcm16x0_binarize_lines
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint16, C.c_uint16, C.c_uint, C.c_int,
-                  C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    lib.sdv_set_mode.argtypes = [C.c_void_p, C.c_int]
     lib.sdv_set_mode(eng, mode)
-    lib.sdv_set_bin_preset.argtypes = [C.c_void_p, C.POINTER(libs.BinPreset)]
     p = preset if preset is not None else libs.default_preset()
     lib.sdv_set_bin_preset(eng, C.byref(p))
     luma = np.ascontiguousarray(luma)

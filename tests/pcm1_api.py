@@ -6,31 +6,17 @@ import hashlib
 import numpy as np
 
 import libs
-from sdvpcmdecoder_amd import synth
+from sdvpcmdecoder_amd import abi, synth
 from stitch_api import PAIR_DTYPE
+from sdvpcmdecoder_amd.abi import SRV_NEW_FILE, SRV_END_FILE, SRV_FILLER, SRV_END_FIELD, SRV_END_FRAME, LF_BW_SET, LF_FORCED_BAD  # noqa: F401
 
-LINE1_DTYPE = synth.PCM1_LINE_DTYPE
-FRASM1_DTYPE = np.dtype([("frame_number", "<u4"),
-                         ("odd_std_lines", "<u2"), ("even_std_lines", "<u2"), ("odd_data_lines", "<u2"), ("even_data_lines", "<u2"),
-                         ("odd_valid_lines", "<u2"), ("even_valid_lines", "<u2"),
-                         ("odd_top_data", "<u2"), ("odd_bottom_data", "<u2"), ("even_top_data", "<u2"), ("even_bottom_data", "<u2"),
-                         ("odd_sample_rate", "<u2"), ("even_sample_rate", "<u2"),
-                         ("blocks_total", "<u2"), ("blocks_drop", "<u2"), ("samples_drop", "<u2"),
-                         ("odd_top_padding", "<u2"), ("odd_bottom_padding", "<u2"), ("even_top_padding", "<u2"), ("even_bottom_padding", "<u2"),
-                         ("blocks_fix_bp", "<u2"),
-                         ("field_order", "u1"), ("odd_ref", "u1"), ("even_ref", "u1"), ("service_type", "u1"), ("flags", "u1"), ("_pad", "u1", (3,))])
-assert LINE1_DTYPE.itemsize == 32 and FRASM1_DTYPE.itemsize == 52, (LINE1_DTYPE.itemsize, FRASM1_DTYPE.itemsize)
+LINE1_DTYPE = abi.PCM1_LINE_DTYPE
+FRASM1_DTYPE = abi.FRAME_ASM_PCM1_DTYPE
 
-SRV_NEW_FILE, SRV_END_FILE, SRV_FILLER, SRV_END_FIELD, SRV_END_FRAME, SRV_HEADER = 1, 2, 3, 4, 5, 6
-LF_BW_SET, LF_FORCED_BAD = 8, 32
+SRV_HEADER = abi.SRV_HEADER_LINE
 
 
-class Pcm1Settings(C.Structure):
-    _fields_ = [("field_order", C.c_uint8), ("auto_offset", C.c_uint8), ("use_ecc", C.c_uint8), ("odd_offset", C.c_int8),
-                ("even_offset", C.c_int8), ("_pad", C.c_uint8 * 3)]
-
-
-assert C.sizeof(Pcm1Settings) == 8
+Pcm1Settings = abi.Pcm1StitchSettings
 
 
 def default_settings(**kw):
@@ -161,12 +147,9 @@ def run_cpu(lib, prefix, recs, st, pair_cap=None, frame_cap=None, overflow_ok=Fa
 
 
 # ---- what the stitcher hands to the visualiser (sdv_set_pcm1_stitch_block_output / _line_output) ----------------------------------------------
-BLOCK1_DTYPE = np.dtype([("frame_number", "<u4"), ("start_line", "<u2"), ("stop_line", "<u2"), ("interleave_num", "u1"), ("flags", "u1"), ("sample_rate", "<u2"),
-                         ("words", "<u2", (184,)), ("word_flags", "u1", (184,)), ("_pad", "u1", (12,))])
-ASM1_DTYPE = np.dtype([("frame_number", "<u4"), ("line_number", "<u2"), ("words", "<u2", (2,)), ("picked_bits_left", "u1"), ("picked_bits_right", "u1"),
-                       ("line_part", "u1"), ("flags", "u1"), ("_pad", "u1", (2,))])
-assert BLOCK1_DTYPE.itemsize == 576 and ASM1_DTYPE.itemsize == 16
-P1S_SKIP = 0x80
+BLOCK1_DTYPE = abi.PCM1_BLOCK_DTYPE
+ASM1_DTYPE = abi.PCM1_ASM_LINE_DTYPE
+P1S_SKIP = abi.P1S_SKIP
 
 
 def run_cpu_vis(lib, prefix, recs, st):

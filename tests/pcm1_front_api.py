@@ -5,14 +5,10 @@ import ctypes as C
 import numpy as np
 
 import libs
+from sdvpcmdecoder_amd import abi
+from sdvpcmdecoder_amd.abi import LF_COORDS_SWEEPED, LF_BY_EXT_TUNE, LF_BW_SET, LF_COORDS_SET, LF_FORCED_BAD, LF_CRC_VALID  # noqa: F401
 
-BIN1_DTYPE = np.dtype([("frame_number", "<u4"), ("line_number", "<u2"), ("words", "<u2", (7,)), ("calc_crc", "<u2"),
-                       ("data_start", "<i2"), ("data_stop", "<i2"),
-                       ("black_level", "u1"), ("white_level", "u1"), ("ref_low", "u1"), ("ref_level", "u1"), ("ref_high", "u1"),
-                       ("hysteresis_depth", "u1"), ("shift_stage", "u1"), ("service_type", "u1"),
-                       ("picked_bits_left", "u1"), ("picked_bits_right", "u1"), ("flags", "u1"), ("_pad", "u1", (3,))])
-assert BIN1_DTYPE.itemsize == 40
-LF_COORDS_SWEEPED, LF_BY_EXT_TUNE, LF_BW_SET, LF_COORDS_SET, LF_FORCED_BAD, LF_CRC_VALID = 2, 4, 8, 16, 32, 64
+BIN1_DTYPE = abi.PCM1_BIN_DTYPE
 
 
 def run_lines(lib, prefix, luma, mode=1, coord_search=True, preset=None, feedback="good", services=None, doubled=False, empty=None,
@@ -132,12 +128,7 @@ def make_case(name):
 def run_engine_lines(lib, eng, luma, states=None, mode=1, coord_search=True, preset=None, doubled=False, first_line=1, frame=1, line_step=1):
     """sdv_pcm1_binarize_lines on host buffers (the emulator build); one launch for all rows, row i preset with states[i]."""
     f = lib.sdv_pcm1_binarize_lines
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint16, C.c_uint16, C.c_uint, C.c_int,
-                  C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.sdv_set_mode.argtypes = [C.c_void_p, C.c_int]
     lib.sdv_set_mode(eng, mode)
-    lib.sdv_set_bin_preset.argtypes = [C.c_void_p, C.POINTER(libs.BinPreset)]
     p = preset if preset is not None else libs.default_preset()
     lib.sdv_set_bin_preset(eng, C.byref(p))
     luma = np.ascontiguousarray(luma)
@@ -148,8 +139,7 @@ def run_engine_lines(lib, eng, luma, states=None, mode=1, coord_search=True, pre
     return rc, out
 
 
-STATE_DTYPE = np.dtype([("black", "u1"), ("white", "u1"), ("ref", "u1"), ("sweep_flag", "u1"), ("start", "<i2"), ("stop", "<i2"), ("doubled", "u1"), ("_p2", "u1")])
-assert STATE_DTYPE.itemsize == 10
+STATE_DTYPE = abi.BIN_STATE_SHORT_DTYPE
 
 
 def run_lines_with_states(lib, prefix, luma, states, mode=1, coord_search=True, preset=None, doubled=False, first_line=1, frame=1, line_step=1):

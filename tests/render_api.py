@@ -9,14 +9,15 @@ import libs
 import oracle_run
 import pcm1_frames_api as p1f
 import pcm16_frames_api as p16f
-from sdvpcmdecoder_amd import synth
+from sdvpcmdecoder_amd import abi, synth
+from sdvpcmdecoder_amd.abi import SRV_FILLER, SRV_END_FRAME, LF_BW_SET, LF_COORDS_SET, LF_FORCED_BAD, LF_CRC_VALID  # noqa: F401
 
-STC007, PCM1, PCM16X0, STC007_BLOCKS_NTSC, STC007_BLOCKS_PAL, STC007_ASM_NTSC, STC007_ASM_PAL, PCM1_BLOCKS, PCM1_ASM, PCM16X0_BLOCKS = range(10)
+(STC007, PCM1, PCM16X0, STC007_BLOCKS_NTSC, STC007_BLOCKS_PAL, STC007_ASM_NTSC, STC007_ASM_PAL, PCM1_BLOCKS, PCM1_ASM, PCM16X0_BLOCKS) = (
+    abi.VIS_STC007_LINES, abi.VIS_PCM1_LINES, abi.VIS_PCM16X0_LINES, abi.VIS_STC007_BLOCKS_NTSC, abi.VIS_STC007_BLOCKS_PAL, abi.VIS_STC007_ASM_NTSC, abi.VIS_STC007_ASM_PAL,
+    abi.VIS_PCM1_BLOCKS, abi.VIS_PCM1_ASM, abi.VIS_PCM16X0_BLOCKS)
 SIZE = {STC007: (685, 650), PCM1: (752, 490), PCM16X0: (772, 490), STC007_BLOCKS_NTSC: (654, 490), STC007_BLOCKS_PAL: (654, 588),
         STC007_ASM_NTSC: (685, 490), STC007_ASM_PAL: (685, 588), PCM1_BLOCKS: (858, 368), PCM1_ASM: (624, 490), PCM16X0_BLOCKS: (678, 490)}   # width, height of the canvas
 BLANK = 0xFF000000                                                          # a canvas nothing was drawn on yet (QImage::fill(Qt::black))
-SRV_FILLER, SRV_END_FRAME = 3, 5
-LF_BW_SET, LF_COORDS_SET, LF_FORCED_BAD, LF_CRC_VALID = 8, 16, 32, 64
 
 
 def _stc_records(n, h, seed, mode=2, first_frame_no=1, p_dropout=0.0, **kw):
@@ -148,7 +149,7 @@ def digest(canvases, mask):
 
 # ---- the data blocks window (sdv_vis_render_blocks; RenderPCM::renderNewBlock(STC007DataBlock), renderpcm.cpp:1770-2051) ---------------------------
 # name: (canvas, scenario of tests/stitch_cases.py whose blocks are drawn)
-M2_SAMPLES = 0x100              # SDV_VIS_M2_SAMPLES, or-ed to a block canvas
+M2_SAMPLES = abi.VIS_M2_SAMPLES              # SDV_VIS_M2_SAMPLES, or-ed to a block canvas
 for _k in (STC007_BLOCKS_NTSC, STC007_BLOCKS_PAL):
     SIZE[_k | M2_SAMPLES] = SIZE[_k]
 BLOCK_CASES = {

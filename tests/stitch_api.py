@@ -2,33 +2,13 @@
 import ctypes as C
 import numpy as np
 import libs
+from sdvpcmdecoder_amd import abi
 
-PAIR_DTYPE = np.dtype([("audio_word", "<i2", (2,)), ("sample_flags", "u1", (2,)), ("sample_rate", "<u2"),
-                       ("emphasis", "u1"), ("service_type", "u1"), ("_pad", "<u2")])
-FRASM_DTYPE = np.dtype([("frame_number", "<u4"),
-                        ("odd_std_lines", "<u2"), ("even_std_lines", "<u2"), ("odd_data_lines", "<u2"), ("even_data_lines", "<u2"),
-                        ("odd_valid_lines", "<u2"), ("even_valid_lines", "<u2"),
-                        ("odd_top_data", "<u2"), ("odd_bottom_data", "<u2"), ("even_top_data", "<u2"), ("even_bottom_data", "<u2"),
-                        ("odd_sample_rate", "<u2"), ("even_sample_rate", "<u2"),
-                        ("blocks_total", "<u2"), ("blocks_drop", "<u2"), ("samples_drop", "<u2"),
-                        ("inner_padding", "<u2"), ("outer_padding", "<u2"),
-                        ("blocks_broken_field", "<u2"), ("blocks_broken_seam", "<u2"),
-                        ("blocks_fix_p", "<u2"), ("blocks_fix_q", "<u2"), ("blocks_fix_cwd", "<u2"),
-                        ("field_order", "u1"), ("odd_ref", "u1"), ("even_ref", "u1"), ("service_type", "u1"),
-                        ("video_standard", "u1"), ("tff_cnt", "u1"), ("bff_cnt", "u1"), ("odd_resolution", "u1"), ("even_resolution", "u1"),
-                        ("flags", "u1"), ("flags2", "u1"),
-                        ("ctrl_index", "i1"), ("ctrl_hour", "i1"), ("ctrl_minute", "i1"), ("ctrl_second", "i1"), ("ctrl_field", "i1")])
-assert PAIR_DTYPE.itemsize == 12 and FRASM_DTYPE.itemsize == 64, (PAIR_DTYPE.itemsize, FRASM_DTYPE.itemsize)
+PAIR_DTYPE = abi.PAIR_DTYPE
+FRASM_DTYPE = abi.FRAME_ASM_DTYPE
 
 
-class StitchSettings(C.Structure):
-    _fields_ = [("video_standard", C.c_uint8), ("field_order", C.c_uint8), ("enable_p", C.c_uint8), ("enable_q", C.c_uint8),
-                ("enable_cwd", C.c_uint8), ("m2_format", C.c_uint8), ("resolution_preset", C.c_uint8), ("max_unch_14", C.c_uint8),
-                ("max_unch_16", C.c_uint8), ("use_ecc", C.c_uint8), ("mask_seams", C.c_uint8), ("broke_mask", C.c_uint8),
-                ("top_line_fix", C.c_uint8), ("_pad", C.c_uint8), ("sample_rate_preset", C.c_uint16)]
-
-
-assert C.sizeof(StitchSettings) == 16
+StitchSettings = abi.StitchSettings
 
 
 def default_settings(**kw):
@@ -87,8 +67,7 @@ def run_cpu(lib, prefix, recs, st, pair_cap=None, frame_cap=None):
     return pairs[:n], frames[:min(nf.value, frame_cap)]
 
 
-BLOCK_DTYPE = np.dtype([("w_frame", "<u4", (8,)), ("w_line", "<u2", (8,)), ("words", "<u2", (8,)), ("line_crc", "u1"), ("cwd_fixed", "u1"), ("word_valid", "u1"),
-                        ("resolution", "u1"), ("audio_state", "u1"), ("cwd_applied", "u1"), ("sample_rate", "<u2")])     # sdv_block_rec, 72 bytes
+BLOCK_DTYPE = abi.BLOCK_DTYPE     # sdv_block_rec
 
 
 def run_cpu_blocks(lib, prefix, recs, st):
@@ -109,8 +88,7 @@ def run_cpu_blocks(lib, prefix, recs, st):
     return pairs[:n], frames[:min(nf.value, frame_cap)], blocks[:nb.value]
 
 
-ASM_DTYPE = np.dtype([("frame_number", "<u4"), ("line_number", "<u2"), ("words", "<u2", (9,)), ("calc_crc", "<u2"), ("word_crc_ok", "<u2"), ("word_valid", "<u2"),
-                      ("flags", "u1"), ("_pad", "u1")])       # sdv_asm_line_rec, 32 bytes
+ASM_DTYPE = abi.ASM_LINE_DTYPE       # sdv_asm_line_rec
 
 
 def last_asm_lines(lib, prefix):

@@ -27,53 +27,15 @@ import pcm16_frames_api as p16f
 import pcm16_front_api as p16l
 import render_api as ra
 import stitch_api as sa
-from sdvpcmdecoder_amd import synth
+from sdvpcmdecoder_amd import abi, synth
 
-VP, SZ, I, U, U16, U32, U64 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint, C.c_uint16, C.c_uint32, C.c_uint64
-PSZ = C.POINTER(C.c_size_t)
-PCM1, PCM16X0, STC007 = 0, 1, 2
-FRAMES_SIG = [VP, VP, SZ, SZ, I, I, I, U32, U, VP, SZ, VP, SZ, VP]
-STITCH_SIG = [VP, VP, SZ, VP, SZ, PSZ, VP, SZ, PSZ, VP]
-SIGS = {
-    "sdv_engine_destroy": [VP], "sdv_set_mode": [VP, I], "sdv_set_pcm_type": [VP, I, I], "sdv_reset_stream": [VP],
-    "sdv_binarize_frames": FRAMES_SIG, "sdv_pcm1_binarize_frames": FRAMES_SIG, "sdv_pcm16x0_binarize_frames": FRAMES_SIG,
-    "sdv_binarize_lines": [VP, VP, SZ, I, SZ, VP, U32, U16, U16, U, VP, SZ, VP],
-    "sdv_pcm1_binarize_lines": [VP, VP, SZ, I, SZ, VP, U32, U16, U16, U, I, VP, SZ, VP],
-    "sdv_pcm16x0_binarize_lines": [VP, VP, SZ, I, SZ, VP, U32, U16, U16, U, I, VP, SZ, VP, VP],
-    "sdv_deinterleave_blocks": [VP, VP, SZ, VP, VP, SZ, VP],
-    "sdv_stitch_frames": STITCH_SIG, "sdv_pcm1_stitch_frames": STITCH_SIG, "sdv_pcm16x0_stitch_frames": STITCH_SIG,
-    "sdv_set_stitch_settings": [VP, VP], "sdv_set_pcm1_stitch_settings": [VP, VP], "sdv_set_pcm16x0_stitch_settings": [VP, VP],
-    "sdv_pcm1_bin_to_line_recs": [VP, VP, SZ, VP, VP],
-    "sdv_decode_frames": [VP, I, VP, SZ, SZ, I, I, I, U32, U, VP, SZ, PSZ, VP, SZ, PSZ, VP, SZ, I, I, VP, SZ, PSZ, C.POINTER(U64), VP],
-    "sdv_double_width": [VP, VP, SZ, I, SZ, VP, SZ, VP],
-    "sdv_set_audio_masking": [VP, I], "sdv_set_deemphasis": [VP, I],
-    "sdv_audio_process": [VP, VP, SZ, I, VP, SZ, PSZ, VP, SZ, PSZ, C.POINTER(U64), VP],
-    "sdv_audio_deemphasis": [VP, VP, SZ, VP, VP], "sdv_wav_pack": [VP, VP, SZ, VP, VP],
-    "sdv_vis_render_lines": [VP, I, VP, SZ, VP, SZ, PSZ, VP],
-    "sdv_vis_render_blocks": [VP, I, VP, SZ, VP, SZ, VP, SZ, VP], "sdv_vis_render_asm_lines": [VP, I, VP, SZ, VP, SZ, VP, SZ, VP],
-    "sdv_get_chain_state": [VP, VP], "sdv_set_chain_state": [VP, VP],
-    "sdv_get_stitch_state": [VP, VP, SZ], "sdv_set_stitch_state": [VP, VP, SZ],
-    "sdv_get_pcm16x0_chain_state": [VP, VP, SZ], "sdv_set_pcm16x0_chain_state": [VP, VP, SZ],
-    "sdv_get_pcm16x0_stitch_state": [VP, VP, SZ], "sdv_set_pcm16x0_stitch_state": [VP, VP, SZ],
-    "sdv_reset_stitcher": [VP], "sdv_get_stitch_info": [VP, VP], "sdv_vis_reset": [VP, I, VP], "sdv_saturate_pcm16x0_stitch_stats": [VP],
-}
+VP, I, U16, U32 = C.c_void_p, C.c_int, C.c_uint16, C.c_uint32
+PCM1, PCM16X0, STC007 = abi.PCM_PCM1, abi.PCM_PCM16X0, abi.PCM_STC007
 
 
 def bind(lib):
-    """The C-ABI of the product library or of its emulator build through a handle of its own, so that the argument types set here (pointers
-    as integers, structures by reference) and the ones other test modules set on theirs do not meet."""
-    lib = C.CDLL(lib._name)
-    lib.sdv_engine_create.restype = VP
-    lib.sdv_engine_create.argtypes = [I]
-    lib.sdv_last_error.restype = C.c_char_p
-    lib.sdv_last_error.argtypes = [VP]
-    for nm in ("sdv_stitch_state_size", "sdv_pcm16x0_stitch_state_size", "sdv_pcm16x0_chain_state_size"):
-        getattr(lib, nm).restype = SZ
-    for nm, sig in SIGS.items():
-        f = getattr(lib, nm)
-        f.restype = C.c_int
-        f.argtypes = sig
-    return lib
+    """The C-ABI of the product library or of its emulator build through a handle of its own."""
+    return abi.bind(C.CDLL(lib._name))
 
 
 def ok(ctx, h, rc):

@@ -13,7 +13,6 @@ import pytest
 
 import audio_api as A
 import device_calls as dc
-import engine_api as ea
 import libs
 from stitch_api import PAIR_DTYPE
 
@@ -118,127 +117,121 @@ def test_wav_header_known_answers(oracle_lib):
 
 # ---- the kernels on the emulator -----------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def emu(emu_lib):
-    return A.bind_product(ea.bind(emu_lib))
-
-
-@pytest.fixture(scope="module")
 def gpu():
     return dc.product_lib()
 
 
 @pytest.mark.parametrize("name", SUPPORTED)
-def test_emu_matches_oracle(name, emu, oracle_lib):
+def test_emu_matches_oracle(name, emu_lib, oracle_lib):
     pairs, mode, ends, stop, want, idx, want_pur, want_masked, hit = _oracle(name)
-    out, pur, masked = A.emu_run(emu, pairs, mode, ends, stop)
+    out, pur, masked = A.emu_run(emu_lib, pairs, mode, ends, stop)
     assert out.tobytes() == want.tobytes(), _diff(out, want)
     assert pur.tobytes() == want_pur.tobytes() and masked == want_masked
 
 
-def _follows_the_reference_into_its_dead_ends(emu, via, oracle_lib):
-    emu.sdv_audio_stalled.argtypes = [C.c_void_p]
-    eng = emu.sdv_engine_create(0)
-    emu.sdv_set_audio_masking(eng, A.DROP_INTER_LIN_WORD)
+def _follows_the_reference_into_its_dead_ends(emu_lib, via, oracle_lib):
+    eng = emu_lib.sdv_engine_create(0)
+    emu_lib.sdv_set_audio_masking(eng, A.DROP_INTER_LIN_WORD)
     # a stream that starts with invalid samples and no NEW_FILE tag: the reference's window fills up and nothing can ever leave
     bad = A.audio(2000, 77, runs=[(0, 5, 2)])
-    rc, out, pur, masked, n_out, n_pur = via.audio(emu, eng, bad, 0)
-    assert rc == 0 and n_out == 0 and n_pur == 0 and emu.sdv_audio_pending(eng) == 512 and emu.sdv_audio_stalled(eng) == 1
+    rc, out, pur, masked, n_out, n_pur = via.audio(emu_lib, eng, bad, 0)
+    assert rc == 0 and n_out == 0 and n_pur == 0 and emu_lib.sdv_audio_pending(eng) == 512 and emu_lib.sdv_audio_stalled(eng) == 1
     want = A.run_cpu(oracle_lib, "orc_", bad, A.DROP_INTER_LIN_WORD, np.array([len(bad)], dtype=np.uint64), 0)
     assert want[4] == 1 and len(want[0]) == 0
     # ... nothing is taken any more, tags included
-    rc, out, pur, masked, n_out, n_pur = via.audio(emu, eng, A.tape(["N", A.audio(700, 3), "E"]), 0)
-    assert rc == 0 and n_out == 0 and n_pur == 0 and emu.sdv_audio_pending(eng) == 512 and emu.sdv_audio_stalled(eng) == 1
+    rc, out, pur, masked, n_out, n_pur = via.audio(emu_lib, eng, A.tape(["N", A.audio(700, 3), "E"]), 0)
+    assert rc == 0 and n_out == 0 and n_pur == 0 and emu_lib.sdv_audio_pending(eng) == 512 and emu_lib.sdv_audio_stalled(eng) == 1
     # ... until stop() purges the window as it is
-    rc, out, pur, masked, n_out, n_pur = via.audio(emu, eng, A.audio(10, 4), 1)
+    rc, out, pur, masked, n_out, n_pur = via.audio(emu_lib, eng, A.audio(10, 4), 1)
     want = A.run_cpu(oracle_lib, "orc_", bad, A.DROP_INTER_LIN_WORD, np.array([len(bad)], dtype=np.uint64), 1)
     assert rc == 0 and out.tobytes() == want[0].tobytes() and n_out == 511 and n_pur == 1 and pur[0]["kind"] == A.PURGE_STOP and pur[0]["first_pair"] == 511
-    assert emu.sdv_audio_stalled(eng) == 0 and emu.sdv_audio_pending(eng) == 1
+    assert emu_lib.sdv_audio_stalled(eng) == 0 and emu_lib.sdv_audio_pending(eng) == 1
     # a failed call takes nothing, also when an END_FILE that does not purge has split it into spans
     pairs, mode, ends, stop = A.make_input("tiny_files_bad")
-    emu.sdv_reset_audio(eng)
-    rc, out, pur, masked, n_out, n_pur = via.audio(emu, eng, pairs, 1, out_cap=300)
-    assert rc == -1 and b"too small" in emu.sdv_last_error(eng) and emu.sdv_audio_pending(eng) == 0 and emu.sdv_audio_next_index(eng) == 0
-    rc, out, pur, masked, n_out, n_pur = via.audio(emu, eng, pairs, 1)
+    emu_lib.sdv_reset_audio(eng)
+    rc, out, pur, masked, n_out, n_pur = via.audio(emu_lib, eng, pairs, 1, out_cap=300)
+    assert rc == -1 and b"too small" in emu_lib.sdv_last_error(eng) and emu_lib.sdv_audio_pending(eng) == 0 and emu_lib.sdv_audio_next_index(eng) == 0
+    rc, out, pur, masked, n_out, n_pur = via.audio(emu_lib, eng, pairs, 1)
     want = A.run_cpu(oracle_lib, "orc_", pairs, mode, ends, stop)
     assert rc == 0 and out.tobytes() == want[0].tobytes() and pur.tobytes() == want[2].tobytes() and masked == want[3]
     # a tag that is neither NEW_FILE nor END_FILE (PCMSamplePair has no such type)
     odd = A.tape(["N", A.audio(100, 78), A.tag(7), A.audio(100, 79)])
-    rc = via.audio(emu, eng, odd, 0)[0]
-    assert rc == -4 and b"neither NEW_FILE nor END_FILE" in emu.sdv_last_error(eng)
+    rc = via.audio(emu_lib, eng, odd, 0)[0]
+    assert rc == -4 and b"neither NEW_FILE nor END_FILE" in emu_lib.sdv_last_error(eng)
     # the engine is still usable
     pairs, mode, ends, stop = A.make_input("short_runs_lin")
-    emu.sdv_reset_audio(eng)
-    rc, out, pur, masked, _, _ = via.audio(emu, eng, pairs, 1)
+    emu_lib.sdv_reset_audio(eng)
+    rc, out, pur, masked, _, _ = via.audio(emu_lib, eng, pairs, 1)
     want = A.run_cpu(oracle_lib, "orc_", pairs, mode, ends, stop)
     assert rc == 0 and out.tobytes() == want[0].tobytes()
-    emu.sdv_engine_destroy(eng)
+    emu_lib.sdv_engine_destroy(eng)
 
 
-def test_emu_follows_the_reference_into_its_dead_ends(emu, oracle_lib):
-    _follows_the_reference_into_its_dead_ends(emu, dc.HOST, oracle_lib)
+def test_emu_follows_the_reference_into_its_dead_ends(emu_lib, oracle_lib):
+    _follows_the_reference_into_its_dead_ends(emu_lib, dc.HOST, oracle_lib)
 
 
-def _edge_inputs(emu, via, oracle_lib):
-    eng = emu.sdv_engine_create(0)
-    emu.sdv_set_audio_masking(eng, A.DROP_HOLD_WORD)
-    rc, out, pur, masked, _, _ = via.audio(emu, eng, np.zeros(0, dtype=PAIR_DTYPE), 0)           # empty
-    assert rc == 0 and len(out) == 0 and len(pur) == 0 and emu.sdv_audio_pending(eng) == 0
-    rc, out, pur, masked, _, _ = via.audio(emu, eng, A.tag(A.SRV_NEW_FILE), 0)                   # a lone NEW_FILE: the silent pair waits
-    assert rc == 0 and len(out) == 0 and len(pur) == 1 and pur[0]["kind"] == A.PURGE_NEW_FILE and emu.sdv_audio_pending(eng) == 1
+def _edge_inputs(emu_lib, via, oracle_lib):
+    eng = emu_lib.sdv_engine_create(0)
+    emu_lib.sdv_set_audio_masking(eng, A.DROP_HOLD_WORD)
+    rc, out, pur, masked, _, _ = via.audio(emu_lib, eng, np.zeros(0, dtype=PAIR_DTYPE), 0)           # empty
+    assert rc == 0 and len(out) == 0 and len(pur) == 0 and emu_lib.sdv_audio_pending(eng) == 0
+    rc, out, pur, masked, _, _ = via.audio(emu_lib, eng, A.tag(A.SRV_NEW_FILE), 0)                   # a lone NEW_FILE: the silent pair waits
+    assert rc == 0 and len(out) == 0 and len(pur) == 1 and pur[0]["kind"] == A.PURGE_NEW_FILE and emu_lib.sdv_audio_pending(eng) == 1
     few = A.audio(100, 5, runs=[(50, 10, 2)])
-    rc, out, pur, masked, _, _ = via.audio(emu, eng, few, 0)                                    # fewer than 227 pairs: no scan yet
-    assert rc == 0 and len(out) == 0 and emu.sdv_audio_pending(eng) == 101 and emu.sdv_audio_next_index(eng) == 0
-    rc, out, pur, masked, _, _ = via.audio(emu, eng, A.tag(A.SRV_END_FILE), 0)                   # the end of the file flushes it
+    rc, out, pur, masked, _, _ = via.audio(emu_lib, eng, few, 0)                                    # fewer than 227 pairs: no scan yet
+    assert rc == 0 and len(out) == 0 and emu_lib.sdv_audio_pending(eng) == 101 and emu_lib.sdv_audio_next_index(eng) == 0
+    rc, out, pur, masked, _, _ = via.audio(emu_lib, eng, A.tag(A.SRV_END_FILE), 0)                   # the end of the file flushes it
     want = A.run_cpu(oracle_lib, "orc_", A.tape(["N", few, "E"]), A.DROP_HOLD_WORD, np.array([1, 101, 102], dtype=np.uint64), 0)
-    assert rc == 0 and out.tobytes() == want[0].tobytes() and masked == want[3] and len(out) == 100 and emu.sdv_audio_pending(eng) == 1
-    assert emu.sdv_audio_next_index(eng) == 0
+    assert rc == 0 and out.tobytes() == want[0].tobytes() and masked == want[3] and len(out) == 100 and emu_lib.sdv_audio_pending(eng) == 1
+    assert emu_lib.sdv_audio_next_index(eng) == 0
     # output buffers too small: reported with the sizes, nothing taken, repeatable
     pairs, mode, ends, stop = A.make_input("two_files")
-    emu.sdv_reset_audio(eng)
-    rc, out, pur, masked, n_out, n_pur = via.audio(emu, eng, pairs, 1, out_cap=100)
-    assert rc == -1 and b"too small" in emu.sdv_last_error(eng) and n_out == 3400 and n_pur == 5 and emu.sdv_audio_pending(eng) == 0
-    rc, out, pur, masked, n_out, n_pur = via.audio(emu, eng, pairs, 1, purges_cap=2)
+    emu_lib.sdv_reset_audio(eng)
+    rc, out, pur, masked, n_out, n_pur = via.audio(emu_lib, eng, pairs, 1, out_cap=100)
+    assert rc == -1 and b"too small" in emu_lib.sdv_last_error(eng) and n_out == 3400 and n_pur == 5 and emu_lib.sdv_audio_pending(eng) == 0
+    rc, out, pur, masked, n_out, n_pur = via.audio(emu_lib, eng, pairs, 1, purges_cap=2)
     assert rc == -1 and n_out == 3400 and n_pur == 5
-    rc, out, pur, masked, n_out, n_pur = via.audio(emu, eng, pairs, 1, out_cap=n_out, purges_cap=n_pur)
+    rc, out, pur, masked, n_out, n_pur = via.audio(emu_lib, eng, pairs, 1, out_cap=n_out, purges_cap=n_pur)
     want = A.run_cpu(oracle_lib, "orc_", pairs, A.DROP_HOLD_WORD, ends, 1)
     assert rc == 0 and out.tobytes() == want[0].tobytes() and pur.tobytes() == want[2].tobytes()
-    assert emu.sdv_set_audio_masking(eng, 7) == -1
-    emu.sdv_engine_destroy(eng)
+    assert emu_lib.sdv_set_audio_masking(eng, 7) == -1
+    emu_lib.sdv_engine_destroy(eng)
 
 
-def test_emu_edge_inputs(emu, oracle_lib):
-    _edge_inputs(emu, dc.HOST, oracle_lib)
+def test_emu_edge_inputs(emu_lib, oracle_lib):
+    _edge_inputs(emu_lib, dc.HOST, oracle_lib)
 
 
-def _in_place_and_staged_paths_agree(emu, via, oracle_lib):
+def _in_place_and_staged_paths_agree(emu_lib, via, oracle_lib):
     """With room for the whole burst the pairs are worked on in place in the caller's buffer; with exactly the room the output needs they go through
     a buffer of the engine.  Same result, burst by burst."""
     for name in ("short_runs_lin", "window_edges", "bursts_long_runs", "worn_tape", "no_first_tag"):
         pairs, mode, ends, stop, want, idx, want_pur, want_masked, hit = _oracle(name)
-        eng = emu.sdv_engine_create(0)
-        emu.sdv_set_audio_masking(eng, mode)
+        eng = emu_lib.sdv_engine_create(0)
+        emu_lib.sdv_set_audio_masking(eng, mode)
         outs, a = [], 0
         for k, b in enumerate(ends):
             b = int(b)
             st = 1 if (stop and k + 1 == len(ends)) else 0
-            rc, o, _, _, n_out, n_pur = via.audio(emu, eng, pairs[a:b], st, out_cap=0)          # refused: tells the size, takes nothing
+            rc, o, _, _, n_out, n_pur = via.audio(emu_lib, eng, pairs[a:b], st, out_cap=0)          # refused: tells the size, takes nothing
             if rc == 0:                 # ... unless the burst puts nothing out
                 assert n_out == 0
             else:
                 assert rc == -1 and n_out > 0
-                rc, o, p, m, n_out2, _ = via.audio(emu, eng, pairs[a:b], st, out_cap=n_out, purges_cap=max(n_pur, 1))
+                rc, o, p, m, n_out2, _ = via.audio(emu_lib, eng, pairs[a:b], st, out_cap=n_out, purges_cap=max(n_pur, 1))
                 assert rc == 0 and n_out2 == n_out
             outs.append(o.copy()); a = b
-        emu.sdv_engine_destroy(eng)
+        emu_lib.sdv_engine_destroy(eng)
         out = np.concatenate(outs)
         assert out.tobytes() == want.tobytes(), name + ": " + _diff(out, want)
 
 
-def test_emu_in_place_and_staged_paths_agree(emu, oracle_lib):
-    _in_place_and_staged_paths_agree(emu, dc.HOST, oracle_lib)
+def test_emu_in_place_and_staged_paths_agree(emu_lib, oracle_lib):
+    _in_place_and_staged_paths_agree(emu_lib, dc.HOST, oracle_lib)
 
 
-def test_emu_random_tapes(emu, oracle_lib):
+def test_emu_random_tapes(emu_lib, oracle_lib):
     """Differential fuzz (tools/audio_fuzz.py): 60 random tapes - files of random length, dropout runs of random place / length / channel, random
     invalid words and blocks, tags in random order, random bursts, every masking mode - the kernels against the oracle.  (The same generator
     ran 150 tapes through the real AudioProcessor against the oracle, and 400 through the emulator, when this was written.)"""
@@ -246,53 +239,53 @@ def test_emu_random_tapes(emu, oracle_lib):
     spec = importlib.util.spec_from_file_location("audio_fuzz", os.path.join(os.path.dirname(GOLD), "..", "tools", "audio_fuzz.py"))
     fz = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(fz)
-    res = [fz.check(emu, oracle_lib, seed) for seed in range(5000, 5060)]
+    res = [fz.check(emu_lib, oracle_lib, seed) for seed in range(5000, 5060)]
     assert res.count("ok") >= 55
 
 
-def _next_index_runs_on_across_calls(emu, via, oracle_lib):
+def _next_index_runs_on_across_calls(emu_lib, via, oracle_lib):
     """sdv_audio_next_index before a call = PCMSample::index of the first pair that call puts out (the reference's own index, from the oracle run)."""
     for name in ("bursts_long_runs", "bursts_two_files", "bursts_small"):
         pairs, mode, ends, stop, want, idx, want_pur, want_masked, hit = _oracle(name)
-        eng = emu.sdv_engine_create(0)
-        emu.sdv_set_audio_masking(eng, mode)
+        eng = emu_lib.sdv_engine_create(0)
+        emu_lib.sdv_set_audio_masking(eng, mode)
         a = got = 0
         for k, b in enumerate(ends):
             b = int(b)
-            before = emu.sdv_audio_next_index(eng)
-            rc, o, p, m, _, _ = via.audio(emu, eng, pairs[a:b], 1 if (stop and k + 1 == len(ends)) else 0)
+            before = emu_lib.sdv_audio_next_index(eng)
+            rc, o, p, m, _, _ = via.audio(emu_lib, eng, pairs[a:b], 1 if (stop and k + 1 == len(ends)) else 0)
             assert rc == 0
             if len(o) and (len(p) == 0 or p[0]["first_pair"] > 0):
                 assert before == idx[got], (name, k)
             got += len(o); a = b
-        emu.sdv_engine_destroy(eng)
+        emu_lib.sdv_engine_destroy(eng)
 
 
-def test_emu_next_index_runs_on_across_calls(emu, oracle_lib):
-    _next_index_runs_on_across_calls(emu, dc.HOST, oracle_lib)
+def test_emu_next_index_runs_on_across_calls(emu_lib, oracle_lib):
+    _next_index_runs_on_across_calls(emu_lib, dc.HOST, oracle_lib)
 
 
-def _call_in_place(emu, via, oracle_lib):
+def _call_in_place(emu_lib, via, oracle_lib):
     """out_pairs == pairs: the output overwrites the input."""
     for name in ("short_runs_lin", "two_files", "worn_tape"):
         pairs, mode, ends, stop, want, idx, want_pur, want_masked, hit = _oracle(name)
-        eng = emu.sdv_engine_create(0)
-        emu.sdv_set_audio_masking(eng, mode)
+        eng = emu_lib.sdv_engine_create(0)
+        emu_lib.sdv_set_audio_masking(eng, mode)
         buf = via.array(np.concatenate([pairs, np.zeros(1024, dtype=PAIR_DTYPE)]))
         pur = via.zeros(16, A.PURGE_DTYPE)
         n_out, n_pur, nm = C.c_size_t(0), C.c_size_t(0), C.c_uint64(0)
         at = via.ptr(buf)           # input and output: the room behind the input lies in the same allocation
-        rc = emu.sdv_audio_process(eng, at, len(pairs), 1, at, len(buf), C.byref(n_out), via.ptr(pur), 16, C.byref(n_pur), C.byref(nm), via.stream())
-        emu.sdv_engine_destroy(eng)
+        rc = emu_lib.sdv_audio_process(eng, at, len(pairs), 1, at, len(buf), C.byref(n_out), via.ptr(pur), 16, C.byref(n_pur), C.byref(nm), via.stream())
+        emu_lib.sdv_engine_destroy(eng)
         via.check(pur)
         assert rc == 0 and via.get(buf, n_out.value).tobytes() == want.tobytes() and nm.value == want_masked, name
 
 
-def test_emu_call_in_place(emu, oracle_lib):
-    _call_in_place(emu, dc.HOST, oracle_lib)
+def test_emu_call_in_place(emu_lib, oracle_lib):
+    _call_in_place(emu_lib, dc.HOST, oracle_lib)
 
 
-def _many_files_in_one_call(emu, via, oracle_lib):
+def _many_files_in_one_call(emu_lib, via, oracle_lib):
     """The stretches between tags are independent: 40 short files in one burst, one wave each."""
     rng = np.random.default_rng(5)
     parts = []
@@ -304,27 +297,27 @@ def _many_files_in_one_call(emu, via, oracle_lib):
     ends = np.array([len(pairs)], dtype=np.uint64)
     want = A.run_cpu(oracle_lib, "orc_", pairs, A.DROP_INTER_LIN_WORD, ends, 1)
     assert want[4] == 0
-    out, pur, masked = via.run(emu, pairs, A.DROP_INTER_LIN_WORD, ends, 1)
+    out, pur, masked = via.run(emu_lib, pairs, A.DROP_INTER_LIN_WORD, ends, 1)
     assert out.tobytes() == want[0].tobytes(), _diff(out, want[0])
     assert pur.tobytes() == want[2].tobytes() and masked == want[3]
 
 
-def test_emu_many_files_in_one_call(emu, oracle_lib):
-    _many_files_in_one_call(emu, dc.HOST, oracle_lib)
+def test_emu_many_files_in_one_call(emu_lib, oracle_lib):
+    _many_files_in_one_call(emu_lib, dc.HOST, oracle_lib)
 
 
-def _wav_pack_and_header(emu, via, oracle_lib):
+def _wav_pack_and_header(emu_lib, via, oracle_lib):
     pairs, mode, ends, stop, out, idx, pur, masked, hit = _oracle("two_files")
-    eng = emu.sdv_engine_create(0)
+    eng = emu_lib.sdv_engine_create(0)
     pcm, src = via.zeros(2 * len(out), np.dtype("<i2")), via.array(out)
-    assert emu.sdv_wav_pack(eng, via.ptr(src), len(out), via.ptr(pcm), via.stream()) == 0
+    assert emu_lib.sdv_wav_pack(eng, via.ptr(src), len(out), via.ptr(pcm), via.stream()) == 0
     assert np.array_equal(via.get(pcm).reshape(-1, 2), out["audio_word"])
-    emu.sdv_engine_destroy(eng)
-    assert dict(A.wav_files(emu, "sdv_", out, pur)) == dict(A.wav_files(oracle_lib, "orc_", out, pur))
+    emu_lib.sdv_engine_destroy(eng)
+    assert dict(A.wav_files(emu_lib, "sdv_", out, pur)) == dict(A.wav_files(oracle_lib, "orc_", out, pur))
 
 
-def test_emu_wav_pack_and_header(emu, oracle_lib):
-    _wav_pack_and_header(emu, dc.HOST, oracle_lib)
+def test_emu_wav_pack_and_header(emu_lib, oracle_lib):
+    _wav_pack_and_header(emu_lib, dc.HOST, oracle_lib)
 
 
 # ---- the product on the GPU ------------------------------------------------------------------------------------------

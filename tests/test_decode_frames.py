@@ -16,18 +16,9 @@ import pcm16_api as p16
 import stitch_api as sa
 from emu_engine_adapter import EmuEngine
 from stitch_api import PAIR_DTYPE
+from sdvpcmdecoder_amd.abi import PCM_PCM1 as PCM1, PCM_PCM16X0 as PCM16X0, PCM_STC007 as STC007
 
-PCM1, PCM16X0, STC007 = 0, 1, 2
 FRASM = {STC007: sa.FRASM_DTYPE, PCM1: p1.FRASM1_DTYPE, PCM16X0: p16.FRASM16_DTYPE}
-
-
-def _bind(lib):
-    lib.sdv_decode_frames.restype = C.c_int
-    lib.sdv_decode_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint,
-                                      C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t,
-                                      C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.c_void_p]
-    lib.sdv_set_pcm_type.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    return lib
 
 
 def _tape(fmt, n):
@@ -72,7 +63,7 @@ def _fused_host(lib, h, fmt, luma, with_audio, stop=1, give_stats=True, first_fr
 
 @pytest.mark.parametrize("fmt", [STC007, PCM1, PCM16X0])
 def test_emu_fused_equals_separate_calls(fmt, emu_lib, oracle_lib):
-    lib = A.bind_product(_bind(ea.bind(emu_lib)))
+    lib = emu_lib
     luma = _tape(fmt, 3)
     a = EmuEngine(lib)
     lib.sdv_set_pcm_type(a.h, fmt, 0)
@@ -100,7 +91,7 @@ def test_emu_fused_equals_separate_calls(fmt, emu_lib, oracle_lib):
 def test_emu_fused_stream_in_calls_equals_one_call(clean, emu_lib, oracle_lib):
     """A source decoded a few frames per call (NEW_FILE with the first, END_FILE with the last): the calls in between hand records of known
     layout to the stitch stage, which then neither looks for the frame ends nor waits for its analysis (sdv_stitch_info.pipelined)."""
-    lib = A.bind_product(_bind(ea.bind(emu_lib)))
+    lib = emu_lib
     luma = _tape(STC007, 12)
     if clean:       # every call settles in one round: the next call's state and the waiting frame are copied ahead of the read-back
         from sdvpcmdecoder_amd import synth
@@ -134,7 +125,7 @@ def test_emu_fused_direct_frames_decoded_again_with_records(emu_lib, oracle_lib,
     """The way back of the frames that went straight into the field buffers: should the stitch call not take the path they were written for, the
     binarize stage runs again from the stream state it started with and leaves records (forced here by a switch of the developer builds)."""
     from sdvpcmdecoder_amd import synth
-    lib = A.bind_product(_bind(ea.bind(emu_lib)))
+    lib = emu_lib
     luma = synth.stc007_frames(12, seed=12, noise_sigma=4.0)[0].copy()
     a = EmuEngine(lib)
     lib.sdv_set_pcm_type(a.h, STC007, 0)
@@ -170,7 +161,7 @@ def _fused_refuses_bad_arguments(lib, via):
 
 
 def test_emu_fused_refuses_bad_arguments(emu_lib):
-    _fused_refuses_bad_arguments(A.bind_product(_bind(ea.bind(emu_lib))), dc.HOST)
+    _fused_refuses_bad_arguments(emu_lib, dc.HOST)
 
 
 # ---- the product on the GPU ------------------------------------------------------------------------------------------
@@ -271,7 +262,7 @@ def _oracle_chain(oracle_lib, luma):
 def test_emu_fused_uneven_calls_equal_the_sequential_oracle(emu_lib, oracle_lib):
     """A damaged tape through sdv_decode_frames in calls of 1, 3, 2 and 1 frames (emulator): pair stream, frame descriptors and frame statistics equal
     what the oracle's two workers make of the whole tape one line after the other."""
-    lib = A.bind_product(_bind(ea.bind(emu_lib)))
+    lib = emu_lib
     from sdvpcmdecoder_amd import synth
     from test_gpu_parity import _unreadable_cells
     luma = synth.stc007_frames(7, seed=93, noise_sigma=4.0, height=120, lines_per_field=60)[0].copy()
@@ -396,7 +387,7 @@ def test_emu_fused_direct_frames_other_geometries(geometry, emu_lib, oracle_lib)
     """Frames without records (the frame kernel writes the stitch stage's field buffers itself) with fields of unequal length - a frame of 485 rows: 243 + 242
     lines - with the 288 lines per field of a PAL frame (five chunks of 64 lines), with fields that fill a field buffer to its last line and with fields one line
     longer than that (no frame of those may go without records): calls of two frames against one call over the whole tape."""
-    lib = A.bind_product(_bind(ea.bind(emu_lib)))
+    lib = emu_lib
     luma = _geometry_tape(geometry, 10)
     a = EmuEngine(lib)
     lib.sdv_set_pcm_type(a.h, STC007, 0)
@@ -495,7 +486,7 @@ def _tape_clean_then_damaged(n=15, bad_from=9):
 def test_emu_fused_stitch_queued_ahead_is_made_over_when_the_frame_stage_needs_more_rounds(emu_lib, oracle_lib):
     """Calls of three frames: while the tape plays the stitch kernels of a call are queued behind the frame kernel's first round (pipelined & 4); the call
     that meets the damage had them queued too - its frame stage then took more rounds and the stitch stage was run again on the final records (& 8)."""
-    lib = A.bind_product(_bind(ea.bind(emu_lib)))
+    lib = emu_lib
     luma = _tape_clean_then_damaged()
     a = EmuEngine(lib)
     lib.sdv_set_pcm_type(a.h, STC007, 0)
@@ -543,8 +534,6 @@ def _stitch_and_fused_calls_interleaved_with_the_visualiser_feeds_toggled(lib, v
     depend on which way a call took.  The whole equals the sequential oracle; the emulator build also checks the state that was copied ahead against
     the last turn's (SDV_DEV_AIDS, stitch_engine.inc)."""
     from sdvpcmdecoder_amd import synth
-    lib.sdv_set_stitch_block_output.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.sdv_set_stitch_line_output.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     n = 14
     luma = np.ascontiguousarray(synth.stc007_frames(n, seed=97, noise_sigma=3.0, height=120, lines_per_field=60)[0])
     want_p, want_f, _ = _oracle_chain(oracle_lib, luma)
@@ -585,7 +574,7 @@ def _stitch_and_fused_calls_interleaved_with_the_visualiser_feeds_toggled(lib, v
 
 
 def test_emu_stitch_and_fused_calls_interleaved_with_the_visualiser_feeds_toggled(emu_lib, oracle_lib):
-    _stitch_and_fused_calls_interleaved_with_the_visualiser_feeds_toggled(A.bind_product(_bind(ea.bind(emu_lib))), dc.HOST, oracle_lib)
+    _stitch_and_fused_calls_interleaved_with_the_visualiser_feeds_toggled(emu_lib, dc.HOST, oracle_lib)
 
 
 # ---- the GPU twins of the emulator's call-by-call tests: the same bodies through tests/device_calls.py ----------------------------------------------

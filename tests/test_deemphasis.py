@@ -9,21 +9,18 @@ one: every sample within 1 LSB, at most 2 samples per case (cases hold at most 2
 float differs in about one sample per thousand - hundreds at that size, several in the smallest noise case here - and fails
 (test_the_condition_tells_float_from_double).  Every field but audio_word is compared bytewise."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import audio_api as A
+from sdvpcmdecoder_amd import abi
 from stitch_api import PAIR_DTYPE
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = open(os.path.join(ROOT, "include", "sdvpcm.h")).read()
-T = int(re.search(r"#define SDV_DEEMPH_TILE (\d+)", HDR).group(1))           # pairs per tile of the device's work
-WARM = int(re.search(r"#define SDV_DEEMPH_WARMUP (\d+)", HDR).group(1))      # pairs in front of a tile its state comes from
-OFF, AUTO, FORCE = 0, 1, 2
-BAD_ARG, NULL_LINES, NULL_BLOCK = -1, 16, 17
+T = abi.DEEMPH_TILE          # pairs per tile of the device's work
+WARM = abi.DEEMPH_WARMUP     # pairs in front of a tile its state comes from
+OFF, AUTO, FORCE = abi.DEEMPH_OFF, abi.DEEMPH_AUTO, abi.DEEMPH_FORCE
+BAD_ARG, NULL_LINES, NULL_BLOCK = abi.ERR_BAD_ARG, abi.ERR_NULL_LINES, abi.ERR_NULL_BLOCK
 T1, T2 = 50e-6, 15e-6
 
 
@@ -133,22 +130,10 @@ def wanted(key, pairs, mode):
 
 
 # ---- the two ways to the code under test ---------------------------------------------------------------------------------------
-def bind(lib):
-    lib.sdv_deemphasis_coeffs.argtypes = [C.c_uint16, C.POINTER(C.c_double)]
-    lib.sdv_deemphasis_coeffs.restype = None
-    lib.sdv_set_deemphasis.argtypes = [C.c_void_p, C.c_int]
-    lib.sdv_reset_deemphasis.argtypes = [C.c_void_p]
-    lib.sdv_audio_deemphasis.restype = C.c_int
-    lib.sdv_audio_deemphasis.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    lib.sdv_engine_create.restype = C.c_void_p
-    lib.sdv_engine_destroy.argtypes = [C.c_void_p]
-    return lib
-
-
 class Emu:
     """The emulator build: host memory."""
     def __init__(self, lib):
-        self.lib = bind(lib)
+        self.lib = lib
         self.h = C.c_void_p(self.lib.sdv_engine_create(0))
 
     def close(self):
@@ -178,7 +163,7 @@ class Gpu:
     def __init__(self):
         from sdvpcmdecoder_amd import Engine
         self.eng = Engine(0)
-        self.lib, self.h = bind(self.eng.lib), self.eng._h
+        self.lib, self.h = self.eng.lib, self.eng._h
 
     def close(self):
         self.eng.close()
@@ -314,7 +299,7 @@ def _reset(be):
 # ---- CPU: the coefficients of the product library, the definition itself, the emulator ---------------------------------------------
 def test_coefficients_of_the_product_library():
     from sdvpcmdecoder_amd import build as b
-    lib = bind(C.CDLL(b.build_hip()))
+    lib = abi.bind(C.CDLL(b.build_hip()))
     got = {}
     for rate in (44056, 44100, 48000, 0, 32000):
         c = (C.c_double * 3)()

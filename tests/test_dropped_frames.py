@@ -94,8 +94,6 @@ def test_oracle_matches_live_reference(name, oracle_lib):
 
 def _engine_run(lib, eng, name, device=False):
     fmt, luma, mode, mask, fl = make_case(name)
-    lib.sdv_set_frame_flags.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.sdv_set_mode.argtypes = [C.c_void_p, C.c_int]
     lib.sdv_set_mode(eng, mode)
     assert lib.sdv_set_frame_flags(eng, mask.ctypes.data, len(mask)) == 0
     if fmt == "stc007":
@@ -110,7 +108,7 @@ def _engine_run(lib, eng, name, device=False):
 
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_emu_matches_oracle(name, emu_lib, oracle_lib):
-    lib = ea.bind(emu_lib)
+    lib = emu_lib
     eng = C.c_void_p(lib.sdv_engine_create(0))
     fmt, luma, mode, mask, fl = make_case(name)
     if fmt != "stc007":
@@ -124,7 +122,6 @@ def test_emu_matches_oracle(name, emu_lib, oracle_lib):
 def _marks_are_consumed_by_one_call(lib, via):
     """The marks belong to the next frame call only: the call after it decodes its pixels."""
     eng = C.c_void_p(lib.sdv_engine_create(0))
-    lib.sdv_set_frame_flags.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.sdv_set_mode(eng, 2)
     luma = synth.stc007_frames(n_frames=4, seed=31, height=64, lines_per_field=34, noise_sigma=3.0)[0]
     mask = np.array([0, 1, 0, 0], dtype=np.uint8)
@@ -139,7 +136,7 @@ def _marks_are_consumed_by_one_call(lib, via):
 
 
 def test_emu_marks_are_consumed_by_one_call(emu_lib, oracle_lib):
-    _marks_are_consumed_by_one_call(ea.bind(emu_lib), dc.HOST)
+    _marks_are_consumed_by_one_call(emu_lib, dc.HOST)
 
 
 # ---- the product on the GPU ------------------------------------------------------------------------------------------------------
@@ -192,9 +189,7 @@ def test_emu_double_width_feeds_the_doubled_path(emu_lib, oracle_lib):
     """sdv_double_width: integer pixel replication (NOT libswscale's Gauss filter, which the reference uses and which is outside the
     rebuilt path); what it makes decodes, with SDV_FLAG_DOUBLED, to what the oracle makes of the same doubled pixels - and to the
     generator's words."""
-    lib = ea.bind(emu_lib)
-    lib.sdv_double_width.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.sdv_needs_double_width.argtypes = [C.c_int]
+    lib = emu_lib
     assert lib.sdv_needs_double_width(720) == 1 and lib.sdv_needs_double_width(1440) == 0 and lib.sdv_needs_double_width(8) == 0
     luma, _, _ = synth.stc007_frames(n_frames=3, seed=51, width=717, height=48, noise_sigma=3.0)
     n, h, w = luma.shape

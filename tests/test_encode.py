@@ -419,12 +419,10 @@ def test_gpu_refusals():
 # ---- 7. the library ---------------------------------------------------------------------------------------------------------------------------
 def test_symbols_of_the_product_library():
     from sdvpcmdecoder_amd import build as b
-    lib = C.CDLL(b.build_hip())
+    lib = en.bind(C.CDLL(b.build_hip()))
     assert hasattr(lib, "sdv_encode_geometry") and hasattr(lib, "sdv_encode_frames") and hasattr(lib, "sdv_reset_encoder")
-    lib.sdv_abi_version.restype = C.c_int
     assert lib.sdv_abi_version() >= 9
     # the geometry needs neither an engine nor a device
-    en.bind(lib)
     assert en.geometry(lib, en.desc(en.NTSC, ctrl=1)) == (0, 1470, 246, 720)
     assert en.geometry(lib, en.desc(en.PAL, en.BIT16, width=640)) == (0, 1764, 294, 640)
 

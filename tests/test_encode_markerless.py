@@ -16,8 +16,8 @@ import encode_markerless_api as ml
 import pcm1_api as p1
 import pcm16_api as p16
 from stitch_api import PAIR_DTYPE
+from sdvpcmdecoder_amd.abi import PCM_PCM1 as PCM1_TYPE, PCM_PCM16X0 as PCM16X0_TYPE
 
-PCM1_TYPE, PCM16X0_TYPE = 0, 1
 FORMATS = (ml.PCM1, ml.SI, ml.EI)
 EDGES = (-32768, -8193, -8192, -1, 0, 8191, 8192, 32767)        # either side of the PCM-1 companding ranges, and the ends
 
@@ -489,12 +489,10 @@ def test_gpu_refusals():
 # ---- 7. the library ---------------------------------------------------------------------------------------------------------------------------
 def test_symbols_of_the_product_library():
     from sdvpcmdecoder_amd import build as b
-    lib = C.CDLL(b.build_hip())
+    lib = ml.bind(C.CDLL(b.build_hip()))
     assert hasattr(lib, "sdv_encode_markerless_geometry") and hasattr(lib, "sdv_encode_markerless_frames")
-    lib.sdv_abi_version.restype = C.c_int
     assert lib.sdv_abi_version() >= 10
     # the geometry needs neither an engine nor a device
-    ml.bind(lib)
     assert ml.geometry(lib, ml.desc(ml.PCM1, header=1, height=492)) == (0, 1470, 246, 720)
     assert ml.geometry(lib, ml.desc(ml.EI, ctrl_flags=7, width=640)) == (0, 1470, 245, 640)
 

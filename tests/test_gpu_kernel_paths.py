@@ -20,10 +20,10 @@ from oracle_run import oracle_binarize
 from sdvpcmdecoder_amd import synth
 from test_stc_lines import _oracle_lines, _states_behind
 from pcm1_front_api import STATE_DTYPE
+from sdvpcmdecoder_amd.abi import LF_REF_SWEEPED
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LF_REF_SWEEPED = 1
 
 
 @functools.lru_cache(maxsize=None)

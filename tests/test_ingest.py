@@ -357,13 +357,11 @@ def test_gpu_ingest_runs_on_the_given_stream():
 # ---- 8. the library ---------------------------------------------------------------------------------------------------------------------------
 def test_symbols_of_the_product_library():
     from sdvpcmdecoder_amd import build as b
-    lib = C.CDLL(b.build_hip())
+    lib = ia.bind(C.CDLL(b.build_hip()))
     assert hasattr(lib, "sdv_ingest_geometry") and hasattr(lib, "sdv_ingest_frames")
-    lib.sdv_abi_version.restype = C.c_int
     assert lib.sdv_abi_version() >= 8
     assert C.sizeof(ia.Desc) == 20
     # the geometry needs neither an engine nor a device
-    ia.bind(lib)
     assert ia.geometry(lib, ia.desc(ia.V210, 720, 486, crop=(4, 6, 2, 4), double=ia.AUTO)) == (0, 1420, 480, 1, 1920)
     assert ia.geometry(lib, ia.desc(ia.RGB0, 1920, 1080)) == (0, 1920, 640, 0, 7680)
 

@@ -9,13 +9,13 @@ import numpy as np
 import pytest
 
 import geometry_cases as gc
+from sdvpcmdecoder_amd.abi import LF_CRC_VALID, LF_BY_EXT_TUNE
 
 FMT_NAMES = sorted(gc.FORMATS)
 FRAME_IDS = [gc.shape_id(s) for s in gc.FRAME_SHAPES]
 LINE_IDS = [gc.shape_id(s) for s in gc.LINE_SHAPES]
 FUSED = [gc.STC007, gc.PCM1, gc.PCM16X0]
 FUSED_IDS = ["stc007", "pcm1", "pcm16x0"]
-LF_CRC_VALID, LF_BY_EXT_TUNE = 64, 4
 
 
 def _placed_frames(fmt_name, idx):
@@ -81,11 +81,6 @@ def test_the_frames_of_the_tables_read(fmt_name, oracle_lib):
 
 
 # ---- the kernels on the emulator ---------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def emu(emu_lib):
-    return gc.bind(emu_lib)
-
-
 def _emu_engine(lib, mode):
     eng = C.c_void_p(lib.sdv_engine_create(0))
     gc.emu_configure(lib, eng, mode)
@@ -94,14 +89,14 @@ def _emu_engine(lib, mode):
 
 @pytest.mark.parametrize("idx", range(len(gc.FRAME_SHAPES)), ids=FRAME_IDS)
 @pytest.mark.parametrize("fmt_name", FMT_NAMES)
-def test_emu_frames_in_awkward_buffers(fmt_name, idx, emu, oracle_lib):
+def test_emu_frames_in_awkward_buffers(fmt_name, idx, emu_lib, oracle_lib):
     placed, want, wstats, mode = _placed_frames(fmt_name, idx)
-    eng = _emu_engine(emu, mode)
-    rc, got, stats, nrec = gc.emu_frames(emu, eng, gc.FORMATS[fmt_name], placed)
-    err = emu.sdv_last_error(eng)
+    eng = _emu_engine(emu_lib, mode)
+    rc, got, stats, nrec = gc.emu_frames(emu_lib, eng, gc.FORMATS[fmt_name], placed)
+    err = emu_lib.sdv_last_error(eng)
     info = gc.ea.RunInfo()
-    emu.sdv_get_run_info(eng, C.byref(info))
-    emu.sdv_engine_destroy(eng)
+    emu_lib.sdv_get_run_info(eng, C.byref(info))
+    emu_lib.sdv_engine_destroy(eng)
     assert rc == 0, err
     _check_frames(got, stats, nrec, gc.N_FRAMES, want, wstats)
     if gc.lean_build_alone(gc.FRAME_SHAPES[idx]):
@@ -109,19 +104,19 @@ def test_emu_frames_in_awkward_buffers(fmt_name, idx, emu, oracle_lib):
 
 
 @pytest.mark.parametrize("fmt_name", FMT_NAMES)
-def test_emu_stream_in_awkward_buffers(fmt_name, emu, oracle_lib):
+def test_emu_stream_in_awkward_buffers(fmt_name, emu_lib, oracle_lib):
     """12 damaged frames of 717 x 25 in calls of 1, 7 and 4: the chain state crosses the calls, the repair rounds read the rows again through the same strides."""
     placed, want, wstats, mode = _placed_stream(fmt_name)
     fmt = gc.FORMATS[fmt_name]
-    eng = _emu_engine(emu, mode)
+    eng = _emu_engine(emu_lib, mode)
     got, gst, at = [], [], 0
     for cnt in gc.STREAM_CALLS:
-        rc, recs, stats, nrec = gc.emu_frames(emu, eng, fmt, placed, first_frame=at, n=cnt, first_frame_no=1 + at, new_file=(at == 0))
-        assert rc == 0, emu.sdv_last_error(eng)
+        rc, recs, stats, nrec = gc.emu_frames(emu_lib, eng, fmt, placed, first_frame=at, n=cnt, first_frame_no=1 + at, new_file=(at == 0))
+        assert rc == 0, emu_lib.sdv_last_error(eng)
         assert gc.guards_intact(recs, nrec) and gc.guards_intact(stats, cnt)
         got.append(recs[:nrec]); gst.append(stats[:cnt])
         at += cnt
-    emu.sdv_engine_destroy(eng)
+    emu_lib.sdv_engine_destroy(eng)
     got, gst = np.concatenate(got), np.concatenate(gst)
     assert got.tobytes() == want.tobytes(), gc.first_difference(got, want)
     assert gst.tobytes() == wstats.tobytes(), gc.first_difference(gst, wstats)
@@ -129,49 +124,49 @@ def test_emu_stream_in_awkward_buffers(fmt_name, emu, oracle_lib):
 
 @pytest.mark.parametrize("idx", range(len(gc.LINE_SHAPES)), ids=LINE_IDS)
 @pytest.mark.parametrize("fmt_name", FMT_NAMES)
-def test_emu_lines_in_awkward_buffers(fmt_name, idx, emu, oracle_lib):
+def test_emu_lines_in_awkward_buffers(fmt_name, idx, emu_lib, oracle_lib):
     placed, step, runs, mode = _placed_lines(fmt_name, idx)
     fmt = gc.FORMATS[fmt_name]
     _, n_rows, w = placed.shape
-    eng = _emu_engine(emu, mode)
+    eng = _emu_engine(emu_lib, mode)
     for states, want, wscans in runs:
-        rc, got, scans = gc.emu_lines_raw(emu, eng, fmt, placed.ptr(), step * placed.row_stride, w, n_rows // step, states)
-        assert rc == 0, emu.sdv_last_error(eng)
+        rc, got, scans = gc.emu_lines_raw(emu_lib, eng, fmt, placed.ptr(), step * placed.row_stride, w, n_rows // step, states)
+        assert rc == 0, emu_lib.sdv_last_error(eng)
         _check_lines(got, scans, want, wscans)
-    emu.sdv_engine_destroy(eng)
+    emu_lib.sdv_engine_destroy(eng)
 
 
 @pytest.mark.parametrize("pcm_type", FUSED, ids=FUSED_IDS)
-def test_emu_fused_call_in_an_awkward_buffer(pcm_type, emu, oracle_lib):
+def test_emu_fused_call_in_an_awkward_buffer(pcm_type, emu_lib, oracle_lib):
     want = gc.fused_case(pcm_type)
     placed = gc.place(want[0], gc.FUSED_PAD, gc.FUSED_SHIFT, 0, seed=1090 + pcm_type)
-    eng = _emu_engine(emu, 2)
-    emu.sdv_set_pcm_type(eng, pcm_type, 0)
-    assert emu.sdv_set_pcm1_stitch_settings(eng, C.byref(gc.p1.default_settings())) == 0
-    assert emu.sdv_set_pcm16x0_stitch_settings(eng, C.byref(gc.p16.default_settings())) == 0
-    rc, pairs, n_pairs, frames, n_fr, stats, nst = gc.emu_decode(emu, eng, pcm_type, placed)
-    err = emu.sdv_last_error(eng)
-    emu.sdv_engine_destroy(eng)
+    eng = _emu_engine(emu_lib, 2)
+    emu_lib.sdv_set_pcm_type(eng, pcm_type, 0)
+    assert emu_lib.sdv_set_pcm1_stitch_settings(eng, C.byref(gc.p1.default_settings())) == 0
+    assert emu_lib.sdv_set_pcm16x0_stitch_settings(eng, C.byref(gc.p16.default_settings())) == 0
+    rc, pairs, n_pairs, frames, n_fr, stats, nst = gc.emu_decode(emu_lib, eng, pcm_type, placed)
+    err = emu_lib.sdv_last_error(eng)
+    emu_lib.sdv_engine_destroy(eng)
     assert rc == 0, err
     _check_fused(pairs, n_pairs, frames, n_fr, stats, nst, want)
 
 
-def test_emu_refuses_geometry_it_cannot_take(emu):
+def test_emu_refuses_geometry_it_cannot_take(emu_lib):
     """row_stride < width, a line wider than the staged row, frames that overlap: SDV_ERR_BAD_ARG, and nothing written."""
     h, w = 8, 720
     luma = np.zeros(2 * h * (gc.PX_BYTES + 1) + 64, dtype=np.uint8)
-    eng = _emu_engine(emu, 2)
+    eng = _emu_engine(emu_lib, 2)
     for fmt in gc.FORMATS.values():
         for rs, fs, ww, n in ((w - 1, h * w, w, 1), (gc.PX_BYTES + 1, h * (gc.PX_BYTES + 1), gc.PX_BYTES + 1, 1), (w + 3, (h - 1) * (w + 3) + w - 1, w, 2)):
-            rc, recs, stats, _ = gc.emu_frames_raw(emu, eng, fmt, luma.ctypes.data, rs, fs, ww, h, n)
+            rc, recs, stats, _ = gc.emu_frames_raw(emu_lib, eng, fmt, luma.ctypes.data, rs, fs, ww, h, n)
             assert rc == gc.BAD_ARG and gc.guards_intact(recs, 0) and gc.guards_intact(stats, 0), (fmt.name, rs, fs, ww, n)
         for rs, ww in ((w - 1, w), (gc.PX_BYTES + 1, gc.PX_BYTES + 1)):
-            rc, recs, scans = gc.emu_lines_raw(emu, eng, fmt, luma.ctypes.data, rs, ww, 4, None)
+            rc, recs, scans = gc.emu_lines_raw(emu_lib, eng, fmt, luma.ctypes.data, rs, ww, 4, None)
             assert rc == gc.BAD_ARG and gc.guards_intact(recs, 0) and (scans is None or gc.guards_intact(scans, 0)), (fmt.name, rs, ww)
         # ... and the tightest frame_stride that is legal is taken
-        rc, _, _, _ = gc.emu_frames_raw(emu, eng, fmt, luma.ctypes.data, w + 3, (h - 1) * (w + 3) + w, w, h, 2)
-        assert rc == 0, emu.sdv_last_error(eng)
-    emu.sdv_engine_destroy(eng)
+        rc, _, _, _ = gc.emu_frames_raw(emu_lib, eng, fmt, luma.ctypes.data, w + 3, (h - 1) * (w + 3) + w, w, h, 2)
+        assert rc == 0, emu_lib.sdv_last_error(eng)
+    emu_lib.sdv_engine_destroy(eng)
 
 
 # ---- the product on the GPU, through Engine --------------------------------------------------------------------------------------------------------

@@ -94,114 +94,109 @@ def test_clean_stream_is_a_permutation_of_the_lines(oracle_lib):
 
 # ---- the kernels on the emulator -----------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def emu(emu_lib):
-    return ea.bind(emu_lib)
-
-
-@pytest.fixture(scope="module")
 def gpu():
     return dc.product_lib()
 
 
 @pytest.mark.parametrize("name", list(p1.CASES))
-def test_emu_matches_oracle(name, emu, oracle_lib):
+def test_emu_matches_oracle(name, emu_lib, oracle_lib):
     recs, st, want_p, want_f = _oracle(name)
-    eng = emu.sdv_engine_create(0)
-    rc, pairs, frames = ea.emu_pcm1_stitch(emu, eng, recs, st)
-    emu.sdv_engine_destroy(eng)
+    eng = emu_lib.sdv_engine_create(0)
+    rc, pairs, frames = ea.emu_pcm1_stitch(emu_lib, eng, recs, st)
+    emu_lib.sdv_engine_destroy(eng)
     assert rc == 0
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
 
 
-def _streaming_calls_equal_one_call(emu, via):
+def _streaming_calls_equal_one_call(emu_lib, via):
     """The stream may arrive in arbitrary pieces: records wait in the engine for their END_FRAME."""
     recs, st, want_p, want_f = _oracle("file_marks")
-    eng = emu.sdv_engine_create(0)
+    eng = emu_lib.sdv_engine_create(0)
     cuts = [0, 1, 2, 300, 496, 497, 1200, 1201, 2000, len(recs) - 1, len(recs)]
     got_p, got_f = [], []
     for a, b in zip(cuts[:-1], cuts[1:]):
-        rc, p, f = via.pcm1_stitch(emu, eng, recs[a:b], st if a == 0 else None, pair_cap=8000, frame_cap=16)
+        rc, p, f = via.pcm1_stitch(emu_lib, eng, recs[a:b], st if a == 0 else None, pair_cap=8000, frame_cap=16)
         assert rc == 0
         got_p.append(p.copy())
         got_f.append(f.copy())
-    emu.sdv_engine_destroy(eng)
+    emu_lib.sdv_engine_destroy(eng)
     pairs, frames = np.concatenate(got_p), np.concatenate(got_f)
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
 
 
-def test_emu_streaming_calls_equal_one_call(emu, oracle_lib):
-    _streaming_calls_equal_one_call(emu, dc.HOST)
+def test_emu_streaming_calls_equal_one_call(emu_lib, oracle_lib):
+    _streaming_calls_equal_one_call(emu_lib, dc.HOST)
 
 
-def _edge_inputs(emu, via, oracle_lib):
-    eng = emu.sdv_engine_create(0)
-    rc, p, f = via.pcm1_stitch(emu, eng, np.zeros(0, dtype=p1.LINE1_DTYPE))            # empty
+def _edge_inputs(emu_lib, via, oracle_lib):
+    eng = emu_lib.sdv_engine_create(0)
+    rc, p, f = via.pcm1_stitch(emu_lib, eng, np.zeros(0, dtype=p1.LINE1_DTYPE))            # empty
     assert rc == 0 and len(p) == 0 and len(f) == 0
     recs, st = p1.make_input("clean")
     end = int(np.nonzero(recs["service_type"] == p1.SRV_END_FRAME)[0][0])
-    rc, p, f = via.pcm1_stitch(emu, eng, recs[:end])                                  # a frame without its END_FRAME: nothing yet
+    rc, p, f = via.pcm1_stitch(emu_lib, eng, recs[:end])                                  # a frame without its END_FRAME: nothing yet
     assert rc == 0 and len(p) == 0 and len(f) == 0
-    rc, p, f = via.pcm1_stitch(emu, eng, recs[end:end + 1])                           # ... now it completes
+    rc, p, f = via.pcm1_stitch(emu_lib, eng, recs[end:end + 1])                           # ... now it completes
     want_p, want_f = p1.run_cpu(oracle_lib, "orc_", recs[:end + 1], st)
     assert rc == 0 and _same(p, f, want_p, want_f)
     lone = recs[end:end + 1].copy()                                                      # a lone END_FRAME: an all-padding frame
     lone["frame_number"] = 9
-    rc, p, f = via.pcm1_stitch(emu, eng, lone)
+    rc, p, f = via.pcm1_stitch(emu_lib, eng, lone)
     want_p, want_f = p1.run_cpu(oracle_lib, "orc_", lone, st)
     assert rc == 0 and len(p) == 1470 and _same(p, f, want_p, want_f)
-    rc, p, f = via.pcm1_stitch(emu, eng, recs, pair_cap=100, frame_cap=8)             # output buffer too small: reported, sized
-    assert rc != 0 and b"too small" in emu.sdv_last_error(eng)
-    emu.sdv_engine_destroy(eng)
+    rc, p, f = via.pcm1_stitch(emu_lib, eng, recs, pair_cap=100, frame_cap=8)             # output buffer too small: reported, sized
+    assert rc != 0 and b"too small" in emu_lib.sdv_last_error(eng)
+    emu_lib.sdv_engine_destroy(eng)
 
 
-def test_emu_edge_inputs(emu, oracle_lib):
-    _edge_inputs(emu, dc.HOST, oracle_lib)
+def test_emu_edge_inputs(emu_lib, oracle_lib):
+    _edge_inputs(emu_lib, dc.HOST, oracle_lib)
 
 
-def _failed_call_leaves_the_stream_untouched(emu, via):
+def _failed_call_leaves_the_stream_untouched(emu_lib, via):
     """A call that is refused (buffers too small) takes nothing: lines that waited for their END_FRAME still wait and the same
     lines can be handed over again."""
     recs, st, want_p, want_f = _oracle("file_marks")
-    eng = emu.sdv_engine_create(0)
+    eng = emu_lib.sdv_engine_create(0)
     cut = 700                                                                            # inside the second frame
-    rc, p0, f0 = via.pcm1_stitch(emu, eng, recs[:cut], st, pair_cap=8000, frame_cap=16)
+    rc, p0, f0 = via.pcm1_stitch(emu_lib, eng, recs[:cut], st, pair_cap=8000, frame_cap=16)
     assert rc == 0 and len(f0) >= 1
-    rc, p, f = via.pcm1_stitch(emu, eng, recs[cut:], None, pair_cap=100, frame_cap=16)
-    assert rc != 0 and b"too small" in emu.sdv_last_error(eng)
-    rc, p1_, f1 = via.pcm1_stitch(emu, eng, recs[cut:], None, pair_cap=8000, frame_cap=16)   # the same lines again
+    rc, p, f = via.pcm1_stitch(emu_lib, eng, recs[cut:], None, pair_cap=100, frame_cap=16)
+    assert rc != 0 and b"too small" in emu_lib.sdv_last_error(eng)
+    rc, p1_, f1 = via.pcm1_stitch(emu_lib, eng, recs[cut:], None, pair_cap=8000, frame_cap=16)   # the same lines again
     assert rc == 0
-    emu.sdv_engine_destroy(eng)
+    emu_lib.sdv_engine_destroy(eng)
     pairs, frames = np.concatenate([p0, p1_]), np.concatenate([f0, f1])
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
 
 
-def test_emu_failed_call_leaves_the_stream_untouched(emu, oracle_lib):
-    _failed_call_leaves_the_stream_untouched(emu, dc.HOST)
+def test_emu_failed_call_leaves_the_stream_untouched(emu_lib, oracle_lib):
+    _failed_call_leaves_the_stream_untouched(emu_lib, dc.HOST)
 
 
-def _field_buffers_outlive_calls(name, emu, via):
+def _field_buffers_outlive_calls(name, emu_lib, via):
     """Manual line offsets over damaged fields, the stream cut into calls at every frame end and in the middle of frames: the lines earlier
     frames left in the field buffers are found whether those frames came with this call or with one before."""
     recs, st, want_p, want_f = _oracle(name)
     ends = np.nonzero(recs["service_type"] == p1.SRV_END_FRAME)[0]
     cuts = sorted(set([0, int(ends[0]) + 1, int(ends[1]) + 200, int(ends[3]) + 1, len(recs)]))
-    eng = emu.sdv_engine_create(0)
+    eng = emu_lib.sdv_engine_create(0)
     pairs, frames = [], []
     for a, b in zip(cuts[:-1], cuts[1:]):
-        rc, p, f = via.pcm1_stitch(emu, eng, recs[a:b], st if a == 0 else None, pair_cap=20000, frame_cap=32)
-        assert rc == 0, emu.sdv_last_error(eng)
+        rc, p, f = via.pcm1_stitch(emu_lib, eng, recs[a:b], st if a == 0 else None, pair_cap=20000, frame_cap=32)
+        assert rc == 0, emu_lib.sdv_last_error(eng)
         pairs.append(p); frames.append(f)
-    emu.sdv_engine_destroy(eng)
+    emu_lib.sdv_engine_destroy(eng)
     pairs, frames = np.concatenate(pairs), np.concatenate(frames)
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
 
 
 @pytest.mark.parametrize("name", ["manual_lost_many", "manual_lost_file_marks"])
-def test_emu_field_buffers_outlive_calls(name, emu):
-    _field_buffers_outlive_calls(name, emu, dc.HOST)
+def test_emu_field_buffers_outlive_calls(name, emu_lib):
+    _field_buffers_outlive_calls(name, emu_lib, dc.HOST)
 
 
-def test_emu_refuses_what_the_reference_never_finishes(emu):
+def test_emu_refuses_what_the_reference_never_finishes(emu_lib):
     """A line of a later frame queued ahead of an END_FRAME: the reference pops its queue up to that line (pcm1datastitcher.cpp:1634-1660),
     finds the same END_FRAME again and assembles what is left of the frame without end (shown on the real reference: more frame reports
     than the stream has frames, until the driver's buffers are full).  The product refuses the stream."""
@@ -211,10 +206,10 @@ def test_emu_refuses_what_the_reference_never_finishes(emu):
     if libs.ref_available():
         pairs, n_frames = p1.run_cpu(libs.load_ref(), "ref_", recs, st, overflow_ok=True)
         assert pairs is None and n_frames > 3
-    eng = emu.sdv_engine_create(0)
-    rc, p, f = ea.emu_pcm1_stitch(emu, eng, recs, st)
-    assert rc != 0 and b"later frame" in emu.sdv_last_error(eng)
-    emu.sdv_engine_destroy(eng)
+    eng = emu_lib.sdv_engine_create(0)
+    rc, p, f = ea.emu_pcm1_stitch(emu_lib, eng, recs, st)
+    assert rc != 0 and b"later frame" in emu_lib.sdv_last_error(eng)
+    emu_lib.sdv_engine_destroy(eng)
 
 
 # ---- the product on the GPU ------------------------------------------------------------------------------------------

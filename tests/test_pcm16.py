@@ -2,7 +2,6 @@
   oracle (oracle/pcm16.c)  vs  golden fixtures of the real reference and - when the reference build is loadable - the real
                                PCM16X0Deinterleaver / PCM16X0DataStitcher run live on every scenario;
   HIP kernel source        vs  the oracle, on the SIMT emulator (CPU) and through the C-ABI on the GPU (-m gpu)."""
-import ctypes as C
 import hashlib
 import os
 
@@ -115,102 +114,95 @@ import engine_api as ea  # noqa: E402
 
 
 @pytest.fixture(scope="module")
-def emu(emu_lib):
-    return ea.bind(emu_lib)
-
-
-@pytest.fixture(scope="module")
 def gpu():
     return dc.product_lib()
 
 
 # (the 372-frame tape takes the emulator most of a minute: it is left to the GPU test and to the comparison of the oracle with the real reference)
 @pytest.mark.parametrize("name", [n for n in p16.CASES if n != "ei_lost_every_field"])
-def test_emu_matches_oracle(name, emu, oracle_lib):
+def test_emu_matches_oracle(name, emu_lib, oracle_lib):
     recs, st, want_p, want_f = _oracle(name)
-    eng = emu.sdv_engine_create(0)
-    rc, pairs, frames = ea.emu_pcm16_stitch(emu, eng, recs, st)
-    emu.sdv_engine_destroy(eng)
+    eng = emu_lib.sdv_engine_create(0)
+    rc, pairs, frames = ea.emu_pcm16_stitch(emu_lib, eng, recs, st)
+    emu_lib.sdv_engine_destroy(eng)
     assert rc == 0
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
 
 
-def _streaming_calls_equal_one_call(name, emu, via):
+def _streaming_calls_equal_one_call(name, emu_lib, via):
     """The stream may arrive in arbitrary pieces: sub-lines wait in the engine for their END_FRAME, the padding and Control Bit
     histories carry over from call to call."""
     recs, st, want_p, want_f = _oracle(name)
-    eng = emu.sdv_engine_create(0)
+    eng = emu_lib.sdv_engine_create(0)
     cuts = [0, 1, 2, 700, 1473, 1474, 3000, 3001, 6000, len(recs) - 1, len(recs)]
     got_p, got_f = [], []
     for a, b in zip(cuts[:-1], cuts[1:]):
-        rc, p, f = via.pcm16_stitch(emu, eng, recs[a:b], st if a == 0 else None, pair_cap=9000, frame_cap=16)
+        rc, p, f = via.pcm16_stitch(emu_lib, eng, recs[a:b], st if a == 0 else None, pair_cap=9000, frame_cap=16)
         assert rc == 0
         got_p.append(p.copy())
         got_f.append(f.copy())
-    emu.sdv_engine_destroy(eng)
+    emu_lib.sdv_engine_destroy(eng)
     pairs, frames = np.concatenate(got_p), np.concatenate(got_f)
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
 
 
 @pytest.mark.parametrize("name", ["si_file_marks", "ei_wander"])
-def test_emu_streaming_calls_equal_one_call(name, emu, oracle_lib):
-    _streaming_calls_equal_one_call(name, emu, dc.HOST)
+def test_emu_streaming_calls_equal_one_call(name, emu_lib, oracle_lib):
+    _streaming_calls_equal_one_call(name, emu_lib, dc.HOST)
 
 
-def _edge_inputs(emu, via, oracle_lib):
-    eng = emu.sdv_engine_create(0)
-    rc, p, f = via.pcm16_stitch(emu, eng, np.zeros(0, dtype=p16.SUB_DTYPE))            # empty
+def _edge_inputs(emu_lib, via, oracle_lib):
+    eng = emu_lib.sdv_engine_create(0)
+    rc, p, f = via.pcm16_stitch(emu_lib, eng, np.zeros(0, dtype=p16.SUB_DTYPE))            # empty
     assert rc == 0 and len(p) == 0 and len(f) == 0
     recs, st = p16.make_input("si_clean")
     end = int(np.nonzero(recs["service_type"] == p16.SRV_END_FRAME)[0][0])
-    rc, p, f = via.pcm16_stitch(emu, eng, recs[:end], st)                             # a frame without its END_FRAME: nothing yet
+    rc, p, f = via.pcm16_stitch(emu_lib, eng, recs[:end], st)                             # a frame without its END_FRAME: nothing yet
     assert rc == 0 and len(p) == 0 and len(f) == 0
-    rc, p, f = via.pcm16_stitch(emu, eng, recs[end:end + 1])                          # ... now it completes
+    rc, p, f = via.pcm16_stitch(emu_lib, eng, recs[end:end + 1])                          # ... now it completes
     want_p, want_f = p16.run_cpu(oracle_lib, "orc_", recs[:end + 1], st)
     assert rc == 0 and _same(p, f, want_p, want_f)
-    emu.sdv_engine_destroy(eng)
-    eng = emu.sdv_engine_create(0)
+    emu_lib.sdv_engine_destroy(eng)
+    eng = emu_lib.sdv_engine_create(0)
     lone = recs[end:end + 1].copy()                                                      # a lone END_FRAME: an all-padding frame
     lone["frame_number"] = 9
-    rc, p, f = via.pcm16_stitch(emu, eng, lone, st)
+    rc, p, f = via.pcm16_stitch(emu_lib, eng, lone, st)
     want_p, want_f = p16.run_cpu(oracle_lib, "orc_", lone, st)
     assert rc == 0 and len(p) == 1470 and _same(p, f, want_p, want_f)
-    rc, p, f = via.pcm16_stitch(emu, eng, recs, pair_cap=100, frame_cap=8)            # output buffer too small: reported, sized
-    assert rc != 0 and b"too small" in emu.sdv_last_error(eng)
-    emu.sdv_engine_destroy(eng)
+    rc, p, f = via.pcm16_stitch(emu_lib, eng, recs, pair_cap=100, frame_cap=8)            # output buffer too small: reported, sized
+    assert rc != 0 and b"too small" in emu_lib.sdv_last_error(eng)
+    emu_lib.sdv_engine_destroy(eng)
 
 
-def test_emu_edge_inputs(emu, oracle_lib):
-    _edge_inputs(emu, dc.HOST, oracle_lib)
+def test_emu_edge_inputs(emu_lib, oracle_lib):
+    _edge_inputs(emu_lib, dc.HOST, oracle_lib)
 
 
-def _failed_call_leaves_the_stream_untouched(emu, via):
+def _failed_call_leaves_the_stream_untouched(emu_lib, via):
     """A call that is refused takes nothing: waiting sub-lines still wait, the histories are as before, and the same records can be
     handed over again."""
     recs, st, want_p, want_f = _oracle("si_wander")
-    eng = emu.sdv_engine_create(0)
+    eng = emu_lib.sdv_engine_create(0)
     cut = 4000                                                                           # inside the third frame
-    rc, p0, f0 = via.pcm16_stitch(emu, eng, recs[:cut], st, pair_cap=20000, frame_cap=16)
+    rc, p0, f0 = via.pcm16_stitch(emu_lib, eng, recs[:cut], st, pair_cap=20000, frame_cap=16)
     assert rc == 0 and len(f0) == 2
-    rc, p, f = via.pcm16_stitch(emu, eng, recs[cut:], None, pair_cap=100, frame_cap=16)
-    assert rc != 0 and b"too small" in emu.sdv_last_error(eng)
-    rc, p1_, f1 = via.pcm16_stitch(emu, eng, recs[cut:], None, pair_cap=20000, frame_cap=16)   # the same records again
+    rc, p, f = via.pcm16_stitch(emu_lib, eng, recs[cut:], None, pair_cap=100, frame_cap=16)
+    assert rc != 0 and b"too small" in emu_lib.sdv_last_error(eng)
+    rc, p1_, f1 = via.pcm16_stitch(emu_lib, eng, recs[cut:], None, pair_cap=20000, frame_cap=16)   # the same records again
     assert rc == 0
-    emu.sdv_engine_destroy(eng)
+    emu_lib.sdv_engine_destroy(eng)
     pairs, frames = np.concatenate([p0, p1_]), np.concatenate([f0, f1])
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
 
 
-def test_emu_failed_call_leaves_the_stream_untouched(emu, oracle_lib):
-    _failed_call_leaves_the_stream_untouched(emu, dc.HOST)
+def test_emu_failed_call_leaves_the_stream_untouched(emu_lib, oracle_lib):
+    _failed_call_leaves_the_stream_untouched(emu_lib, dc.HOST)
 
 
-def test_emu_burst_counters_as_mask_arithmetic(emu):
+def test_emu_burst_counters_as_mask_arithmetic(emu_lib):
     """bursts_word (the analysis' burst counters on 64 blocks at once, pcm16_stitch_device.h) = the block-by-block counters of the reference's
     sweep (pcm16x0datastitcher.cpp:1380-1462) on 100 000 random flag sequences, SI and EI limits, words cut at random places."""
-    emu.sdv_emu_selftest_bursts.restype = C.c_int
-    emu.sdv_emu_selftest_bursts.argtypes = [C.c_uint64, C.c_int]
-    assert emu.sdv_emu_selftest_bursts(20261002, 100000) == 0
+    assert emu_lib.sdv_emu_selftest_bursts(20261002, 100000) == 0
 
 
 def _strangers():
@@ -223,33 +215,33 @@ def _strangers():
 
 
 @pytest.mark.parametrize("name,recs,st", list(_strangers()), ids=lambda v: v if isinstance(v, str) else "")
-def test_emu_refuses_what_the_reference_never_finishes(name, recs, st, emu):
+def test_emu_refuses_what_the_reference_never_finishes(name, recs, st, emu_lib):
     """A record numbered for another frame ahead of an END_FRAME: the reference pops its queue up to the stranger
     (pcm16x0datastitcher.cpp:5711-5732), finds the same END_FRAME again and assembles what is left of the frame without end (shown on
     the real reference: more frame reports than the stream has frames, until the driver's buffers are full).  The product refuses."""
     if libs.ref_available():
         pairs, n_frames = p16.run_cpu(libs.load_ref(), "ref_", recs, st, overflow_ok=True)
         assert pairs is None and n_frames > int((recs["service_type"] == p16.SRV_END_FRAME).sum())
-    eng = emu.sdv_engine_create(0)
-    rc, p, f = ea.emu_pcm16_stitch(emu, eng, recs, st)
-    assert rc != 0 and b"another frame" in emu.sdv_last_error(eng)
-    emu.sdv_engine_destroy(eng)
+    eng = emu_lib.sdv_engine_create(0)
+    rc, p, f = ea.emu_pcm16_stitch(emu_lib, eng, recs, st)
+    assert rc != 0 and b"another frame" in emu_lib.sdv_last_error(eng)
+    emu_lib.sdv_engine_destroy(eng)
 
 
-def _long_frame_takes_the_global_memory_path(emu, via, oracle_lib):
+def _long_frame_takes_the_global_memory_path(emu_lib, via, oracle_lib):
     """More sub-lines in a frame than the LDS staging holds (1536): the same result, read from global memory."""
     recs, _ = synth.pcm16x0_sub_stream(3, seed=88, cut=(4, 6), lead=(30, 30), trail=(20, 25), p_bad=0.03, p_picked=0.05, rate_44100=True)
     assert max(np.diff(np.nonzero(recs["service_type"] == p16.SRV_END_FRAME)[0])) > 1536
     st = p16.default_settings()
     want_p, want_f = p16.run_cpu(oracle_lib, "orc_", recs, st)
-    eng = emu.sdv_engine_create(0)
-    rc, pairs, frames = via.pcm16_stitch(emu, eng, recs, st)
-    emu.sdv_engine_destroy(eng)
+    eng = emu_lib.sdv_engine_create(0)
+    rc, pairs, frames = via.pcm16_stitch(emu_lib, eng, recs, st)
+    emu_lib.sdv_engine_destroy(eng)
     assert rc == 0 and _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
 
 
-def test_emu_long_frame_takes_the_global_memory_path(emu, oracle_lib):
-    _long_frame_takes_the_global_memory_path(emu, dc.HOST, oracle_lib)
+def test_emu_long_frame_takes_the_global_memory_path(emu_lib, oracle_lib):
+    _long_frame_takes_the_global_memory_path(emu_lib, dc.HOST, oracle_lib)
 
 
 # ---- the product on the GPU ------------------------------------------------------------------------------------------
@@ -507,18 +499,18 @@ def _long_tape(ei, hurt):
 
 
 @pytest.mark.parametrize("ei,hurt", [(False, True), (True, True)])       # (the clean tapes are the first 70 frames of these)
-def test_emu_long_tape_matches_oracle(ei, hurt, emu, oracle_lib):
+def test_emu_long_tape_matches_oracle(ei, hurt, emu_lib, oracle_lib):
     recs = _long_tape(ei, hurt)
     st = p16.default_settings(format=2 if ei else 1)
     want_p, want_f = p16.run_cpu(oracle_lib, "orc_", recs, st)
-    eng = emu.sdv_engine_create(0)
-    rc, pairs, frames = ea.emu_pcm16_stitch(emu, eng, recs, st)
-    emu.sdv_engine_destroy(eng)
+    eng = emu_lib.sdv_engine_create(0)
+    rc, pairs, frames = ea.emu_pcm16_stitch(emu_lib, eng, recs, st)
+    emu_lib.sdv_engine_destroy(eng)
     assert rc == 0 and len(want_f) == 150
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
 
 
-def _long_ei_tape_in_calls_matches_oracle(cuts, emu, via, oracle_lib):
+def _long_ei_tape_in_calls_matches_oracle(cuts, emu_lib, via, oracle_lib):
     """The EI tape above in several calls: from the second call on the padding history is full when a call begins, so the analysis makes its padding
     tables for that one padding (round 4) - all of them again for the hurt frames (70, 71, 100, 131), and the whole call once more where the history
     says something else in the middle of it (the second tape: its later frames are padded otherwise)."""
@@ -526,26 +518,26 @@ def _long_ei_tape_in_calls_matches_oracle(cuts, emu, via, oracle_lib):
     st = p16.default_settings(format=2)
     want_p, want_f = p16.run_cpu(oracle_lib, "orc_", recs, st)
     ends = np.nonzero(recs["service_type"] == 5)[0]
-    eng = emu.sdv_engine_create(0)
+    eng = emu_lib.sdv_engine_create(0)
     got_p, got_f = [], []
     lo = 0
     for k, c in enumerate(list(cuts) + [150]):
         hi = int(ends[c - 1]) + 1
-        rc, pairs, frames = via.pcm16_stitch(emu, eng, recs[lo:hi], st if k == 0 else None)
+        rc, pairs, frames = via.pcm16_stitch(emu_lib, eng, recs[lo:hi], st if k == 0 else None)
         assert rc == 0
         got_p.append(pairs); got_f.append(frames)
         lo = hi
-    emu.sdv_engine_destroy(eng)
+    emu_lib.sdv_engine_destroy(eng)
     pairs, frames = np.concatenate(got_p), np.concatenate(got_f)
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
 
 
 @pytest.mark.parametrize("cuts", [(68, 69, 101, 140)])
-def test_emu_long_ei_tape_in_calls_matches_oracle(cuts, emu, oracle_lib):
-    _long_ei_tape_in_calls_matches_oracle(cuts, emu, dc.HOST, oracle_lib)
+def test_emu_long_ei_tape_in_calls_matches_oracle(cuts, emu_lib, oracle_lib):
+    _long_ei_tape_in_calls_matches_oracle(cuts, emu_lib, dc.HOST, oracle_lib)
 
 
-def test_emu_ei_call_runs_again_with_full_tables(emu, oracle_lib, monkeypatch, capfd):
+def test_emu_ei_call_runs_again_with_full_tables(emu_lib, oracle_lib, monkeypatch, capfd):
     """The way back when a frame needed more than the one padding its table was made for: the emulator build's hook makes every such frame say so
     (SDV_P16_HINT_SKEW), the call then runs once more with full tables - the same answer, and the trace shows the second attempt."""
     recs = _long_tape(True, True)
@@ -554,13 +546,13 @@ def test_emu_ei_call_runs_again_with_full_tables(emu, oracle_lib, monkeypatch, c
     st = p16.default_settings(format=2)
     want_p, want_f = p16.run_cpu(oracle_lib, "orc_", recs, st)
     cut = int(ends[71]) + 1
-    eng = emu.sdv_engine_create(0)
-    rc, p0, f0 = ea.emu_pcm16_stitch(emu, eng, recs[:cut], st)
+    eng = emu_lib.sdv_engine_create(0)
+    rc, p0, f0 = ea.emu_pcm16_stitch(emu_lib, eng, recs[:cut], st)
     assert rc == 0
     monkeypatch.setenv("SDV_P16_HINT_SKEW", "1"); monkeypatch.setenv("SDV_P16_HINT_TRACE", "1")
-    rc, p1, f1 = ea.emu_pcm16_stitch(emu, eng, recs[cut:], None)
+    rc, p1, f1 = ea.emu_pcm16_stitch(emu_lib, eng, recs[cut:], None)
     assert rc == 0
-    emu.sdv_engine_destroy(eng)
+    emu_lib.sdv_engine_destroy(eng)
     err = capfd.readouterr().err
     assert "attempt 0: hint on" in err and "needs full tables: 1" in err and "attempt 1: hint off" in err, err
     pairs, frames = np.concatenate([p0, p1]), np.concatenate([f0, f1])

@@ -60,66 +60,59 @@ def test_oracle_matches_golden_from_reference(name, oracle_lib):
 
 
 @pytest.fixture(scope="module")
-def emu(emu_lib):
-    return ea.bind(emu_lib)
-
-
-@pytest.fixture(scope="module")
 def gpu():
     return dc.product_lib()
 
 
 @pytest.mark.parametrize("name", CASES)
-def test_emu_lines_match_oracle(name, emu, oracle_lib):
+def test_emu_lines_match_oracle(name, emu_lib, oracle_lib):
     recs, st, want_p, want_f, want_l = _oracle(name)
-    eng = emu.sdv_engine_create(0)
-    rc, pairs, frames, lines = ea.emu_pcm16_stitch_lines(emu, eng, recs, st)
+    eng = emu_lib.sdv_engine_create(0)
+    rc, pairs, frames, lines = ea.emu_pcm16_stitch_lines(emu_lib, eng, recs, st)
     assert rc == 0 and pairs.tobytes() == want_p.tobytes() and frames.tobytes() == want_f.tobytes()
     assert lines.tobytes() == want_l.tobytes(), [(f, np.argwhere(lines[f] != want_l[f])[:4].tolist()) for f in lines.dtype.names if lines[f].tobytes() != want_l[f].tobytes()]
-    emu.sdv_engine_destroy(eng)
+    emu_lib.sdv_engine_destroy(eng)
 
 
-def _lines_in_calls_and_too_small(emu, via):
+def _lines_in_calls_and_too_small(emu_lib, via):
     recs, st, want_p, want_f, want_l = _oracle("si_file_marks")
-    eng = emu.sdv_engine_create(0)
+    eng = emu_lib.sdv_engine_create(0)
     cuts = [0, len(recs) // 3, len(recs) // 3 + 11, len(recs)]
     got = []
     for a, b in zip(cuts[:-1], cuts[1:]):
-        rc, p, f, ln = via.pcm16_stitch_lines(emu, eng, recs[a:b], st if a == 0 else None)
+        rc, p, f, ln = via.pcm16_stitch_lines(emu_lib, eng, recs[a:b], st if a == 0 else None)
         assert rc == 0
         got.append(ln)
     assert np.concatenate(got).tobytes() == want_l.tobytes()
-    emu.sdv_engine_destroy(eng)
-    eng = emu.sdv_engine_create(0)
-    rc, p, f, ln = via.pcm16_stitch_lines(emu, eng, recs, st, line_cap=100)
-    assert rc != 0 and b"assembled sub-line records" in emu.sdv_last_error(eng) and via.last_count == len(want_l)
-    rc, p, f, ln = via.pcm16_stitch_lines(emu, eng, recs, st)                 # the refused call took nothing: once more with room
+    emu_lib.sdv_engine_destroy(eng)
+    eng = emu_lib.sdv_engine_create(0)
+    rc, p, f, ln = via.pcm16_stitch_lines(emu_lib, eng, recs, st, line_cap=100)
+    assert rc != 0 and b"assembled sub-line records" in emu_lib.sdv_last_error(eng) and via.last_count == len(want_l)
+    rc, p, f, ln = via.pcm16_stitch_lines(emu_lib, eng, recs, st)                 # the refused call took nothing: once more with room
     assert rc == 0 and ln.tobytes() == want_l.tobytes()
-    emu.sdv_engine_destroy(eng)
+    emu_lib.sdv_engine_destroy(eng)
 
 
-def test_emu_lines_in_calls_and_too_small(emu, oracle_lib):
-    _lines_in_calls_and_too_small(emu, dc.HOST)
+def test_emu_lines_in_calls_and_too_small(emu_lib, oracle_lib):
+    _lines_in_calls_and_too_small(emu_lib, dc.HOST)
 
 
-def _window_is_the_lines_renderer_on_the_feed(emu, via):
+def _window_is_the_lines_renderer_on_the_feed(emu_lib, via):
     """sdv_vis_render_lines(SDV_VIS_PCM16X0_LINES) on the feed = the oracle's renderer on the oracle's feed."""
-    import ctypes as C
     recs, st, want_p, want_f, want_l = _oracle("si_picked_forced")
-    eng = emu.sdv_engine_create(0)
-    rc, pairs, frames, lines = via.pcm16_stitch_lines(emu, eng, recs, st)
+    eng = emu_lib.sdv_engine_create(0)
+    rc, pairs, frames, lines = via.pcm16_stitch_lines(emu_lib, eng, recs, st)
     assert rc == 0
     n = ra.n_frames(lines)
-    emu.sdv_vis_render_lines.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
-    rc, out, nf = via.render_lines(emu, eng, ra.PCM16X0, lines, cap=n)
+    rc, out, nf = via.render_lines(emu_lib, eng, ra.PCM16X0, lines, cap=n)
     assert rc == 0 and nf == n
     want, _ = ra.run_oracle(ra.PCM16X0, want_l)
     assert (out == want).all()
-    emu.sdv_engine_destroy(eng)
+    emu_lib.sdv_engine_destroy(eng)
 
 
-def test_emu_window_is_the_lines_renderer_on_the_feed(emu, oracle_lib):
-    _window_is_the_lines_renderer_on_the_feed(emu, dc.HOST)
+def test_emu_window_is_the_lines_renderer_on_the_feed(emu_lib, oracle_lib):
+    _window_is_the_lines_renderer_on_the_feed(emu_lib, dc.HOST)
 
 
 @pytest.mark.gpu

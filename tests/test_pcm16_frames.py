@@ -66,7 +66,6 @@ def _info(lib, eng):
     """sdv_get_run_info through the shared binding (one argtypes declaration per library: engine_api.bind)."""
     import ctypes as C
     import engine_api
-    lib.sdv_get_run_info.argtypes = [C.c_void_p, C.POINTER(engine_api.RunInfo)]
     i = engine_api.RunInfo()
     lib.sdv_get_run_info(eng, C.byref(i))
     return i

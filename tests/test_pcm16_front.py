@@ -156,7 +156,6 @@ def test_states_reproduce_the_sequential_run(name, oracle_lib):
 
 @pytest.fixture(scope="module")
 def emu(emu_lib):
-    emu_lib.sdv_engine_create.restype = C.c_void_p
     eng = C.c_void_p(emu_lib.sdv_engine_create(0))
     yield emu_lib, eng
     emu_lib.sdv_engine_destroy(eng)

@@ -87,17 +87,11 @@ def test_oracle_matches_golden_from_reference(name, oracle_lib):
 
 
 @pytest.fixture(scope="module")
-def emu(emu_lib):
-    return ea.bind(emu_lib)
-
-
-@pytest.fixture(scope="module")
 def gpu():
     return dc.product_lib()
 
 
 def _emu_canvases(lib, eng, blocks, per):
-    lib.sdv_vis_render_blocks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
     w, h = ra.SIZE[ra.PCM16X0_BLOCKS]
     out = np.zeros((max(len(per), 1), h, w), dtype=np.uint32)
     assert lib.sdv_vis_render_blocks(eng, ra.PCM16X0_BLOCKS, blocks.ctypes.data, len(blocks), per.ctypes.data, len(per), out.ctypes.data, len(per), None) == 0
@@ -105,40 +99,40 @@ def _emu_canvases(lib, eng, blocks, per):
 
 
 @pytest.mark.parametrize("name", CASES)
-def test_emu_blocks_match_oracle(name, emu, oracle_lib):
+def test_emu_blocks_match_oracle(name, emu_lib, oracle_lib):
     recs, st, want_p, want_f, want_b, per = _oracle(name)
-    eng = emu.sdv_engine_create(0)
-    rc, pairs, frames, blocks = ea.emu_pcm16_stitch_vis(emu, eng, recs, st)
+    eng = emu_lib.sdv_engine_create(0)
+    rc, pairs, frames, blocks = ea.emu_pcm16_stitch_vis(emu_lib, eng, recs, st)
     assert rc == 0 and pairs.tobytes() == want_p.tobytes() and frames.tobytes() == want_f.tobytes()
     assert blocks.tobytes() == want_b.tobytes(), [(f, np.argwhere(blocks[f] != want_b[f])[:4].tolist()) for f in blocks.dtype.names if blocks[f].tobytes() != want_b[f].tobytes()]
     if name in RENDER_CASES:
-        got = _emu_canvases(emu, eng, np.ascontiguousarray(blocks), per)
+        got = _emu_canvases(emu_lib, eng, np.ascontiguousarray(blocks), per)
         want, _ = ra.run_oracle_blocks(ra.PCM16X0_BLOCKS, want_b, per)
         assert (got == want).all(), np.argwhere(got != want)[:4].tolist()
-    emu.sdv_engine_destroy(eng)
+    emu_lib.sdv_engine_destroy(eng)
 
 
-def _blocks_in_calls_and_too_small(emu, via):
+def _blocks_in_calls_and_too_small(emu_lib, via):
     recs, st, want_p, want_f, want_b, per = _oracle("si_file_marks")
-    eng = emu.sdv_engine_create(0)
+    eng = emu_lib.sdv_engine_create(0)
     cuts = [0, len(recs) // 3, len(recs) // 3 + 11, len(recs)]
     got = []
     for a, b in zip(cuts[:-1], cuts[1:]):
-        rc, p, f, bl = via.pcm16_stitch_vis(emu, eng, recs[a:b], st if a == 0 else None)
+        rc, p, f, bl = via.pcm16_stitch_vis(emu_lib, eng, recs[a:b], st if a == 0 else None)
         assert rc == 0
         got.append(bl)
     assert np.concatenate(got).tobytes() == want_b.tobytes()
-    emu.sdv_engine_destroy(eng)
-    eng = emu.sdv_engine_create(0)
-    rc, p, f, bl = via.pcm16_stitch_vis(emu, eng, recs, st, block_cap=7)
-    assert rc != 0 and b"blocks for the visualiser" in emu.sdv_last_error(eng) and via.last_count == len(want_b)
-    rc, p, f, bl = via.pcm16_stitch_vis(emu, eng, recs, st)                 # the refused call took nothing: once more with room
+    emu_lib.sdv_engine_destroy(eng)
+    eng = emu_lib.sdv_engine_create(0)
+    rc, p, f, bl = via.pcm16_stitch_vis(emu_lib, eng, recs, st, block_cap=7)
+    assert rc != 0 and b"blocks for the visualiser" in emu_lib.sdv_last_error(eng) and via.last_count == len(want_b)
+    rc, p, f, bl = via.pcm16_stitch_vis(emu_lib, eng, recs, st)                 # the refused call took nothing: once more with room
     assert rc == 0 and bl.tobytes() == want_b.tobytes()
-    emu.sdv_engine_destroy(eng)
+    emu_lib.sdv_engine_destroy(eng)
 
 
-def test_emu_blocks_in_calls_and_too_small(emu, oracle_lib):
-    _blocks_in_calls_and_too_small(emu, dc.HOST)
+def test_emu_blocks_in_calls_and_too_small(emu_lib, oracle_lib):
+    _blocks_in_calls_and_too_small(emu_lib, dc.HOST)
 
 
 @pytest.mark.gpu

@@ -104,7 +104,6 @@ import ctypes as C
 
 @pytest.fixture(scope="module")
 def emu(emu_lib):
-    emu_lib.sdv_engine_create.restype = C.c_void_p
     eng = C.c_void_p(emu_lib.sdv_engine_create(0))
     yield emu_lib, eng
     emu_lib.sdv_engine_destroy(eng)

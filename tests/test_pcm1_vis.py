@@ -56,48 +56,43 @@ def _check(name, blocks, lines, want_b, want_l):
 
 
 @pytest.fixture(scope="module")
-def emu(emu_lib):
-    return ea.bind(emu_lib)
-
-
-@pytest.fixture(scope="module")
 def gpu():
     return dc.product_lib()
 
 
 @pytest.mark.parametrize("name", CASES)
-def test_emu_matches_oracle(name, emu, oracle_lib):
+def test_emu_matches_oracle(name, emu_lib, oracle_lib):
     recs, st, want_p, want_f, want_b, want_l = _oracle(name)
-    eng = emu.sdv_engine_create(0)
-    rc, pairs, frames, blocks, lines = ea.emu_pcm1_stitch_vis(emu, eng, recs, st)
-    emu.sdv_engine_destroy(eng)
+    eng = emu_lib.sdv_engine_create(0)
+    rc, pairs, frames, blocks, lines = ea.emu_pcm1_stitch_vis(emu_lib, eng, recs, st)
+    emu_lib.sdv_engine_destroy(eng)
     assert rc == 0 and pairs.tobytes() == want_p.tobytes() and frames.tobytes() == want_f.tobytes()
     _check(name, blocks, lines, want_b, want_l)
 
 
-def _feeds_in_calls_and_too_small(emu, via):
+def _feeds_in_calls_and_too_small(emu_lib, via):
     """The feeds over a stream cut into calls (frames complete in later calls), one feed alone, and buffers that are too small."""
     recs, st, want_p, want_f, want_b, want_l = _oracle("file_marks")
-    eng = emu.sdv_engine_create(0)
+    eng = emu_lib.sdv_engine_create(0)
     cuts = [0, len(recs) // 3, len(recs) // 3 + 7, len(recs)]
     got_b, got_l = [], []
     for a, b in zip(cuts[:-1], cuts[1:]):
-        rc, p, f, bl, ln = via.pcm1_stitch_vis(emu, eng, recs[a:b], st if a == 0 else None)
+        rc, p, f, bl, ln = via.pcm1_stitch_vis(emu_lib, eng, recs[a:b], st if a == 0 else None)
         assert rc == 0
         got_b.append(bl); got_l.append(ln)
     _check("file_marks", np.concatenate(got_b), np.concatenate(got_l), want_b, want_l)
-    emu.sdv_engine_destroy(eng)
-    eng = emu.sdv_engine_create(0)
-    rc, p, f, bl, ln = via.pcm1_stitch_vis(emu, eng, recs, st, lines=False)
+    emu_lib.sdv_engine_destroy(eng)
+    eng = emu_lib.sdv_engine_create(0)
+    rc, p, f, bl, ln = via.pcm1_stitch_vis(emu_lib, eng, recs, st, lines=False)
     assert rc == 0 and len(ln) == 0 and via.last_counts == (len(want_b), 0)
     _check("file_marks", bl, want_l, want_b, want_l)
-    rc, p, f, bl, ln = via.pcm1_stitch_vis(emu, eng, recs, st, block_cap=5)
-    assert rc != 0 and b"visualiser buffers too small" in emu.sdv_last_error(eng) and via.last_counts == (len(want_b), len(want_l))
-    emu.sdv_engine_destroy(eng)
+    rc, p, f, bl, ln = via.pcm1_stitch_vis(emu_lib, eng, recs, st, block_cap=5)
+    assert rc != 0 and b"visualiser buffers too small" in emu_lib.sdv_last_error(eng) and via.last_counts == (len(want_b), len(want_l))
+    emu_lib.sdv_engine_destroy(eng)
 
 
-def test_emu_feeds_in_calls_and_too_small(emu, oracle_lib):
-    _feeds_in_calls_and_too_small(emu, dc.HOST)
+def test_emu_feeds_in_calls_and_too_small(emu_lib, oracle_lib):
+    _feeds_in_calls_and_too_small(emu_lib, dc.HOST)
 
 
 def _gpu_run(eng, recs, st, torch):

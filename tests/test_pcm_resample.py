@@ -16,7 +16,7 @@ import pytest
 import pcm_condition_api as P
 from pcm_condition_api import check
 
-L, M, HALF, BETA = 1000, 1001, 64, 12.0         # SDV_PCM_RESAMPLE_L / _M: 1000 outputs for 1001 pairs
+L, M, HALF, BETA = P.abi.PCM_RESAMPLE_L, P.abi.PCM_RESAMPLE_M, 64, 12.0         # 1000 outputs for 1001 pairs; 64 taps on each side
 T = 4000                                        # outputs per tile of the device's work (not in the header: no output depends on it; it places the cases)
 
 

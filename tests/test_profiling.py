@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 
 import dist_worker
+from sdvpcmdecoder_amd.abi import PCM_PCM1 as PCM1, PCM_PCM16X0 as PCM16X0, PCM_STC007 as STC007
 
-PCM1, PCM16X0, STC007 = 0, 1, 2
 ENTRIES = ["binarize_frames", "pcm1_binarize_frames", "pcm16x0_binarize_frames", "stitch_frames", "decode_frames"]
 
 

@@ -65,71 +65,58 @@ def test_canvas_is_kept_between_calls(oracle_lib):
 
 # ---- the product's kernels in the SIMT emulator ------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def emu(emu_lib):
-    lib = emu_lib
-    lib.sdv_engine_create.restype = C.c_void_p
-    lib.sdv_engine_destroy.argtypes = [C.c_void_p]
-    lib.sdv_last_error.restype = C.c_char_p
-    lib.sdv_last_error.argtypes = [C.c_void_p]
-    lib.sdv_vis_render_lines.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
-    lib.sdv_vis_reset.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    lib.sdv_vis_canvas_size.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    return lib
-
-
-@pytest.fixture(scope="module")
 def gpu():
     return dc.product_lib()
 
 
-def _emu_run(emu, eng, kind, recs, cap=None):
+def _emu_run(emu_lib, eng, kind, recs, cap=None):
     w, h = ra.SIZE[kind]
     n = ra.n_frames(recs) if cap is None else cap
     out = np.zeros((max(n, 1), h, w), dtype=np.uint32)
     got = C.c_size_t(0)
     recs = np.ascontiguousarray(recs)
-    rc = emu.sdv_vis_render_lines(eng, kind, recs.ctypes.data, len(recs), out.ctypes.data, n, C.byref(got), None)
+    rc = emu_lib.sdv_vis_render_lines(eng, kind, recs.ctypes.data, len(recs), out.ctypes.data, n, C.byref(got), None)
     return rc, out[:min(got.value, n)], got.value
 
 
 @pytest.mark.parametrize("name", list(ra.CASES))
-def test_emu_matches_oracle(name, emu):
+def test_emu_matches_oracle(name, emu_lib):
     kind, recs = ra.make_input(name)
     want, _ = ra.run_oracle(kind, recs)
-    eng = emu.sdv_engine_create(0)
-    rc, out, n = _emu_run(emu, eng, kind, recs)
-    emu.sdv_engine_destroy(eng)
+    eng = emu_lib.sdv_engine_create(0)
+    rc, out, n = _emu_run(emu_lib, eng, kind, recs)
+    emu_lib.sdv_engine_destroy(eng)
     assert rc == 0 and n == len(want)
     assert (out == want).all(), _diff(out, want, np.ones_like(want, dtype=bool))
 
 
-def _calls_continue_on_the_kept_canvas(emu, via):
+def _calls_continue_on_the_kept_canvas(emu_lib, via):
     """Two calls = one call; a reset in between starts from a blank canvas; a buffer that is too small is refused with the count."""
     kind, recs = ra.make_input("stc_shrinking")
     want, _ = ra.run_oracle(kind, recs)
     ends = np.nonzero(recs["service_type"] == ra.SRV_END_FRAME)[0]
     cut = ends[0] + 1
-    eng = emu.sdv_engine_create(0)
-    rc, a, _ = via.render_lines(emu, eng, kind, recs[:cut])
+    eng = emu_lib.sdv_engine_create(0)
+    rc, a, _ = via.render_lines(emu_lib, eng, kind, recs[:cut])
     assert rc == 0
-    rc, b, n = via.render_lines(emu, eng, kind, recs[cut:], cap=1)
-    assert rc != 0 and n == 3 and b"3 canvases" in emu.sdv_last_error(eng)
-    rc, b, _ = via.render_lines(emu, eng, kind, recs[cut:])
+    rc, b, n = via.render_lines(emu_lib, eng, kind, recs[cut:], cap=1)
+    assert rc != 0 and n == 3 and b"3 canvases" in emu_lib.sdv_last_error(eng)
+    rc, b, _ = via.render_lines(emu_lib, eng, kind, recs[cut:])
     assert rc == 0 and (np.concatenate([a, b]) == want).all()
-    assert emu.sdv_vis_reset(eng, kind, via.stream()) == 0
-    rc, c, _ = via.render_lines(emu, eng, kind, recs[cut:])
+    assert emu_lib.sdv_vis_reset(eng, kind, via.stream()) == 0
+    rc, c, _ = via.render_lines(emu_lib, eng, kind, recs[cut:])
     fresh, _ = ra.run_oracle(kind, recs[cut:])
     assert rc == 0 and (c == fresh).all()
-    rc, d, n = via.render_lines(emu, eng, kind, recs[cut:ends[1]])         # no frame ends in these records: nothing is handed out
+    rc, d, n = via.render_lines(emu_lib, eng, kind, recs[cut:ends[1]])         # no frame ends in these records: nothing is handed out
     assert rc == 0 and n == 0
     w, h = C.c_uint32(0), C.c_uint32(0)
-    assert emu.sdv_vis_canvas_size(kind, C.byref(w), C.byref(h)) == 0 and (w.value, h.value) == ra.SIZE[kind]
-    assert emu.sdv_vis_canvas_size(10, C.byref(w), C.byref(h)) != 0          # no such canvas
-    emu.sdv_engine_destroy(eng)
+    assert emu_lib.sdv_vis_canvas_size(kind, C.byref(w), C.byref(h)) == 0 and (w.value, h.value) == ra.SIZE[kind]
+    assert emu_lib.sdv_vis_canvas_size(10, C.byref(w), C.byref(h)) != 0          # no such canvas
+    emu_lib.sdv_engine_destroy(eng)
 
 
-def test_emu_calls_continue_on_the_kept_canvas(emu):
-    _calls_continue_on_the_kept_canvas(emu, dc.HOST)
+def test_emu_calls_continue_on_the_kept_canvas(emu_lib):
+    _calls_continue_on_the_kept_canvas(emu_lib, dc.HOST)
 
 
 # ---- the product on the GPU --------------------------------------------------------------------------------------------------------
@@ -220,7 +207,7 @@ def test_oracle_block_canvases_match_golden(name, oracle_lib):
     assert (_masked(out[-1], mask[-1]) == z["last_canvas"]).all()
 
 
-def _emu_blocks(emu, name, two_calls=False, via=dc.HOST):
+def _emu_blocks(emu_lib, name, two_calls=False, via=dc.HOST):
     """The product's path (in the emulator, or with via=dc.DEVICE on the GPU): records -> sdv_stitch_frames with a block buffer set -> sdv_vis_render_blocks."""
     import engine_api as ea
     import stitch_cases as sc
@@ -228,11 +215,7 @@ def _emu_blocks(emu, name, two_calls=False, via=dc.HOST):
     import oracle_run
     kind, want_blocks, per = ra.make_block_input(name)
     recs, st = sc.make_input(ra.BLOCK_CASES[name][1], lambda luma: oracle_run.oracle_binarize(luma, mode=2))
-    lib = ea.bind(emu)
-    lib.sdv_set_stitch_block_output.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.sdv_stitch_block_count.restype = C.c_size_t
-    lib.sdv_stitch_block_count.argtypes = [C.c_void_p]
-    lib.sdv_vis_render_blocks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib = emu_lib
     eng = lib.sdv_engine_create(0)
     buf = via.zeros(len(want_blocks) + 8, sa.BLOCK_DTYPE)
     assert lib.sdv_set_stitch_block_output(eng, via.ptr(buf), len(buf)) == 0
@@ -255,34 +238,31 @@ def _emu_blocks(emu, name, two_calls=False, via=dc.HOST):
 
 
 @pytest.mark.parametrize("name", list(ra.BLOCK_CASES))
-def test_emu_blocks_and_their_canvases_match_oracle(name, emu):
-    kind, want_blocks, per, blocks, canvases = _emu_blocks(emu, name)
+def test_emu_blocks_and_their_canvases_match_oracle(name, emu_lib):
+    kind, want_blocks, per, blocks, canvases = _emu_blocks(emu_lib, name)
     assert blocks.tobytes() == want_blocks.tobytes()
     want, _ = ra.run_oracle_blocks(kind, want_blocks, per)
     assert (canvases == want).all(), _diff(canvases, want, np.ones_like(want, dtype=bool))
 
 
-def _blocks_in_two_calls(emu, via):
-    kind, want_blocks, per, blocks, canvases = _emu_blocks(emu, "blk_burst", two_calls=True, via=via)
+def _blocks_in_two_calls(emu_lib, via):
+    kind, want_blocks, per, blocks, canvases = _emu_blocks(emu_lib, "blk_burst", two_calls=True, via=via)
     assert blocks.tobytes() == want_blocks.tobytes()
     want, _ = ra.run_oracle_blocks(kind, want_blocks, per)
     assert (canvases == want).all()
 
 
-def test_emu_blocks_in_two_calls(emu):
-    _blocks_in_two_calls(emu, dc.HOST)
+def test_emu_blocks_in_two_calls(emu_lib):
+    _blocks_in_two_calls(emu_lib, dc.HOST)
 
 
-def _block_buffer_too_small_is_refused_with_the_count(emu, via):
+def _block_buffer_too_small_is_refused_with_the_count(emu_lib, via):
     import engine_api as ea
     import stitch_cases as sc
     import stitch_api as sa
     import oracle_run
     recs, st = sc.make_input("ntsc_clean", lambda luma: oracle_run.oracle_binarize(luma, mode=2))
-    lib = ea.bind(emu)
-    lib.sdv_set_stitch_block_output.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.sdv_stitch_block_count.restype = C.c_size_t
-    lib.sdv_stitch_block_count.argtypes = [C.c_void_p]
+    lib = emu_lib
     eng = lib.sdv_engine_create(0)
     buf = via.zeros(100, sa.BLOCK_DTYPE, 2530)          # (on the device: room for what the call needs behind the 100 it is told of, then the guard)
     assert lib.sdv_set_stitch_block_output(eng, via.ptr(buf), len(buf)) == 0
@@ -292,8 +272,8 @@ def _block_buffer_too_small_is_refused_with_the_count(emu, via):
     lib.sdv_engine_destroy(eng)
 
 
-def test_emu_block_buffer_too_small_is_refused_with_the_count(emu):
-    _block_buffer_too_small_is_refused_with_the_count(emu, dc.HOST)
+def test_emu_block_buffer_too_small_is_refused_with_the_count(emu_lib):
+    _block_buffer_too_small_is_refused_with_the_count(emu_lib, dc.HOST)
 
 
 @pytest.mark.gpu
@@ -359,7 +339,7 @@ def test_oracle_asm_canvases_match_golden(name, oracle_lib):
 
 
 @pytest.mark.parametrize("name", list(ra.ASM_CASES))
-def test_emu_asm_lines_and_their_canvases_match_oracle(name, emu):
+def test_emu_asm_lines_and_their_canvases_match_oracle(name, emu_lib):
     """Records -> sdv_stitch_frames with a line buffer set (two calls) -> sdv_vis_render_asm_lines, in the emulator."""
     import engine_api as ea
     import stitch_cases as sc
@@ -367,13 +347,7 @@ def test_emu_asm_lines_and_their_canvases_match_oracle(name, emu):
     import oracle_run
     kind, want_lines, want_per = ra.make_asm_input(name)
     recs, st = sc.make_input(ra.ASM_CASES[name][1], lambda luma: oracle_run.oracle_binarize(luma, mode=2))
-    lib = ea.bind(emu)
-    lib.sdv_set_stitch_line_output.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.sdv_stitch_line_count.restype = C.c_size_t
-    lib.sdv_stitch_line_count.argtypes = [C.c_void_p]
-    lib.sdv_stitch_line_counts.restype = C.c_size_t
-    lib.sdv_stitch_line_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.sdv_vis_render_asm_lines.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib = emu_lib
     eng = lib.sdv_engine_create(0)
     buf = np.zeros(len(want_lines) + 8, dtype=sa.ASM_DTYPE)
     assert lib.sdv_set_stitch_line_output(eng, buf.ctypes.data, 10) == 0
@@ -464,10 +438,9 @@ def test_oracle_pcm1_stitcher_canvases_match_golden(name, oracle_lib):
     assert (_masked(out[-1], mask[-1]) == z["last_line_canvas"]).all()
 
 
-def _emu_p1vis(emu, blocks, per, lines, calls=1, via=dc.HOST):
+def _emu_p1vis(emu_lib, blocks, per, lines, calls=1, via=dc.HOST):
     import engine_api as ea
-    lib = ea.bind(emu)
-    lib.sdv_vis_render_blocks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib = emu_lib
     eng = lib.sdv_engine_create(0)
     bc, lc = [], []
     n = len(per)
@@ -485,26 +458,26 @@ def _emu_p1vis(emu, blocks, per, lines, calls=1, via=dc.HOST):
 
 
 @pytest.mark.parametrize("name", ra.P1VIS_CASES)
-def test_emu_pcm1_stitcher_canvases_match_oracle(name, emu):
+def test_emu_pcm1_stitcher_canvases_match_oracle(name, emu_lib):
     blocks, per, lines = ra.make_p1vis_input(name)
-    bc, lc = _emu_p1vis(emu, blocks, per, lines)
+    bc, lc = _emu_p1vis(emu_lib, blocks, per, lines)
     want, _ = ra.run_oracle_blocks(ra.PCM1_BLOCKS, blocks, per)
     assert (bc == want).all(), _diff(bc, want, np.ones_like(want, dtype=bool))
     want, _ = ra.run_oracle_lines_into(ra.PCM1_ASM, lines, len(per))
     assert (lc == want).all(), _diff(lc, want, np.ones_like(want, dtype=bool))
 
 
-def _pcm1_stitcher_canvases_in_two_calls(emu, via):
+def _pcm1_stitcher_canvases_in_two_calls(emu_lib, via):
     blocks, per, lines = ra.make_p1vis_input("manual_lost_lines")
-    bc, lc = _emu_p1vis(emu, blocks, per, lines, calls=2, via=via)
+    bc, lc = _emu_p1vis(emu_lib, blocks, per, lines, calls=2, via=via)
     want, _ = ra.run_oracle_blocks(ra.PCM1_BLOCKS, blocks, per)
     assert (bc == want).all()
     want, _ = ra.run_oracle_lines_into(ra.PCM1_ASM, lines, len(per))
     assert (lc == want).all()
 
 
-def test_emu_pcm1_stitcher_canvases_in_two_calls(emu):
-    _pcm1_stitcher_canvases_in_two_calls(emu, dc.HOST)
+def test_emu_pcm1_stitcher_canvases_in_two_calls(emu_lib):
+    _pcm1_stitcher_canvases_in_two_calls(emu_lib, dc.HOST)
 
 
 @pytest.mark.gpu

@@ -11,31 +11,20 @@ accumulation differs in about one word of 430 and fails (test_the_condition_tell
 Every field but audio_word is compared bytewise, and the output count must be equal."""
 import ctypes as C
 import math
-import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
 import audio_api as A
+from sdvpcmdecoder_amd import abi
 from stitch_api import PAIR_DTYPE
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = open(os.path.join(ROOT, "include", "sdvpcm.h")).read()
-
-
-def _define(name):
-    m = re.search(r"#define %s (\d+)" % name, HDR)
-    assert m, "include/sdvpcm.h does not define %s" % name
-    return int(m.group(1))
-
-
-L, M, HALF = _define("SDV_RESAMPLE_L"), _define("SDV_RESAMPLE_M"), _define("SDV_RESAMPLE_HALF")
+L, M, HALF = abi.RESAMPLE_L, abi.RESAMPLE_M, abi.RESAMPLE_HALF
 assert (L, M, HALF) == (1001, 1000, 64)
 T = 1024                # the device's tile (audio_resample_device.h); not in the header: no output depends on it, it only places the cases
-OFF, ON = 0, 1
-BAD_ARG, NULL_LINES, NULL_BLOCK = -1, 16, 17
+OFF, ON = abi.RESAMPLE_OFF, abi.RESAMPLE_TO_44100
+BAD_ARG, NULL_LINES, NULL_BLOCK = abi.ERR_BAD_ARG, abi.ERR_NULL_LINES, abi.ERR_NULL_BLOCK
 BETA = 12.0
 
 
@@ -163,24 +152,6 @@ def wanted(key, pairs):
 
 
 # ---- the two ways to the code under test ---------------------------------------------------------------------------------------
-def bind(lib):
-    lib.sdv_resample_taps.argtypes = [C.c_int, C.POINTER(C.c_double)]
-    lib.sdv_resample_taps.restype = None
-    lib.sdv_set_resample.argtypes = [C.c_void_p, C.c_int]
-    lib.sdv_reset_resample.argtypes = [C.c_void_p]
-    lib.sdv_audio_resample_pending.restype = C.c_size_t
-    lib.sdv_audio_resample_pending.argtypes = [C.c_void_p]
-    lib.sdv_audio_resample_room.restype = C.c_size_t
-    lib.sdv_audio_resample_room.argtypes = [C.c_void_p, C.c_size_t]
-    lib.sdv_audio_resample.restype = C.c_int
-    lib.sdv_audio_resample.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
-    lib.sdv_engine_create.restype = C.c_void_p
-    lib.sdv_engine_destroy.argtypes = [C.c_void_p]
-    lib.sdv_last_error.restype = C.c_char_p
-    lib.sdv_last_error.argtypes = [C.c_void_p]
-    return lib
-
-
 class Backend:
     def mode(self, m):
         return self.lib.sdv_set_resample(self.h, m)
@@ -207,7 +178,7 @@ class Backend:
 class Emu(Backend):
     """The emulator build: host memory."""
     def __init__(self, lib):
-        self.lib = bind(lib)
+        self.lib = lib
         self.h = C.c_void_p(self.lib.sdv_engine_create(0))
 
     def close(self):
@@ -234,7 +205,7 @@ class Gpu(Backend):
     def __init__(self):
         from sdvpcmdecoder_amd import Engine
         self.eng = Engine(0)
-        self.lib, self.h = bind(self.eng.lib), self.eng._h
+        self.lib, self.h = self.eng.lib, self.eng._h
 
     def close(self):
         self.eng.close()
@@ -434,7 +405,7 @@ def _reset_and_off(be):
 # ---- CPU: the taps of the product library, the definition itself, the emulator ---------------------------------------------------
 def test_symbols_and_taps_of_the_product_library():
     from sdvpcmdecoder_amd import build as b
-    lib = bind(C.CDLL(b.build_hip()))
+    lib = abi.bind(C.CDLL(b.build_hip()))
     got = np.zeros((L, 2 * HALF))
     for p in range(L):
         c = (C.c_double * 128)()
@@ -655,7 +626,7 @@ def test_gpu_decode_tape_wav_44100(tmp_path):
     masked, pur, _ = eng.audio_process(p, stop=True)
     plain = eng.wav_files(masked, pur)[0]
     assert tape() == plain and tape("6") == plain
-    pv = pur.cpu().numpy().view(np.dtype([("first_pair", "<u8"), ("tag_index", "<u4"), ("kind", "u1"), ("_pad", "u1", 3)])).reshape(-1)
+    pv = pur.cpu().numpy().view(A.PURGE_DTYPE).reshape(-1)
     k = int(np.nonzero(pv["kind"] == 1)[0][0])
     a0, a1 = int(pv["first_pair"][k]), int(pv["first_pair"][k + 1]) if k + 1 < len(pv) else masked.shape[0]
     eng.set_deemphasis(2)
@@ -672,8 +643,7 @@ def test_gpu_decode_tape_wav_44100(tmp_path):
         want = wanted(("tape", base is plain), src)
         assert len(got) == 44 + 4 * len(want)
         hdr = C.create_string_buffer(44)
-        lib = C.CDLL(b.build_hip())
-        lib.sdv_wav_header.argtypes = [C.c_char_p, C.c_uint64, C.c_uint16]
+        lib = abi.bind(C.CDLL(b.build_hip()))
         lib.sdv_wav_header(hdr, len(want), 44100)
         assert got[:44] == hdr.raw and got[24:28] == (44100).to_bytes(4, "little")
         res = want.copy()

@@ -11,8 +11,7 @@ import pytest
 import libs
 from pcm1_front_api import STATE_DTYPE
 from sdvpcmdecoder_amd import synth
-
-LF_BY_EXT_TUNE, LF_BW_SET, LF_CRC_VALID = 4, 8, 64
+from sdvpcmdecoder_amd.abi import LF_BY_EXT_TUNE, LF_BW_SET, LF_CRC_VALID
 
 
 def _lines(seed=5, noise=4.0, width=720):
@@ -96,9 +95,6 @@ def _states_behind(recs, mode):
 def _engine_lines_host(lib, eng, rows, states, mode, doubled=False, first_line=1, line_step=2, frame=7, pad=0):
     """pad > 0: the lines in a buffer of rows pad bytes longer than a line (row_stride > width), the bytes between them 0x5A."""
     f = lib.sdv_binarize_lines
-    f.restype = C.c_int
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint16, C.c_uint16, C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.sdv_set_mode.argtypes = [C.c_void_p, C.c_int]
     lib.sdv_set_mode(eng, mode)
     out = np.zeros(len(rows), dtype=libs.LINE_DTYPE)
     st = None if states is None else np.ascontiguousarray(states)

@@ -35,44 +35,39 @@ def _diff(pairs, frames, want_p, want_f):
 
 
 @pytest.fixture(scope="module")
-def emu(emu_lib):
-    return ea.bind(emu_lib)
-
-
-@pytest.fixture(scope="module")
 def gpu():
     return dc.product_lib()
 
 
 @pytest.mark.parametrize("name", EMU_CASES)
-def test_emu_matches_oracle(name, emu, oracle_lib):
+def test_emu_matches_oracle(name, emu_lib, oracle_lib):
     recs, st = sc.make_input(name, lambda luma: oracle_binarize(luma, mode=2))
     want_p, want_f = sa.run_cpu(libs.load_oracle(), "orc_", recs, st)
-    eng = emu.sdv_engine_create(0)
-    rc, pairs, frames = ea.emu_stitch(emu, eng, recs, st)
-    emu.sdv_engine_destroy(eng)
+    eng = emu_lib.sdv_engine_create(0)
+    rc, pairs, frames = ea.emu_stitch(emu_lib, eng, recs, st)
+    emu_lib.sdv_engine_destroy(eng)
     assert rc == 0
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
 
 
-def _streaming_calls_equal_one_call(emu, via):
+def _streaming_calls_equal_one_call(emu_lib, via):
     """The stream may arrive in arbitrary pieces (frame by frame, mid-frame): the engine keeps what cannot be stitched yet."""
     recs, st = sc.make_input("ntsc_bad5", lambda luma: oracle_binarize(luma, mode=2))
     want_p, want_f = sa.run_cpu(libs.load_oracle(), "orc_", recs, st)
-    eng = emu.sdv_engine_create(0)
+    eng = emu_lib.sdv_engine_create(0)
     cuts = [0, 1, 300, 490, 1000, 1471, 1472, 2500, len(recs)]
     got_p, got_f = [], []
     for a, b in zip(cuts[:-1], cuts[1:]):
-        rc, p, f = via.stitch(emu, eng, recs[a:b], st if a == 0 else None, pair_cap=20000, frame_cap=64)
+        rc, p, f = via.stitch(emu_lib, eng, recs[a:b], st if a == 0 else None, pair_cap=20000, frame_cap=64)
         assert rc == 0
         got_p.append(p.copy()); got_f.append(f.copy())
-    emu.sdv_engine_destroy(eng)
+    emu_lib.sdv_engine_destroy(eng)
     pairs, frames = np.concatenate(got_p), np.concatenate(got_f)
     assert _same(pairs, frames, want_p, want_f), _diff(pairs, frames, want_p, want_f)
 
 
-def test_emu_streaming_calls_equal_one_call(emu, oracle_lib):
-    _streaming_calls_equal_one_call(emu, dc.HOST)
+def test_emu_streaming_calls_equal_one_call(emu_lib, oracle_lib):
+    _streaming_calls_equal_one_call(emu_lib, dc.HOST)
 
 
 def _frame_cuts(recs, frames_per_call):
@@ -119,7 +114,7 @@ PIPE_CASES = {
 }
 
 
-def _pipelined_calls_equal_one_call(name, emu, via):
+def _pipelined_calls_equal_one_call(name, emu_lib, via):
     """A stream that plays is stitched without waiting for the host between the stages (stitch_engine.inc "1p"): whatever the later calls meet -
     more frames than the estimate, damage, another resolution or field order, the end of the file - the PCM stream is the sequential one's."""
     tape_kw, per_call, dmg, want_piped = PIPE_CASES[name]
@@ -132,17 +127,17 @@ def _pipelined_calls_equal_one_call(name, emu, via):
         recs = np.concatenate([recs[:a], tail])
     st = sa.default_settings()
     want_p, want_f = sa.run_cpu(libs.load_oracle(), "orc_", recs, st)
-    eng = emu.sdv_engine_create(0)
+    eng = emu_lib.sdv_engine_create(0)
     cuts = _frame_cuts(recs, per_call)
     got_p, got_f, piped = [], [], []
     info = ea.StitchInfo()
     for a, b in zip(cuts[:-1], cuts[1:]):
-        rc, p, f = via.stitch(emu, eng, recs[a:b], st if a == 0 else None, pair_cap=30000, frame_cap=64)
+        rc, p, f = via.stitch(emu_lib, eng, recs[a:b], st if a == 0 else None, pair_cap=30000, frame_cap=64)
         assert rc == 0, (a, b)
         got_p.append(p.copy()); got_f.append(f.copy())
-        assert emu.sdv_get_stitch_info(eng, C.byref(info)) == 0
+        assert emu_lib.sdv_get_stitch_info(eng, C.byref(info)) == 0
         piped.append(int(info.pipelined))
-    emu.sdv_engine_destroy(eng)
+    emu_lib.sdv_engine_destroy(eng)
     pairs, frames = np.concatenate(got_p), np.concatenate(got_f)
     print("pipelined per call (%s, %s): %s" % (name, via.name, piped))
     assert _same(pairs, frames, want_p, want_f), (_diff(pairs, frames, want_p, want_f), piped)
@@ -153,90 +148,84 @@ def _pipelined_calls_equal_one_call(name, emu, via):
 
 
 @pytest.mark.parametrize("name", list(PIPE_CASES))
-def test_emu_pipelined_calls_equal_one_call(name, emu, oracle_lib):
-    _pipelined_calls_equal_one_call(name, emu, dc.HOST)
+def test_emu_pipelined_calls_equal_one_call(name, emu_lib, oracle_lib):
+    _pipelined_calls_equal_one_call(name, emu_lib, dc.HOST)
 
 
-def _pipelined_calls_feed_the_visualiser(emu, via):
+def _pipelined_calls_feed_the_visualiser(emu_lib, via):
     """The data blocks and the assembled lines of pipelined calls (their turns are run once more from the final hand-overs; the first
     round of such a call never went through the host's per-turn arrays) equal those of the sequential run."""
     recs = _pipelined_tape(n=14)
     st = sa.default_settings()
     _, _, want_blocks = sa.run_cpu_blocks(libs.load_oracle(), "orc_", recs, st)
     want_lines, _ = sa.last_asm_lines(libs.load_oracle(), "orc_")
-    emu.sdv_set_stitch_block_output.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    emu.sdv_stitch_block_count.restype = C.c_size_t
-    emu.sdv_stitch_block_count.argtypes = [C.c_void_p]
-    emu.sdv_set_stitch_line_output.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    emu.sdv_stitch_line_count.restype = C.c_size_t
-    emu.sdv_stitch_line_count.argtypes = [C.c_void_p]
-    eng = emu.sdv_engine_create(0)
+    eng = emu_lib.sdv_engine_create(0)
     bbuf = via.zeros(len(want_blocks) + 8, sa.BLOCK_DTYPE)
     lbuf = via.zeros(len(want_lines) + 8, sa.ASM_DTYPE)
-    assert emu.sdv_set_stitch_block_output(eng, via.ptr(bbuf), len(bbuf)) == 0
-    assert emu.sdv_set_stitch_line_output(eng, via.ptr(lbuf), len(lbuf)) == 0
+    assert emu_lib.sdv_set_stitch_block_output(eng, via.ptr(bbuf), len(bbuf)) == 0
+    assert emu_lib.sdv_set_stitch_line_output(eng, via.ptr(lbuf), len(lbuf)) == 0
     cuts = _frame_cuts(recs, [3] * 5)
     blocks, lines, piped = [], [], []
     info = ea.StitchInfo()
     for a, b in zip(cuts[:-1], cuts[1:]):
-        rc, _, _ = via.stitch(emu, eng, recs[a:b], st if a == 0 else None, pair_cap=30000, frame_cap=64)
+        rc, _, _ = via.stitch(emu_lib, eng, recs[a:b], st if a == 0 else None, pair_cap=30000, frame_cap=64)
         assert rc == 0
-        blocks.append(via.get(bbuf, emu.sdv_stitch_block_count(eng))); lines.append(via.get(lbuf, emu.sdv_stitch_line_count(eng)))
-        assert emu.sdv_get_stitch_info(eng, C.byref(info)) == 0
+        blocks.append(via.get(bbuf, emu_lib.sdv_stitch_block_count(eng))); lines.append(via.get(lbuf, emu_lib.sdv_stitch_line_count(eng)))
+        assert emu_lib.sdv_get_stitch_info(eng, C.byref(info)) == 0
         piped.append(int(info.pipelined))
-    emu.sdv_engine_destroy(eng)
+    emu_lib.sdv_engine_destroy(eng)
     assert sum(1 for x in piped if x) >= 2, piped
     assert np.concatenate(blocks).tobytes() == want_blocks.tobytes()
     assert np.concatenate(lines).tobytes() == want_lines.tobytes()
 
 
-def test_emu_pipelined_calls_feed_the_visualiser(emu, oracle_lib):
-    _pipelined_calls_feed_the_visualiser(emu, dc.HOST)
+def test_emu_pipelined_calls_feed_the_visualiser(emu_lib, oracle_lib):
+    _pipelined_calls_feed_the_visualiser(emu_lib, dc.HOST)
 
 
-def test_emu_pipelined_call_reports_what_the_host_would_have_refused(emu, oracle_lib):
+def test_emu_pipelined_call_reports_what_the_host_would_have_refused(emu_lib, oracle_lib):
     """Frame numbers that do not increase are refused before the turns run; a pipelined call has run them already - the call fails all the same."""
     recs = _pipelined_tape(n=14, end_file=False)
     st = sa.default_settings()
-    eng = emu.sdv_engine_create(0)
+    eng = emu_lib.sdv_engine_create(0)
     cuts = _frame_cuts(recs, [3, 3, 3, 3])
     info = ea.StitchInfo()
     for a, b in zip(cuts[:3], cuts[1:4]):
-        rc, _, _ = ea.emu_stitch(emu, eng, recs[a:b], st if a == 0 else None, pair_cap=30000, frame_cap=64)
+        rc, _, _ = ea.emu_stitch(emu_lib, eng, recs[a:b], st if a == 0 else None, pair_cap=30000, frame_cap=64)
         assert rc == 0
-    assert emu.sdv_get_stitch_info(eng, C.byref(info)) == 0 and info.pipelined == 1
+    assert emu_lib.sdv_get_stitch_info(eng, C.byref(info)) == 0 and info.pipelined == 1
     again = recs[cuts[2]:cuts[3]].copy()            # the frames of the last call once more: numbers go backwards
-    rc, _, _ = ea.emu_stitch(emu, eng, again, None, pair_cap=30000, frame_cap=64)
-    assert rc == -4 and b"frame numbers" in emu.sdv_last_error(eng)      # SDV_ERR_UNSUPPORTED
-    emu.sdv_engine_destroy(eng)
+    rc, _, _ = ea.emu_stitch(emu_lib, eng, again, None, pair_cap=30000, frame_cap=64)
+    assert rc == -4 and b"frame numbers" in emu_lib.sdv_last_error(eng)      # SDV_ERR_UNSUPPORTED
+    emu_lib.sdv_engine_destroy(eng)
 
 
-def _empty_and_tiny_inputs(emu, via):
+def _empty_and_tiny_inputs(emu_lib, via):
     """Nothing in, nothing out; a single frame has no successor yet and produces nothing until the next one arrives; a stream that
     is only the end-of-file frame produces nothing at all."""
     recs, st = sc.make_input("ntsc_clean", lambda luma: oracle_binarize(luma, mode=2))
     want_p, want_f = sa.run_cpu(libs.load_oracle(), "orc_", recs, st)
-    eng = emu.sdv_engine_create(0)
-    rc, p, f = via.stitch(emu, eng, recs[:0], st, pair_cap=16, frame_cap=4)
+    eng = emu_lib.sdv_engine_create(0)
+    rc, p, f = via.stitch(emu_lib, eng, recs[:0], st, pair_cap=16, frame_cap=4)
     assert rc == 0 and len(p) == 0 and len(f) == 0
     one = 1 + 489                                   # NEW_FILE + the first frame
-    rc, p, f = via.stitch(emu, eng, recs[:one], None, pair_cap=16, frame_cap=4)
+    rc, p, f = via.stitch(emu_lib, eng, recs[:one], None, pair_cap=16, frame_cap=4)
     assert rc == 0 and len(p) == 0 and len(f) == 0
-    rc, p, f = via.stitch(emu, eng, recs[one:], None)
+    rc, p, f = via.stitch(emu_lib, eng, recs[one:], None)
     assert rc == 0 and _same(p, f, want_p, want_f), _diff(p, f, want_p, want_f)
-    emu.sdv_engine_destroy(eng)
-    eng = emu.sdv_engine_create(0)
+    emu_lib.sdv_engine_destroy(eng)
+    eng = emu_lib.sdv_engine_create(0)
     tail = recs[-(486 + 4):]                        # filler frame + END_FILE only
-    rc, p, f = via.stitch(emu, eng, tail, st, pair_cap=16, frame_cap=4)
+    rc, p, f = via.stitch(emu_lib, eng, tail, st, pair_cap=16, frame_cap=4)
     assert rc == 0 and len(p) == 0 and len(f) == 0
-    emu.sdv_engine_destroy(eng)
+    emu_lib.sdv_engine_destroy(eng)
 
 
-def test_emu_empty_and_tiny_inputs(emu, oracle_lib):
-    _empty_and_tiny_inputs(emu, dc.HOST)
+def test_emu_empty_and_tiny_inputs(emu_lib, oracle_lib):
+    _empty_and_tiny_inputs(emu_lib, dc.HOST)
 
 
-def _rejects_what_it_cannot_reproduce(emu, via):
+def _rejects_what_it_cannot_reproduce(emu_lib, via):
     """A line numbered for a later frame in the middle of a frame: the real stitcher pops its queue up to that line and never gets past it
     (more frame reports than the stream has frames until the driver's buffers are full).  The product refuses the stream."""
     recs, st = sc.make_input("ntsc_clean", lambda luma: oracle_binarize(luma, mode=2))
@@ -250,18 +239,18 @@ def _rejects_what_it_cannot_reproduce(emu, via):
         pairs, frames, nf = np.zeros(40000, dtype=sa.PAIR_DTYPE), np.zeros(40, dtype=sa.FRASM_DTYPE), C.c_size_t(0)
         assert f(bad.ctypes.data, len(bad), C.byref(st), pairs.ctypes.data, len(pairs), frames.ctypes.data, len(frames), C.byref(nf)) == -1
         assert nf.value > int((bad["service_type"] == 5).sum()) + 2
-    eng = emu.sdv_engine_create(0)
-    rc, _, _ = via.stitch(emu, eng, bad, st)
-    assert rc == -4 and b"frame" in emu.sdv_last_error(eng)      # SDV_ERR_UNSUPPORTED, loudly
-    emu.sdv_engine_destroy(eng)
-    eng = emu.sdv_engine_create(0)
-    rc, _, _ = via.stitch(emu, eng, recs, st, pair_cap=100)
+    eng = emu_lib.sdv_engine_create(0)
+    rc, _, _ = via.stitch(emu_lib, eng, bad, st)
+    assert rc == -4 and b"frame" in emu_lib.sdv_last_error(eng)      # SDV_ERR_UNSUPPORTED, loudly
+    emu_lib.sdv_engine_destroy(eng)
+    eng = emu_lib.sdv_engine_create(0)
+    rc, _, _ = via.stitch(emu_lib, eng, recs, st, pair_cap=100)
     assert rc == -1                                             # output buffer too small
-    emu.sdv_engine_destroy(eng)
+    emu_lib.sdv_engine_destroy(eng)
 
 
-def test_emu_rejects_what_it_cannot_reproduce(emu, oracle_lib):
-    _rejects_what_it_cannot_reproduce(emu, dc.HOST)
+def test_emu_rejects_what_it_cannot_reproduce(emu_lib, oracle_lib):
+    _rejects_what_it_cannot_reproduce(emu_lib, dc.HOST)
 
 
 # ---------------------------------------------------------------------------------------------------------- GPU

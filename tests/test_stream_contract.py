@@ -557,12 +557,12 @@ def test_gpu_other_device_state_entries(fmt, oracle_lib):
         ctx2.stream.synchronize()
         handover_check(outs, fmt, oracle_lib, gpu_fetch)
         lib = ctx1.lib
-        info = C.create_string_buffer(64)
+        info = ss.ea.StitchInfo()
         for h in ctx1.engines + ctx2.engines:
             assert lib.sdv_reset_stitcher(h) == 0 and on_device_0()
             assert lib.sdv_saturate_pcm16x0_stitch_stats(h) == 0 and on_device_0()
             assert lib.sdv_vis_reset(h, 0, ctx1.s) == 0 and on_device_0()
-            assert lib.sdv_get_stitch_info(h, info) in (0, -1) and on_device_0()
+            assert lib.sdv_get_stitch_info(h, C.byref(info)) in (0, -1) and on_device_0()
             blob(lib, h, lib.sdv_stitch_state_size(), lib.sdv_get_stitch_state)
             assert on_device_0()
     finally:

@@ -54,7 +54,7 @@ def check(emu, orc, seed, ref=None):
 if __name__ == "__main__":
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 300
     ref = libs.load_ref() if len(sys.argv) > 2 and sys.argv[2] == "ref" else None
-    emu = A.bind_product(ea.bind(C.CDLL(b.build_emu())))
+    emu = ea.bind(C.CDLL(b.build_emu()))
     orc = libs.load_oracle()
     res = {}
     for seed in range(1000, 1000 + n):

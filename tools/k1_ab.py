@@ -5,7 +5,7 @@ import ctypes as C, os, sys, statistics
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
-from sdvpcmdecoder_amd import synth
+from sdvpcmdecoder_amd import abi, synth
 reps = int(sys.argv[1]); paths = sys.argv[2:]
 n, W, H = 10000, 720, 486
 luma, _ = synth.stc007_frames_torch(n, seed=2, device="cuda", width=W, height=H, noise_sigma=4.0, cyclic=True)
@@ -13,11 +13,7 @@ recs = torch.empty((n * (H + 3) + 1, 48), dtype=torch.uint8, device="cuda")
 stats = torch.empty((n, 32), dtype=torch.uint8, device="cuda")
 engines = []
 for p in paths:
-    lib = C.CDLL(os.path.abspath(p))
-    lib.sdv_engine_create.restype = C.c_void_p; lib.sdv_engine_create.argtypes = [C.c_int]
-    lib.sdv_binarize_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint,
-                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.sdv_set_mode.argtypes = [C.c_void_p, C.c_int]
+    lib = abi.bind(C.CDLL(os.path.abspath(p)))
     e = C.c_void_p(lib.sdv_engine_create(0)); lib.sdv_set_mode(e, 2)
     def call(first, flags, lib=lib, e=e):
         rc = lib.sdv_binarize_frames(e, luma.data_ptr(), W, W * H, W, H, n, first, flags, recs.data_ptr() + (0 if flags & 1 else 48), recs.shape[0], stats.data_ptr(), n, None)

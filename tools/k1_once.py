@@ -4,17 +4,13 @@ import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
-from sdvpcmdecoder_amd import synth
+from sdvpcmdecoder_amd import abi, synth
 path = sys.argv[1]; calls = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 n, W, H = 10000, 720, 486
 luma, _ = synth.stc007_frames_torch(n, seed=2, device="cuda", width=W, height=H, noise_sigma=4.0, cyclic=True)
 recs = torch.empty((n * (H + 3) + 1, 48), dtype=torch.uint8, device="cuda")
 stats = torch.empty((n, 32), dtype=torch.uint8, device="cuda")
-lib = C.CDLL(os.path.abspath(path))
-lib.sdv_engine_create.restype = C.c_void_p; lib.sdv_engine_create.argtypes = [C.c_int]
-lib.sdv_binarize_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint,
-                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-lib.sdv_set_mode.argtypes = [C.c_void_p, C.c_int]
+lib = abi.bind(C.CDLL(os.path.abspath(path)))
 e = C.c_void_p(lib.sdv_engine_create(0)); lib.sdv_set_mode(e, 2)
 fno = 1
 for i in range(calls + 1):

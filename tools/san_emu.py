@@ -45,7 +45,6 @@ lib.sdv_engine_destroy(eng)
 print("binarize emu (sweeps in small rounds) ok")
 import ctypes as C
 import pcm1_front_api as pf
-lib.sdv_engine_create.restype = C.c_void_p
 for name in ("clean_fast", "cut_bits_draft", "noisy_header", "window_moves", "garbage", "forced_coords"):
     luma1, run = pf.make_case(name)
     seq, _, _ = pf.run_lines(orc, "orc_bin1_", luma1, **run)
@@ -79,7 +78,6 @@ for name in ("si_clean", "si_bad10", "si_picked_forced"):
 print("pcm16x0 stitch emu ok")
 # round 2, SURVEY 8f: AudioProcessor on the emulator (plan with leaps, window chains, emit, WAV packing)
 import audio_api as au
-au.bind_product(lib)
 for name in sorted(au.CASES):
     pairs, mode, ends, stop = au.make_input(name)
     want = au.run_cpu(orc, "orc_", pairs, mode, ends, stop)
