@@ -23,21 +23,26 @@
  *       captured frames as the video decoder delivers them (pixfmt: gray8 uyvy422 yuyv422 v210 gray10le rgb24 bgr24 rgb0 bgr0; rows
  *       src_row_stride bytes apart, frames src_h rows apart) -> sdv_ingest_frames: crop, channel, 8-bit luma, 2x doubling -> the plane the
  *       other modes read (and, on the device, the plane the frame entries take); prints `out_w out_h doubled`
- *   decode_tape encode <in.wav> <out.luma> [pal] [16] [noctrl] [emphasis] [nocopy] [from44100] [preemph]
+ *   decode_tape encode <in.wav> <out.luma> [pal] [16] [noctrl] [emphasis] [nocopy] [from44100] [preemph] [<pixfmt>]
  *       the way back: a 16-bit stereo PCM WAV file -> sdv_encode_frames -> 8-bit luma frames of an STC-007 tape (`16`: PCM-F1, 16 bit) as the
  *       other modes read them: 720 pixels wide, data window 12 .. 708, every line of both fields (NTSC 492 rows, PAL 590; with `noctrl`, without
  *       the control line, 490 / 588), top field first, black 30, white 200.  One frame more than the samples fill is made from no pairs: it plays
  *       the 112 lines of interleave delay out.  `emphasis` and `nocopy` set the bits of the control block (`emphasis` alone leaves the samples as they are).
- *       Prints `n_frames width height`; `decode_tape wav <out.luma> 720 <height> <n_frames> <back.wav>` gives the samples back.
+ *       Prints `n_frames width height row_bytes`; `decode_tape wav <out.luma> 720 <height> <n_frames> <back.wav>` gives the samples back.
+ *       <pixfmt>, one of uyvy422 yuyv422 v210 gray10le rgb24 bgr24 rgb0 bgr0: the frames leave the encoder in that packed format (out_fmt of the
+ *       descriptor) with neutral chroma, as a playout card or a video encoder takes them: rows of row_bytes bytes with no padding, row_bytes being
+ *       the fourth number printed - the stride for the next tool.  `decode_tape ingest <out> <pixfmt> 720 <height> <row_bytes> <n_frames> 0,0,0,0
+ *       bw off <luma>` is the way back to the plane `wav` and `frames` read
  *       `from44100`: the file is an ordinary 44 100 Hz WAV and the tape runs at 44 056 Hz - its pairs are resampled before anything else
  *       (sdv_pcm_resample, one call, flush = 1); a usage error with `pal`, whose tape runs at 44 100 Hz.  `preemph`: the pairs are pre-emphasised at
  *       the tape's rate (sdv_pcm_preemphasis; 44 056 Hz, with `pal` 44 100 Hz) and the emphasis bit is set; `clipped N` on stderr says how many samples
  *       that clipped.  `16 from44100 preemph`, then `decode_tape wav ... force 44100`, gives a 44 100 Hz file back
- *   decode_tape encode <in.wav> <out.luma> pcm1|pcm16si|pcm16ei [bff] [emphasis] [44100] [from44100] [preemph]
+ *   decode_tape encode <in.wav> <out.luma> pcm1|pcm16si|pcm16ei [bff] [emphasis] [44100] [from44100] [preemph] [<pixfmt>]
  *       the same for the marker-less formats: -> sdv_encode_markerless_frames -> frames of a PCM-1 tape (492 rows: one Header line and the 245
  *       data lines of either field) or of a PCM-1630 tape in the SI or EI interleave (490 rows), 720 pixels wide, data window 4 .. 716, black 30,
  *       white 200, top field first or, with `bff`, bottom field first.  `emphasis` and `44100` set Control Bits of a PCM-16x0 tape (without
- *       `44100` it says 44 056 Hz).  As many frames as the samples fill, the rest of the last one silence.  Prints `n_frames width height`.
+ *       `44100` it says 44 056 Hz).  As many frames as the samples fill, the rest of the last one silence.  Prints `n_frames width height
+ *       row_bytes`; <pixfmt> as above.
  *       `from44100` and `preemph` as above: the tape's rate is 44 056 Hz, or 44 100 Hz for PCM-16x0 with `44100` (with which `from44100` is a usage
  *       error); `preemph` sets the emphasis Control Bit of a PCM-16x0 tape - a PCM-1 tape has none, only its samples change
  *   decode_tape frames <luma.raw> <width> <height> <n_frames> pcm1|pcm16si|pcm16ei tff|bff <pairs.out>
@@ -57,6 +62,14 @@
 
 #define HIP_OK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); return 2; } } while (0)
 #define SDV_OKAY(x) do { int r_ = (x); if (r_ != SDV_OK) { fprintf(stderr, "%s = %d: %s\n", #x, r_, sdv_last_error(eng)); return 3; } } while (0)
+
+/* an option of `encode` that names an output pixel format: its SDV_PIX_* value, or -1 */
+static int encode_pix_fmt(const std::string &opt)
+{
+    static const char *const fmts[] = { "gray8", "uyvy422", "yuyv422", "v210", "gray10le", "rgb24", "bgr24", "rgb0", "bgr0" };
+    for (int i = 1; i < 9; i++) if (opt == fmts[i]) return i;
+    return -1;
+}
 
 static bool read_file(const char *path, std::vector<uint8_t> &out)
 {
@@ -340,12 +353,13 @@ int main(int argc, char **argv)
             else if (opt == "44100" && !pcm1) d.ctrl_flags |= SDV_ENC_ML_RATE_44100;
             else if (opt == "from44100") from44100 = true;
             else if (opt == "preemph") { preemph = true; if (!pcm1) d.ctrl_flags |= SDV_ENC_ML_EMPHASIS; }
+            else if (encode_pix_fmt(opt) > 0) d.out_fmt[0] = (uint8_t)encode_pix_fmt(opt);
             else { fprintf(stderr, "usage: see the header of examples/decode_tape.cpp\n"); return 1; }
         }
         if (from44100 && (d.ctrl_flags & SDV_ENC_ML_RATE_44100)) { fprintf(stderr, "usage: from44100 is for a tape that runs at 44 056 Hz (see the header of examples/decode_tape.cpp)\n"); return 1; }
-        size_t per_frame = 0; int lines_per_field = 0;
+        size_t per_frame = 0, row_bytes = 0; int lines_per_field = 0;
         d.height = 2;                       /* (any: the geometry tells the lines of a field, the height follows from them) */
-        const int grc = sdv_encode_markerless_geometry(&d, &per_frame, &lines_per_field, NULL);
+        const int grc = sdv_encode_markerless_geometry(&d, &per_frame, &lines_per_field, &row_bytes);
         if (grc != SDV_OK) { fprintf(stderr, "sdv_encode_markerless_geometry = %d: %s\n", grc, sdv_last_error(NULL)); return 3; }
         d.height = 2 * lines_per_field;
         size_t data_at = 0, n_in = 0;
@@ -355,12 +369,12 @@ int main(int argc, char **argv)
         HIP_OK(hipMemcpy(d_pcm, in.data() + data_at, n_in * 4, hipMemcpyHostToDevice));
         { const int crc = condition_pcm(eng, &d_pcm, &n_in, from44100, preemph, (d.ctrl_flags & SDV_ENC_ML_RATE_44100) ? 44100 : 44056); if (crc) return crc; }
         const int n = n_in ? (int)((n_in + per_frame - 1) / per_frame) : 1;     /* (no delay to play out: a frame is made from its own pairs) */
-        const size_t frame_bytes = (size_t)d.width * d.height;
+        const size_t frame_bytes = row_bytes * (size_t)d.height;       /* rows of row_bytes, no padding */
         HIP_OK(hipMalloc((void **)&d_luma, frame_bytes * n));
-        SDV_OKAY(sdv_encode_markerless_frames(eng, &d, d_pcm, n_in, n, d_luma, (size_t)d.width, frame_bytes, NULL));
+        SDV_OKAY(sdv_encode_markerless_frames(eng, &d, d_pcm, n_in, n, d_luma, row_bytes, frame_bytes, NULL));
         HIP_OK(hipDeviceSynchronize());
         rc = download(d_luma, frame_bytes * n, argv[3]);
-        printf("%d %d %d\n", n, d.width, d.height);
+        printf("%d %d %d %zu\n", n, d.width, d.height, row_bytes);
         (void)hipFree(d_pcm); (void)hipFree(d_luma);
     } else if (mode == "encode" && argc >= 4) {
         sdv_encode_desc d; memset(&d, 0, sizeof(d));
@@ -375,12 +389,13 @@ int main(int argc, char **argv)
             else if (opt == "nocopy") d.ctrl_flags |= SDV_ENC_CTRL_COPY_PROHIBITED;
             else if (opt == "from44100") from44100 = true;
             else if (opt == "preemph") { preemph = true; d.ctrl_flags |= SDV_ENC_CTRL_EMPHASIS; }
+            else if (encode_pix_fmt(opt) > 0) d.out_fmt[0] = (uint8_t)encode_pix_fmt(opt);
             else { fprintf(stderr, "usage: see the header of examples/decode_tape.cpp\n"); return 1; }
         }
         if (from44100 && d.video_standard == SDV_ENC_PAL) { fprintf(stderr, "usage: from44100 is for a tape that runs at 44 056 Hz (see the header of examples/decode_tape.cpp)\n"); return 1; }
-        size_t per_frame = 0; int lines_per_field = 0;
+        size_t per_frame = 0, row_bytes = 0; int lines_per_field = 0;
         d.height = 2;                       /* (any: the geometry tells the lines of a field, the height follows from them) */
-        const int grc = sdv_encode_geometry(&d, &per_frame, &lines_per_field, NULL);
+        const int grc = sdv_encode_geometry(&d, &per_frame, &lines_per_field, &row_bytes);
         if (grc != SDV_OK) { fprintf(stderr, "sdv_encode_geometry = %d: %s\n", grc, sdv_last_error(NULL)); return 3; }
         d.height = 2 * lines_per_field;
         size_t data_at = 0, n_in = 0;
@@ -390,12 +405,12 @@ int main(int argc, char **argv)
         HIP_OK(hipMemcpy(d_pcm, in.data() + data_at, n_in * 4, hipMemcpyHostToDevice));
         { const int crc = condition_pcm(eng, &d_pcm, &n_in, from44100, preemph, d.video_standard == SDV_ENC_PAL ? 44100 : 44056); if (crc) return crc; }
         const int n = (int)((n_in + per_frame - 1) / per_frame) + 1;          /* ... and the frame that plays the delay out */
-        const size_t frame_bytes = (size_t)d.width * d.height;
+        const size_t frame_bytes = row_bytes * (size_t)d.height;       /* rows of row_bytes, no padding */
         HIP_OK(hipMalloc((void **)&d_luma, frame_bytes * n));
-        SDV_OKAY(sdv_encode_frames(eng, &d, d_pcm, n_in, n, d_luma, (size_t)d.width, frame_bytes, NULL));
+        SDV_OKAY(sdv_encode_frames(eng, &d, d_pcm, n_in, n, d_luma, row_bytes, frame_bytes, NULL));
         HIP_OK(hipDeviceSynchronize());
         rc = download(d_luma, frame_bytes * n, argv[3]);
-        printf("%d %d %d\n", n, d.width, d.height);
+        printf("%d %d %d %zu\n", n, d.width, d.height, row_bytes);
         (void)hipFree(d_pcm); (void)hipFree(d_luma);
     } else { fprintf(stderr, "usage: see the header of examples/decode_tape.cpp\n"); rc = 1; }
     if (d_pairs) (void)hipFree(d_pairs);

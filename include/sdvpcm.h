@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define SDV_ABI_VERSION 11  /* 2: output capacities on sdv_binarize_frames / sdv_pcm1_binarize_lines; 3: sdv_audio_process, sdv_wav_pack, sdv_wav_header, sdv_decode_frames (additions only);
+#define SDV_ABI_VERSION 12  /* 2: output capacities on sdv_binarize_frames / sdv_pcm1_binarize_lines; 3: sdv_audio_process, sdv_wav_pack, sdv_wav_header, sdv_decode_frames (additions only);
                              * 4: sdv_pcm16x0_binarize_lines, sdv_audio_stalled, sdv_set_frame_flags, sdv_double_width, sdv_vis_render_lines (additions); the calls that used to refuse PCM-16x0 frames of the wrong size and the
                              * AudioProcessor's dead ends now follow the reference; the PCM-16x0 stitch state blob grew by conv_queue's remainder;
                              * 5: sdv_run_info grew by frames_met (at its end), sdv_binarize_lines (addition);
@@ -30,7 +30,9 @@ extern "C" {
                              * 9: sdv_encode_geometry, sdv_encode_frames, sdv_reset_encoder (additions only);
                              * 10: sdv_encode_markerless_geometry, sdv_encode_markerless_frames (additions only);
                              * 11: sdv_preemphasis_coeffs, sdv_reset_preemphasis, sdv_pcm_preemphasis, sdv_pcm_preemphasis_clipped, sdv_pcm_resample_taps, sdv_reset_pcm_resample,
-                             * sdv_pcm_resample_pending, sdv_pcm_resample_room, sdv_pcm_resample (additions only) */
+                             * sdv_pcm_resample_pending, sdv_pcm_resample_room, sdv_pcm_resample (additions only);
+                             * 12: out_fmt in sdv_encode_desc and sdv_encode_markerless_desc, in bytes that were padding (0, SDV_PIX_GRAY8, is what they meant); *row_bytes of
+                             * the two geometry calls follows it */
 
 /* ---- status codes ---------------------------------------------------------------------------
  * 0..4 mirror Binarizer::LB_RET_* (binarizer.h:268-275); 16.. mirror STC007Deinterleaver::DI_RET_*
@@ -404,21 +406,38 @@ int sdv_ingest_frames(sdv_engine *e, const sdv_ingest_desc *d, const void *src, 
  *   lines_per_field) is `black` throughout, and so is the last row of an odd height.
  * Raster.  Pixel x of a line's row is `white` where data_start <= x < data_stop and cell ((x - data_start) * 137) / (data_stop - data_start)
  *   (integer division) is 1, else `black`.  The window may reach past the picture on either side.
+ * Output format.  out_fmt[0] is an SDV_PIX_* value, the enum of sdv_ingest_desc::pix_fmt; out_fmt[1] and out_fmt[2] are reserved and must be 0.
+ *   SDV_PIX_GRAY8 (0, what a zeroed descriptor says) writes the raster as it stands above, a byte a pixel.  Any other value writes the same
+ *   `width` luma values y[x] of every row - `black`, `white`, or `black` throughout for a row without a line - in the packing sdv_ingest_frames
+ *   unpacks, with neutral chroma and an opaque fourth byte; there is nothing to choose, this is a luma signal.  Bytes of a row (*row_bytes), w = width:
+ *     SDV_PIX_UYVY422    4 ceil(w / 2): per pixel pair 128, y[2 i], 128, y[2 i + 1]
+ *     SDV_PIX_YUYV422    4 ceil(w / 2): y[2 i], 128, y[2 i + 1], 128
+ *     SDV_PIX_V210       16 ceil(w / 6): groups of four little-endian 32-bit words; component c = 0 .. 11 sits at bits 10 (c % 3) of word c / 3; luma j
+ *                        of the group is component 2 j + 1 with the value y << 2, every chroma component is 512, bits 30 and 31 of every word are 0
+ *     SDV_PIX_GRAY10LE   2 w: little-endian 16-bit y << 2
+ *     SDV_PIX_RGB24, SDV_PIX_BGR24   3 w: y, y, y;  SDV_PIX_RGB0, SDV_PIX_BGR0   4 w: y, y, y, 255
+ *   Pixels that the last pair (odd w) or the last v210 group (w % 6 != 0) holds beyond `width` are `black`.  So sdv_ingest_frames of the result with
+ *   the same format, SDV_COLOR_BW, no crop and no doubling is the SDV_PIX_GRAY8 output: (77 + 150 + 29) y + 128 >> 8 = y, (y << 2) >> 2 = y.
+ *   Not offered: planar 4:2:0 / 4:2:2 (the luma plane is the SDV_PIX_GRAY8 call, the chroma planes a fill with 128), studio-range scaling (`black`
+ *   and `white` are the caller's levels), blanking or sync.
  *
  * State.  The engine keeps the words of the tape's last 112 blocks and the field count on the device, updated in stream order (the calls of a
  * tape go to one HIP stream): a tape encoded in several calls equals the tape encoded in one.  sdv_engine_create and sdv_reset_encoder start a
  * new tape.  video_standard, resolution and ctrl_block stay as they were in the first call after a reset (else SDV_ERR_BAD_ARG); geometry,
- * levels, field order, tc_index and ctrl_flags may change from call to call.
+ * levels, field order, tc_index, ctrl_flags and out_fmt may change from call to call; the state does not depend on out_fmt.
  *
  * sdv_encode_frames: device pointers of any alignment; all work goes to `stream`, the call is asynchronous and reads nothing back; it runs on
- * the engine's device whatever device is current.  Row r of frame f goes to dst + f dst_frame_stride + r dst_row_stride, `width` bytes.  Bytes of
- * a row behind `width`, and anything else in the buffer, are not written.  Refused before any launch, the engine and the tape untouched,
- * sdv_last_error says why: SDV_ERR_BAD_ARG for a null d, an unknown enum value or control bit, n_frames < 0 or above 2^24, width or height outside
- * 1 .. 32768, data_stop <= data_start, white <= black, a time-code field out of range (tc_index 0 .. 63, tc_hour 0 .. 15, tc_minute and tc_second
- * 0 .. 59, tc_field below 60 / 50), dst_row_stride < width, dst_frame_stride < (height - 1) dst_row_stride + width when n_frames > 1, strides
- * above 4 GiB, any overlap of the pairs the call reads with the destination span; SDV_ERR_NULL_PCM for a null pcm with n_pairs > 0;
- * SDV_ERR_NULL_VIDEO for a null dst.  n_frames == 0: SDV_OK, nothing done.  sdv_encode_geometry is host-only and needs no engine: the same codes for
- * the same descriptor (sdv_last_error(NULL) says why); any of its output pointers may be NULL; *row_bytes = width. */
+ * the engine's device whatever device is current.  Row r of frame f goes to dst + f dst_frame_stride + r dst_row_stride, *row_bytes bytes
+ * (`width` for SDV_PIX_GRAY8, else the value of the table above).  Bytes of a row behind *row_bytes, and anything else in the buffer, are not
+ * written.  Refused before any launch, the engine, the tape and the destination untouched, sdv_last_error says why: SDV_ERR_BAD_ARG for a null
+ * d, an unknown enum value or control bit, an out_fmt[0] that is no SDV_PIX_* value or a reserved out_fmt byte that is not 0, n_frames < 0 or
+ * above 2^24, width or height outside 1 .. 32768, data_stop <= data_start, white <= black, a time-code field out of range (tc_index 0 .. 63,
+ * tc_hour 0 .. 15, tc_minute and tc_second 0 .. 59, tc_field below 60 / 50), dst_row_stride < *row_bytes (a stride of `width` is too small for
+ * SDV_PIX_UYVY422), dst_frame_stride < (height - 1) dst_row_stride + *row_bytes when n_frames > 1, strides above 4 GiB, any overlap of the pairs
+ * the call reads with the destination span, (n_frames - 1) dst_frame_stride + (height - 1) dst_row_stride + *row_bytes bytes from dst;
+ * SDV_ERR_NULL_PCM for a null pcm with n_pairs > 0; SDV_ERR_NULL_VIDEO for a null dst.  n_frames == 0: SDV_OK, nothing done.
+ * sdv_encode_geometry is host-only and needs no engine: the same codes for the same descriptor (sdv_last_error(NULL) says why); any of its
+ * output pointers may be NULL; *row_bytes is the bytes of a row for the descriptor's width and out_fmt. */
 enum { SDV_ENC_NTSC = 0, SDV_ENC_PAL = 1 };
 enum { SDV_ENC_14BIT = 0, SDV_ENC_16BIT = 1 };
 enum { SDV_ENC_TFF = 0, SDV_ENC_BFF = 1 };
@@ -426,7 +445,7 @@ enum { SDV_ENC_CTRL_COPY_PROHIBITED = 1 << 0, SDV_ENC_CTRL_EMPHASIS = 1 << 1 };
 typedef struct sdv_encode_desc {
     uint8_t video_standard, resolution, ctrl_block, ctrl_flags;     /* SDV_ENC_NTSC / _PAL, SDV_ENC_14BIT / _16BIT, 0 / 1, SDV_ENC_CTRL_* */
     uint8_t field_order, black, white, _pad;                        /* SDV_ENC_TFF / _BFF; the two levels */
-    uint8_t tc_index, tc_hour, tc_minute, tc_second, tc_field, _pad2[3];
+    uint8_t tc_index, tc_hour, tc_minute, tc_second, tc_field, out_fmt[3];     /* out_fmt[0]: SDV_PIX_*, 0 = SDV_PIX_GRAY8; the rest 0 */
     int32_t width, height, data_start, data_stop, top_line;
 } sdv_encode_desc;                                                   /* 36 bytes */
 int sdv_encode_geometry(const sdv_encode_desc *d, size_t *pairs_per_frame, int *lines_per_field, size_t *row_bytes);
@@ -467,22 +486,26 @@ int sdv_reset_encoder(sdv_engine *e);
  * Frame.  lines_per_field = 245 + header_lines.  Rows, field order, top_line and the rows without a line are those of sdv_encode_frames.
  * Raster.  As for sdv_encode_frames with the format's cell count: pixel x is `white` where data_start <= x < data_stop and cell
  *   ((x - data_start) * CELLS) / (data_stop - data_start) is 1, CELLS = 94 (PCM-1) or 193 (PCM-16x0), else `black`.
+ * Output format.  out_fmt[0] is an SDV_PIX_* value and out_fmt[1] is reserved and must be 0, with the meaning, the packings, the bytes of a row
+ *   and the black pixels behind `width` of sdv_encode_frames' out_fmt; 0, SDV_PIX_GRAY8, is the raster as it stands above.
  *
  * State.  None: a tape made in several calls equals the tape made in one, given calls that start on frame boundaries of the PCM.  The tape of
  * sdv_encode_frames is neither read nor written; sdv_reset_encoder has nothing to do with these calls.
  *
  * sdv_encode_markerless_frames: the contract of sdv_encode_frames - device pointers of any alignment, all work on `stream`, asynchronous, nothing
- * read back, on the engine's device whatever device is current, only the `width` bytes of every row written - and its refusals, before any launch
- * and with the destination untouched: SDV_ERR_BAD_ARG for a null d, an unknown format, field order or control bit, n_frames < 0 or above 2^24,
- * width or height outside 1 .. 32768, data_stop <= data_start, white <= black, the strides and the overlap as there; SDV_ERR_NULL_PCM,
- * SDV_ERR_NULL_VIDEO.  Also SDV_ERR_BAD_ARG: header_lines > 8; header_lines != 0 with a PCM-16x0 format; ctrl_flags != 0 with PCM-1.
+ * read back, on the engine's device whatever device is current, only the *row_bytes bytes of every row written - and its refusals, before any
+ * launch and with the destination untouched: SDV_ERR_BAD_ARG for a null d, an unknown format, field order or control bit, an out_fmt[0] that is
+ * no SDV_PIX_* value or an out_fmt[1] that is not 0, n_frames < 0 or above 2^24, width or height outside 1 .. 32768, data_stop <= data_start,
+ * white <= black, the strides and the overlap as there, with *row_bytes for the bytes of a row; SDV_ERR_NULL_PCM, SDV_ERR_NULL_VIDEO.  Also
+ * SDV_ERR_BAD_ARG: header_lines > 8; header_lines != 0 with a PCM-16x0 format; ctrl_flags != 0 with PCM-1.  out_fmt may change from call to call.
  * n_frames == 0: SDV_OK, nothing done.  sdv_encode_markerless_geometry is host-only and needs no engine: the same codes for the same descriptor;
- * *pairs_per_frame = 1470, *lines_per_field = 245 + header_lines, *row_bytes = width; any of the three may be NULL. */
+ * *pairs_per_frame = 1470, *lines_per_field = 245 + header_lines, *row_bytes the bytes of a row for the width and out_fmt; any of the three may
+ * be NULL. */
 enum { SDV_ENC_FMT_PCM1 = 0, SDV_ENC_FMT_PCM16X0_SI = 1, SDV_ENC_FMT_PCM16X0_EI = 2 };
 enum { SDV_ENC_ML_EMPHASIS = 1 << 0, SDV_ENC_ML_RATE_44100 = 1 << 1, SDV_ENC_ML_CODE = 1 << 2 };   /* PCM-16x0 Control Bits */
 typedef struct sdv_encode_markerless_desc {
     uint8_t format, field_order, black, white;        /* SDV_ENC_FMT_*, SDV_ENC_TFF / _BFF, the two levels */
-    uint8_t header_lines, ctrl_flags, _pad[2];        /* PCM-1: 0 .. 8 Header lines on top of every field; PCM-16x0: SDV_ENC_ML_* */
+    uint8_t header_lines, ctrl_flags, out_fmt[2];     /* PCM-1: 0 .. 8 Header lines on top of every field; PCM-16x0: SDV_ENC_ML_*; out_fmt[0]: SDV_PIX_*, the rest 0 */
     int32_t width, height, data_start, data_stop, top_line;
 } sdv_encode_markerless_desc;                         /* 28 bytes */
 int sdv_encode_markerless_geometry(const sdv_encode_markerless_desc *d, size_t *pairs_per_frame, int *lines_per_field, size_t *row_bytes);

@@ -102,12 +102,12 @@ class IngestDesc(C.Structure):
 class EncodeDesc(C.Structure):
     """sdv_encode_desc"""
     _fields_ = _f(u8, "video_standard resolution ctrl_block ctrl_flags field_order black white _pad tc_index tc_hour tc_minute tc_second tc_field") + \
-        [("_pad2", u8 * 3)] + _f(i32, "width height data_start data_stop top_line")
+        [("out_fmt", u8 * 3)] + _f(i32, "width height data_start data_stop top_line")
 
 
 class EncodeMarkerlessDesc(C.Structure):
     """sdv_encode_markerless_desc"""
-    _fields_ = _f(u8, "format field_order black white header_lines ctrl_flags") + [("_pad", u8 * 2)] + _f(i32, "width height data_start data_stop top_line")
+    _fields_ = _f(u8, "format field_order black white header_lines ctrl_flags") + [("out_fmt", u8 * 2)] + _f(i32, "width height data_start data_stop top_line")
 
 
 class StitchInfo(C.Structure):
@@ -221,7 +221,7 @@ ASM_LINE_DTYPE = np.dtype(AsmLineRec)
 
 
 # ---- constants: the header's enums and #defines without the SDV_ prefix ----------------------------------------------------------------
-ABI_VERSION = 11
+ABI_VERSION = 12
 OK, ERR_NULL_VIDEO, ERR_NULL_PCM, ERR_SHORT_LINE, ERR_NO_COORD, ERR_NULL_LINES, ERR_NULL_BLOCK, ERR_NO_DATA = 0, 1, 2, 3, 4, 16, 17, 18
 ERR_BAD_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED = -1, -2, -3, -4
 PCM_PCM1, PCM_PCM16X0, PCM_STC007 = 0, 1, 2

@@ -32,6 +32,7 @@ KERNEL_SOURCES = {
     "sdv_k_resample": ("audio_device.h", "audio_resample_device.h", "audio_engine.inc"),
     "sdv_k_ingest": ("ingest_device.h", "ingest_engine.inc"),
     "sdv_k_encode": ("encode_device.h", "encode_engine.inc"),
+    "sdv_k_encode_raster_packed": ("encode_device.h", "encode_packed_device.h", "encode_engine.inc"),
     "sdv_k_mlenc": ("encode_device.h", "encode_markerless_device.h", "encode_engine.inc", "encode_markerless_engine.inc"),
     "sdv_k_preemph": ("pcm_preemph_device.h", "pcm_condition_engine.inc"),
     "sdv_k_pcmrs": ("pcm_preemph_device.h", "pcm_resample_device.h", "pcm_condition_engine.inc"),

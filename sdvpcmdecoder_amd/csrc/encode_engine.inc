@@ -1,7 +1,8 @@
 /*
  * encode_engine.inc - host side of sdv_encode_geometry / sdv_encode_frames / sdv_reset_encoder (include/sdvpcm.h): the checks, the tape's
  * state and the two launches of encode_device.h.  Included at the end of engine.inc, so by the one translation unit of either build.
- * encode_check_buffers and encode_launch_raster also serve encode_markerless_engine.inc.
+ * encode_out_fmt, encode_check_buffers and encode_launch_raster also serve encode_markerless_engine.inc; encode_launch_raster is the one place that
+ * chooses between sdv_k_encode_raster (SDV_PIX_GRAY8) and a build of sdv_k_encode_raster_packed (encode_packed_device.h).
  */
 
 enum { ENCODE_MAX_DIM = 32768, ENCODE_MAX_FRAMES = 1 << 24 };
@@ -16,7 +17,24 @@ struct sdv_encoder {
 
 static void encoder_free(sdv_engine *e) { delete e->enc; e->enc = NULL; }
 
-struct EncodeGeo { int lpf, lpft; uint32_t fps; };
+/* out_fmt of a descriptor (`n` bytes, the first an SDV_PIX_* value, the rest reserved) for rows of `width` pixels: the bytes of a row, or why not */
+static int encode_out_fmt(const uint8_t *out_fmt, int n, int width, size_t *row_bytes, std::string *why)
+{
+    if (out_fmt[0] > SDV_PIX_BGR0) { *why = "unknown output pixel format (out_fmt[0] is an SDV_PIX_* value)"; return SDV_ERR_BAD_ARG; }
+    for (int i = 1; i < n; i++) if (out_fmt[i]) { *why = "the reserved bytes of out_fmt are not 0"; return SDV_ERR_BAD_ARG; }
+    const size_t w = (size_t)width;
+    switch (out_fmt[0]) {
+    case SDV_PIX_GRAY8: *row_bytes = w; break;
+    case SDV_PIX_UYVY422: case SDV_PIX_YUYV422: *row_bytes = 4 * ((w + 1) / 2); break;
+    case SDV_PIX_V210: *row_bytes = 16 * ((w + 5) / 6); break;
+    case SDV_PIX_GRAY10LE: *row_bytes = 2 * w; break;
+    case SDV_PIX_RGB24: case SDV_PIX_BGR24: *row_bytes = 3 * w; break;
+    default: *row_bytes = 4 * w; break;                 /* SDV_PIX_RGB0, SDV_PIX_BGR0 */
+    }
+    return SDV_OK;
+}
+
+struct EncodeGeo { int lpf, lpft; uint32_t fps; size_t row_bytes; };
 
 /* what the descriptor asks for, or why it cannot be had */
 static int encode_geo(const sdv_encode_desc *d, EncodeGeo *g, std::string *why)
@@ -36,20 +54,20 @@ static int encode_geo(const sdv_encode_desc *d, EncodeGeo *g, std::string *why)
     g->lpft = g->lpf + d->ctrl_block;
     g->fps = d->video_standard == SDV_ENC_PAL ? 50 : 60;
     if (d->tc_index > 63 || d->tc_hour > 15 || d->tc_minute > 59 || d->tc_second > 59 || d->tc_field >= g->fps) { *why = "time code out of range"; return SDV_ERR_BAD_ARG; }
-    return SDV_OK;
+    return encode_out_fmt(d->out_fmt, 3, d->width, &g->row_bytes, why);
 }
 
-/* The pointers and strides of a call that makes n_frames frames of width x height from at most call_pairs pairs - the checks of sdv_encode_frames
- * and sdv_encode_markerless_frames behind those of their descriptors.  *used_pairs: the pairs the call reads. */
-static int encode_check_buffers(sdv_engine *e, int width, int height, const int16_t *pcm, size_t n_pairs, uint64_t call_pairs, int n_frames,
+/* The pointers and strides of a call that makes n_frames frames of `height` rows of row_bytes bytes (the out_fmt's) from at most call_pairs pairs -
+ * the checks of sdv_encode_frames and sdv_encode_markerless_frames behind those of their descriptors.  *used_pairs: the pairs the call reads. */
+static int encode_check_buffers(sdv_engine *e, size_t row_bytes, int height, const int16_t *pcm, size_t n_pairs, uint64_t call_pairs, int n_frames,
                                 const uint8_t *dst, size_t dst_row_stride, size_t dst_frame_stride, size_t *used_pairs)
 {
     if (!pcm && n_pairs > 0) { set_error(e, "null pcm"); return SDV_ERR_NULL_PCM; }
     if (!dst) { set_error(e, "null video"); return SDV_ERR_NULL_VIDEO; }
     const size_t max_stride = (size_t)1 << 32;          /* (keeps the spans below inside 64 bits) */
     if (dst_row_stride > max_stride || (n_frames > 1 && dst_frame_stride > max_stride)) { set_error(e, "stride above 4 GiB"); return SDV_ERR_BAD_ARG; }
-    const size_t dst_frame = (size_t)(height - 1) * dst_row_stride + (size_t)width;
-    if (dst_row_stride < (size_t)width) { set_error(e, "dst_row_stride smaller than the " + std::to_string(width) + " bytes of a row"); return SDV_ERR_BAD_ARG; }
+    const size_t dst_frame = (size_t)(height - 1) * dst_row_stride + row_bytes;
+    if (dst_row_stride < row_bytes) { set_error(e, "dst_row_stride smaller than the " + std::to_string(row_bytes) + " bytes of a row"); return SDV_ERR_BAD_ARG; }
     if (n_frames > 1 && dst_frame_stride < dst_frame) { set_error(e, "dst_frame_stride smaller than one frame"); return SDV_ERR_BAD_ARG; }
     *used_pairs = n_pairs < call_pairs ? n_pairs : (size_t)call_pairs;
     const uintptr_t s0 = (uintptr_t)pcm, s1 = s0 + 4 * *used_pairs;
@@ -59,9 +77,20 @@ static int encode_check_buffers(sdv_engine *e, int width, int height, const int1
 }
 
 /* what the raster shows: the packed lines and the cell table of `t`, lpft lines a field with `cells` cells each */
-struct EncodeRaster { int width, height, top_line, lpft, cells; int64_t span; bool bff; uint8_t black, white; };
+struct EncodeRaster { int width, height, top_line, lpft, cells; int64_t span; bool bff; uint8_t black, white; uint8_t out_fmt; size_t row_bytes; };
 
-/* the raster launch of a call (encode_raster_body): the same for every format */
+/* the build of sdv_k_encode_raster_packed for a format family: `threads` threads, a grid stride walks the rest (encode_packed_body) */
+template <int FAM> static inline rt::status_t launch_encode_packed(sdv::EncodePackedArgs &p, uint64_t rows, rt::stream_t s)
+{
+    sdv::EncodeRasterArgs &a = p.r;
+    a.slots = sdv::EncodePackedShape<FAM>::slots(a.width);
+    const uint32_t threads = rt::grid_stride_threads(rows * (uint64_t)a.slots);
+    const rt::StrideSteps st = rt::stride_steps(threads, (uint32_t)a.height, (uint32_t)a.slots);
+    a.step_f = st.step_f; a.step_r = st.step_r; a.step_c = st.step_c;
+    return RT_LAUNCH_ITEMS((sdv_k_encode_raster_packed<FAM>), (sdv::encode_packed_body<FAM>), 0u, threads, 256, s, p);
+}
+
+/* the raster launch of a call: the same for every tape format; SDV_PIX_GRAY8 by encode_raster_body, any other out_fmt by its family's encode_packed_body */
 static int encode_launch_raster(sdv_engine *e, sdv_encoder *t, const EncodeRaster &r, int n_frames, uint8_t *dst, size_t dst_row_stride, size_t dst_frame_stride,
                                 rt::stream_t s)
 {
@@ -75,6 +104,22 @@ static int encode_launch_raster(sdv_engine *e, sdv_encoder *t, const EncodeRaste
     a.black4 = 0x01010101u * r.black; a.white4 = 0x01010101u * r.white;
     /* cells 15 pixels apart are at most 15 * cells / span, rounded up, apart, and a step more at a window edge: beyond 31 the raster's window does not hold them */
     a.narrow = (15 * (int64_t)r.cells) / r.span + 2 > 31;
+    if (r.out_fmt != SDV_PIX_GRAY8) {
+        sdv::EncodePackedArgs p;
+        p.r = a; p.row_bytes = (uint32_t)r.row_bytes;
+        p.narrow_quad = ((sdv::ENCP_QUAD_PX - 1) * (int64_t)r.cells) / r.span + 2 > 31;         /* the same rule for the 64 pixels the lanes of a quad share */
+        const uint64_t rows = (uint64_t)n_frames * (uint64_t)r.height;
+        switch (r.out_fmt) {
+        case SDV_PIX_UYVY422: RT_CHECK(launch_encode_packed<sdv::ENCP_UYVY>(p, rows, s)); break;
+        case SDV_PIX_YUYV422: RT_CHECK(launch_encode_packed<sdv::ENCP_YUYV>(p, rows, s)); break;
+        case SDV_PIX_V210: RT_CHECK(launch_encode_packed<sdv::ENCP_V210>(p, rows, s)); break;
+        case SDV_PIX_GRAY10LE: RT_CHECK(launch_encode_packed<sdv::ENCP_GRAY10>(p, rows, s)); break;
+        case SDV_PIX_RGB24: case SDV_PIX_BGR24: RT_CHECK(launch_encode_packed<sdv::ENCP_RGB3>(p, rows, s)); break;
+        case SDV_PIX_RGB0: case SDV_PIX_BGR0: RT_CHECK(launch_encode_packed<sdv::ENCP_RGB4>(p, rows, s)); break;
+        default: set_error(e, "no raster kernel for this out_fmt"); return SDV_ERR_BAD_ARG;      /* (encode_out_fmt has refused it) */
+        }
+        return SDV_OK;
+    }
     a.slots = (r.width + 30) / 16;
     /* threads of the raster launch: a grid stride walks the rest (encode_raster_body) */
     const uint32_t threads = rt::grid_stride_threads((uint64_t)n_frames * (uint64_t)r.height * (uint64_t)a.slots);
@@ -93,7 +138,7 @@ int sdv_encode_geometry(const sdv_encode_desc *d, size_t *pairs_per_frame, int *
     if (rc != SDV_OK) { set_error(NULL, "sdv_encode_geometry: " + why); return rc; }
     if (pairs_per_frame) *pairs_per_frame = (size_t)g.lpf * 6;
     if (lines_per_field) *lines_per_field = g.lpft;
-    if (row_bytes) *row_bytes = (size_t)d->width;
+    if (row_bytes) *row_bytes = g.row_bytes;
     return SDV_OK;
 }
 
@@ -116,7 +161,7 @@ int sdv_encode_frames(sdv_engine *e, const sdv_encode_desc *d, const int16_t *pc
     if (rc != SDV_OK) { set_error(e, why); return rc; }
     const uint64_t n_fields = 2 * (uint64_t)n_frames, n_data = n_fields * (uint64_t)g.lpf, n_lines = n_fields * (uint64_t)g.lpft;
     size_t used_pairs = 0;                              /* the pairs the call reads */
-    const int rc_buf = encode_check_buffers(e, d->width, d->height, pcm, n_pairs, 3 * n_data, n_frames, dst, dst_row_stride, dst_frame_stride, &used_pairs);
+    const int rc_buf = encode_check_buffers(e, g.row_bytes, d->height, pcm, n_pairs, 3 * n_data, n_frames, dst, dst_row_stride, dst_frame_stride, &used_pairs);
     if (rc_buf != SDV_OK) return rc_buf;
     sdv_encoder *t = e->enc;
     if (t && !t->fresh && (t->video_standard != d->video_standard || t->resolution != d->resolution || t->ctrl_block != d->ctrl_block)) {
@@ -144,7 +189,7 @@ int sdv_encode_frames(sdv_engine *e, const sdv_encode_desc *d, const int16_t *pc
     const uint64_t word_threads = n_lines + (uint64_t)d->width + 2 * sdv::ENC_TABLE_PAD;      /* a line or an entry of the cell table each */
     RT_CHECK(RT_LAUNCH_ITEMS(sdv_k_encode_words, sdv::encode_words_body, 0, word_threads, 256, s, w));
 
-    const EncodeRaster r = { d->width, d->height, d->top_line, g.lpft, sdv::ENC_CELLS, w.span, d->field_order == SDV_ENC_BFF, d->black, d->white };
+    const EncodeRaster r = { d->width, d->height, d->top_line, g.lpft, sdv::ENC_CELLS, w.span, d->field_order == SDV_ENC_BFF, d->black, d->white, d->out_fmt[0], g.row_bytes };
     const int rc_raster = encode_launch_raster(e, t, r, n_frames, dst, dst_row_stride, dst_frame_stride, s);
     if (rc_raster != SDV_OK) return rc_raster;
 

@@ -1,10 +1,11 @@
 /*
  * encode_markerless_engine.inc - host side of sdv_encode_markerless_geometry / sdv_encode_markerless_frames (include/sdvpcm.h): the checks and the
- * two launches - the format's words kernel of encode_markerless_device.h, then the raster of encode_device.h.  Included at the end of engine.inc behind
+ * two launches - the format's words kernel of encode_markerless_device.h, then the raster of encode_device.h or, for a packed out_fmt, of
+ * encode_packed_device.h.  Included at the end of engine.inc behind
  * encode_engine.inc, whose buffer checks, raster launch and device buffers it uses; the tape state of sdv_encode_frames is neither read nor written.
  */
 
-struct MlencGeo { int cells, lpft; };
+struct MlencGeo { int cells, lpft; size_t row_bytes; };
 
 /* what the descriptor asks for, or why it cannot be had */
 static int mlenc_geo(const sdv_encode_markerless_desc *d, MlencGeo *g, std::string *why)
@@ -24,7 +25,7 @@ static int mlenc_geo(const sdv_encode_markerless_desc *d, MlencGeo *g, std::stri
     if (d->white <= d->black) { *why = "white is not above black"; return SDV_ERR_BAD_ARG; }
     g->cells = pcm1 ? sdv::MLENC_PCM1_CELLS : sdv::MLENC_PCM16_CELLS;
     g->lpft = sdv::MLENC_LINES + d->header_lines;
-    return SDV_OK;
+    return encode_out_fmt(d->out_fmt, 2, d->width, &g->row_bytes, why);
 }
 
 extern "C" {
@@ -36,7 +37,7 @@ int sdv_encode_markerless_geometry(const sdv_encode_markerless_desc *d, size_t *
     if (rc != SDV_OK) { set_error(NULL, "sdv_encode_markerless_geometry: " + why); return rc; }
     if (pairs_per_frame) *pairs_per_frame = 2 * (size_t)sdv::MLENC_FIELD_PAIRS;
     if (lines_per_field) *lines_per_field = g.lpft;
-    if (row_bytes) *row_bytes = (size_t)d->width;
+    if (row_bytes) *row_bytes = g.row_bytes;
     return SDV_OK;
 }
 
@@ -52,7 +53,7 @@ int sdv_encode_markerless_frames(sdv_engine *e, const sdv_encode_markerless_desc
     if (rc != SDV_OK) { set_error(e, why); return rc; }
     const uint64_t n_fields = 2 * (uint64_t)n_frames, n_lines = n_fields * (uint64_t)g.lpft;
     size_t used_pairs = 0;                              /* the pairs the call reads */
-    const int rc_buf = encode_check_buffers(e, d->width, d->height, pcm, n_pairs, n_fields * sdv::MLENC_FIELD_PAIRS, n_frames, dst, dst_row_stride, dst_frame_stride,
+    const int rc_buf = encode_check_buffers(e, g.row_bytes, d->height, pcm, n_pairs, n_fields * sdv::MLENC_FIELD_PAIRS, n_frames, dst, dst_row_stride, dst_frame_stride,
                                             &used_pairs);
     if (rc_buf != SDV_OK) return rc_buf;
     SDV_ON_DEVICE(e);
@@ -72,7 +73,7 @@ int sdv_encode_markerless_frames(sdv_engine *e, const sdv_encode_markerless_desc
     if (d->format == SDV_ENC_FMT_PCM1) RT_CHECK(RT_LAUNCH_ITEMS(sdv_k_mlenc_pcm1_words, sdv::mlenc_pcm1_words_body, 0, word_threads, 256, s, w));
     else RT_CHECK(RT_LAUNCH_ITEMS(sdv_k_mlenc_pcm16_words, sdv::mlenc_pcm16_words_body, 0, word_threads, 256, s, w));
 
-    const EncodeRaster r = { d->width, d->height, d->top_line, g.lpft, g.cells, w.span, d->field_order == SDV_ENC_BFF, d->black, d->white };
+    const EncodeRaster r = { d->width, d->height, d->top_line, g.lpft, g.cells, w.span, d->field_order == SDV_ENC_BFF, d->black, d->white, d->out_fmt[0], g.row_bytes };
     return encode_launch_raster(e, t, r, n_frames, dst, dst_row_stride, dst_frame_stride, s);
 }
 

@@ -33,6 +33,7 @@
 
 #include "ingest_device.h"          /* sdv_k_ingest (sdv_ingest_frames, ingest_engine.inc) */
 #include "encode_device.h"          /* sdv_k_encode_words, sdv_k_encode_raster (sdv_encode_frames, encode_engine.inc) */
+#include "encode_packed_device.h"   /* sdv_k_encode_raster_packed (the encoders' out_fmt other than SDV_PIX_GRAY8, encode_engine.inc) */
 #include "encode_markerless_device.h"   /* sdv_k_mlenc_pcm1_words, sdv_k_mlenc_pcm16_words (sdv_encode_markerless_frames, encode_markerless_engine.inc) */
 #include "pcm_preemph_device.h"     /* sdv_k_preemph (sdv_pcm_preemphasis, pcm_condition_engine.inc) */
 #include "pcm_resample_device.h"    /* sdv_k_pcmrs (sdv_pcm_resample, pcm_condition_engine.inc) */

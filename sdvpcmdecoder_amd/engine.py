@@ -173,8 +173,9 @@ class Engine:
 
     def encode_frames(self, pcm, n_frames: int, standard="ntsc", bits: int = 14, ctrl_block: bool = False, ctrl_flags: int = 0, bff: bool = False,
                       width: int = 720, height: int = 486, data_start: int = 12, data_stop=None, top_line: int = 0, black: int = 30, white: int = 200,
-                      time_code=(0, 0, 0, 0, 0), stream=None):
-        """sdv_encode_frames: the next n_frames frames of the tape this engine writes -> (n_frames, height, width) uint8 CUDA tensor.
+                      time_code=(0, 0, 0, 0, 0), stream=None, pix_fmt="gray8"):
+        """sdv_encode_frames: the next n_frames frames of the tape this engine writes -> (n_frames, height, row_bytes) uint8 CUDA tensor; row_bytes
+        is width for pix_fmt "gray8", else the bytes of a packed row (encode_geometry).  pix_fmt: the names ingest takes, or a PIX_* value.
         pcm: torch.int16 CUDA tensor (pairs, 2), interleaved L R; a frame consumes encode_geometry()[0] pairs, pairs that lack are silence (end a
         tape with one frame more from an empty tensor: the interleave delay is played out).  standard: "ntsc" / "pal" or an ENC_* value; bits 14
         or 16; time_code (index, hour, minute, second, field) of the first field after reset_encoder; data_stop defaults to width - 12."""
@@ -185,15 +186,24 @@ class Engine:
         if bits not in (14, 16):
             raise ValueError("bits is 14 or 16")
         desc = EncodeDesc(std, ENC_16BIT if bits == 16 else ENC_14BIT, int(bool(ctrl_block)), ctrl_flags, ENC_BFF if bff else ENC_TFF, black, white, 0,
-                          time_code[0], time_code[1], time_code[2], time_code[3], time_code[4], (C.c_uint8 * 3)(), width, height, data_start,
-                          width - 12 if data_stop is None else data_stop, top_line)
-        self.encode_geometry(desc)
-        out = torch.empty((n_frames, height, width), dtype=torch.uint8, device=pcm.device)
+                          time_code[0], time_code[1], time_code[2], time_code[3], time_code[4], (C.c_uint8 * 3)(self._pix_fmt(pix_fmt)), width, height,
+                          data_start, width - 12 if data_stop is None else data_stop, top_line)
+        row_bytes = self.encode_geometry(desc)[2]
+        out = torch.empty((n_frames, height, row_bytes), dtype=torch.uint8, device=pcm.device)
         n_pairs = pcm.numel() // 2
         sptr = C.c_void_p(stream.cuda_stream) if stream is not None else C.c_void_p(torch.cuda.current_stream(pcm.device).cuda_stream)
         self._check(self.lib.sdv_encode_frames(self._h, C.byref(desc), C.c_void_p(pcm.data_ptr()) if n_pairs else None, n_pairs, n_frames,
-                                               C.c_void_p(out.data_ptr()), width, height * width, sptr))
+                                               C.c_void_p(out.data_ptr()), row_bytes, height * row_bytes, sptr))
         return out
+
+    @staticmethod
+    def _pix_fmt(pix_fmt):
+        """a PIX_* value from its name (as ingest takes it) or itself"""
+        if isinstance(pix_fmt, str):
+            if pix_fmt not in PIX_FORMATS:
+                raise ValueError("pix_fmt is one of " + ", ".join(sorted(PIX_FORMATS)))
+            return PIX_FORMATS[pix_fmt]
+        return int(pix_fmt) & 0xFF
 
     def reset_encoder(self):
         """sdv_reset_encoder: the next encode_frames call starts a new tape."""
@@ -202,14 +212,15 @@ class Engine:
     @staticmethod
     def encode_markerless_desc(fmt="pcm1", bff: bool = False, header_lines: int = 0, emphasis: bool = False, rate_44100: bool = False, code: bool = False,
                                width: int = 720, height: int = 490, data_start: int = 4, data_stop=None, top_line: int = 0, black: int = 30,
-                               white: int = 200) -> EncodeMarkerlessDesc:
-        """The descriptor of encode_markerless_frames' keywords.  fmt: "pcm1" / "pcm16x0_si" / "pcm16x0_ei" or an ENC_FMT_* value."""
+                               white: int = 200, pix_fmt="gray8") -> EncodeMarkerlessDesc:
+        """The descriptor of encode_markerless_frames' keywords.  fmt: "pcm1" / "pcm16x0_si" / "pcm16x0_ei" or an ENC_FMT_* value; pix_fmt: the
+        names ingest takes, or a PIX_* value."""
         formats = {"pcm1": ENC_FMT_PCM1, "pcm16x0_si": ENC_FMT_PCM16X0_SI, "pcm16x0_ei": ENC_FMT_PCM16X0_EI}
         if isinstance(fmt, str) and fmt not in formats:
             raise ValueError("fmt is one of " + ", ".join(sorted(formats)))
         flags = (ENC_ML_EMPHASIS if emphasis else 0) | (ENC_ML_RATE_44100 if rate_44100 else 0) | (ENC_ML_CODE if code else 0)
         return EncodeMarkerlessDesc(formats[fmt] if isinstance(fmt, str) else int(fmt), ENC_BFF if bff else ENC_TFF, black, white, header_lines, flags,
-                                    (C.c_uint8 * 2)(), width, height, data_start, width - 4 if data_stop is None else data_stop, top_line)
+                                    (C.c_uint8 * 2)(Engine._pix_fmt(pix_fmt)), width, height, data_start, width - 4 if data_stop is None else data_stop, top_line)
 
     def encode_markerless_geometry(self, desc: EncodeMarkerlessDesc):
         """sdv_encode_markerless_geometry: (pairs a frame consumes, lines per field, bytes of a row) of a descriptor; host only."""
@@ -220,7 +231,8 @@ class Engine:
         return pairs.value, lines.value, rb.value
 
     def encode_markerless_frames(self, pcm, n_frames: int, fmt="pcm1", stream=None, **kw):
-        """sdv_encode_markerless_frames: n_frames frames of a PCM-1 or PCM-16x0 tape -> (n_frames, height, width) uint8 CUDA tensor.
+        """sdv_encode_markerless_frames: n_frames frames of a PCM-1 or PCM-16x0 tape -> (n_frames, height, row_bytes) uint8 CUDA tensor; row_bytes
+        is width unless the keyword pix_fmt asks for a packed format.
         pcm: torch.int16 CUDA tensor (pairs, 2), interleaved L R; a frame takes 1470 pairs, pairs that lack are silence.  There is no state: the next
         call goes on with pcm[1470 * n_frames:].  The keywords are those of encode_markerless_desc; data_stop defaults to width - 4.  PCM-1 wants
         header_lines = 1 (and height 492) for a tape the decoder reads without a forced-bad first line."""
@@ -228,12 +240,12 @@ class Engine:
         if not (pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous() and (pcm.dim() == 2 and pcm.shape[1] == 2 or pcm.numel() == 0)):
             raise ValueError("pcm must be a contiguous torch.int16 CUDA tensor of shape (pairs, 2)")
         desc = self.encode_markerless_desc(fmt, **kw)
-        self.encode_markerless_geometry(desc)
-        out = torch.empty((n_frames, desc.height, desc.width), dtype=torch.uint8, device=pcm.device)
+        row_bytes = self.encode_markerless_geometry(desc)[2]
+        out = torch.empty((n_frames, desc.height, row_bytes), dtype=torch.uint8, device=pcm.device)
         n_pairs = pcm.numel() // 2
         sptr = C.c_void_p(stream.cuda_stream) if stream is not None else C.c_void_p(torch.cuda.current_stream(pcm.device).cuda_stream)
         self._check(self.lib.sdv_encode_markerless_frames(self._h, C.byref(desc), C.c_void_p(pcm.data_ptr()) if n_pairs else None, n_pairs, n_frames,
-                                                          C.c_void_p(out.data_ptr()), desc.width, desc.height * desc.width, sptr))
+                                                          C.c_void_p(out.data_ptr()), row_bytes, desc.height * row_bytes, sptr))
         return out
 
     # ---- ahead of the encoders: pre-emphasis and 44 100 -> 44 056 Hz on (pairs, 2) int16 PCM: beyond the reference ----------------------
