@@ -106,17 +106,19 @@ def apply(luma, plan, d, how="black", seed=0):
     return out
 
 
-def forced_bad(plan, d):
+def forced_bad(plan, d, opens=None):
     """The lines the reference's VideoToDigital hands on as bad although they read well.  A field that does not open with its control block (or header)
     is "unsafe" from its first line with PCM on: the dropout compensator of the player may have copied that line from above the picture.  The first line
     of such a field whose CRC is good is forced bad, and only a good CRC ends the state (videotodigital.cpp:1156-1166, :1193-1203 with en_first_line_dup,
     :1391-1395).  So: per field, the first captured line the plan leaves alone - unless that line is the control line.  Its words still reach the blocks,
-    but with the line-CRC state 'bad': to every block it is one more unread word."""
+    but with the line-CRC state 'bad': to every block it is one more unread word.  opens: the fields open with such a line (default: the STC-007 descriptor's
+    ctrl_block; tests/markerless_truth.py hands in PCM-1's header_lines - the rule is the same in all three branches of VideoToDigital)."""
+    opens = d.ctrl_block if opens is None else opens
     out = np.zeros_like(plan)
     last = min(plan.shape[1], d.top_line + d.height // 2)
     for f in range(plan.shape[0]):
         alive = np.flatnonzero(~plan[f, d.top_line:last])
-        if len(alive) and not (d.ctrl_block and d.top_line + alive[0] == 0):
+        if len(alive) and not (opens and d.top_line + alive[0] == 0):
             out[f, d.top_line + alive[0]] = True
     return out
 
@@ -317,22 +319,23 @@ def runs_of(mask):
     return [(int(a), int(b - a)) for a, b in zip(edge[0::2], edge[1::2])]
 
 
-def interpolation_bound(ch, g, res):
+def interpolation_bound(ch, g, res, q=None):
     """A w^2 (g + 1)^2 / 8 + 2 q + 1: the chord error of a straight line over g + 1 sample steps of A sin(w n) (max |f''| h^2 / 8), the quantisation q of
-    the two ends (0.5 for rounding; 14 bit: + 3 for the cleared bits) and one for the integer arithmetic"""
+    the two ends (0.5 for rounding; 14 bit: + 3 for the cleared bits; another format states its own q) and one for the integer arithmetic"""
     a, f, _ = SINE[ch]
     w = 2 * np.pi * f / RATE
-    return a * w * w * (g + 1) ** 2 / 8 + 2 * (0.5 if res == en.BIT16 else 3.5) + 1
+    return a * w * w * (g + 1) ** 2 / 8 + 2 * ((0.5 if res == en.BIT16 else 3.5) if q is None else q) + 1
 
 
-def check_t5(t, decoded, n_masked, mode, invalid):
+def check_t5(t, decoded, n_masked, mode, invalid, lead_audio=None, q=None):
     """T5: the audio stage against the signal.  decoded: the pair stream behind the audio stage, n_masked: what the call reported, invalid (pairs, 2): the
     samples the stitch output had marked invalid.  Every sample is the source's (T1's rule) and unmasked, or masked; *n_masked counts the MASKED flags;
     HOLD_WORD repeats the nearest earlier unmasked sample of the channel, INTER_LIN_WORD stays within interpolation_bound of the real-valued sine,
     MUTE_WORD leaves the source's sample or 0 - and a 0 that is not the source's only where the stitch output was invalid (it may lack MASKED: a sample
-    that was 0 already is not flagged)."""
+    that was 0 already is not flagged).  lead_audio, q: where source pair 0 comes out and the quantisation of a format that is not STC-007."""
+    lead_audio = lead(t.d, True) if lead_audio is None else lead_audio
     off, got, flags = align(decoded, t.pcm)
-    assert off == lead(t.d, True), "source pair 0 at %d behind the audio stage, %d on the undamaged tape" % (off, lead(t.d, True))
+    assert off == lead_audio, "source pair 0 at %d behind the audio stage, %d on the undamaged tape" % (off, lead_audio)
     audio = decoded[decoded["service_type"] == 0]
     assert n_masked == int(((audio["sample_flags"] & MASKED) != 0).sum()), "T5: *n_masked"
     masked_all = (audio["sample_flags"] & MASKED) != 0
@@ -354,5 +357,5 @@ def check_t5(t, decoded, n_masked, mode, invalid):
                     assert got[i, ch] == got[start - 1, ch], "T5 hold: %s holds %d, the sample before the run is %d" % (t.where(i, ch), got[i, ch], got[start - 1, ch])
                 else:
                     assert mode == A.DROP_INTER_LIN_WORD
-                    err, bound = abs(float(got[i, ch]) - real[i, ch]), interpolation_bound(ch, g, t.res)
+                    err, bound = abs(float(got[i, ch]) - real[i, ch]), interpolation_bound(ch, g, t.res, q)
                     assert err <= bound, "T5 interpolation: %s in a run of %d is %.1f off the signal, the bound is %.1f" % (t.where(i, ch), g, err, bound)
