@@ -20,13 +20,13 @@ KERNEL_SOURCES = {
     "sdv_k_stc007_frames": ("stc007_device.h", "stc007_sweep_device.h", "engine.inc", "runtime.inc", "stc007_chain_plan.h", "stc007_frames_engine.inc"),
     "sdv_k_stc007_sweep": ("stc007_device.h", "stc007_sweep_device.h", "engine.inc", "runtime.inc", "stc007_chain_plan.h", "stc007_frames_engine.inc"),
     "sdv_k_hist_carry": ("stc007_device.h", "engine.inc", "runtime.inc", "stc007_chain_plan.h", "stc007_frames_engine.inc"),
-    "sdv_k_pcm1_lines": ("stc007_device.h", "pcm1_bin_device.h", "pcm1_engine.inc"),
-    "sdv_k_pcm1_frames": ("pcm1_stitch_device.h", "pcm1_engine.inc"),
-    "sdv_k_pcm1_frames_bin": ("stc007_device.h", "pcm1_bin_device.h", "pcm1_frames_device.h", "markerless_chain_device.h", "markerless_frames_engine.inc", "pcm1_frames_engine.inc"),
-    "sdv_k_pcm1_frames_lean": ("stc007_device.h", "pcm1_bin_device.h", "pcm1_frames_device.h", "markerless_chain_device.h", "markerless_frames_engine.inc", "pcm1_frames_engine.inc"),
-    "sdv_k_pcm1_prescan": ("stc007_device.h", "pcm1_bin_device.h", "pcm1_frames_device.h", "markerless_chain_device.h", "markerless_frames_engine.inc", "pcm1_frames_engine.inc"),
-    "sdv_k_pcm16_frames_lean": ("stc007_device.h", "pcm1_bin_device.h", "pcm16_bin_device.h", "pcm16_frames_device.h", "markerless_chain_device.h", "markerless_frames_engine.inc", "pcm16_frames_engine.inc"),
-    "sdv_k_pcm16_prescan": ("stc007_device.h", "pcm1_bin_device.h", "pcm16_bin_device.h", "pcm16_frames_device.h", "markerless_chain_device.h", "markerless_frames_engine.inc", "pcm16_frames_engine.inc"),
+    "sdv_k_pcm1_lines": ("stc007_device.h", "pcm1_bin_device.h", "markerless_frames_engine.inc", "pcm1_frames_engine.inc"),
+    "sdv_k_pcm1_frames": ("pcm1_stitch_device.h", "stitch_stream_device.h", "stitch_stream.inc", "pcm1_engine.inc"),
+    "sdv_k_pcm1_frames_bin": ("stc007_device.h", "pcm1_bin_device.h", "markerless_frames_device.h", "pcm1_frames_device.h", "markerless_chain_device.h", "markerless_frames_engine.inc", "pcm1_frames_engine.inc"),
+    "sdv_k_pcm1_frames_lean": ("stc007_device.h", "pcm1_bin_device.h", "markerless_frames_device.h", "pcm1_frames_device.h", "markerless_chain_device.h", "markerless_frames_engine.inc", "pcm1_frames_engine.inc"),
+    "sdv_k_pcm1_prescan": ("stc007_device.h", "pcm1_bin_device.h", "markerless_frames_device.h", "pcm1_frames_device.h", "markerless_chain_device.h", "markerless_frames_engine.inc", "pcm1_frames_engine.inc"),
+    "sdv_k_pcm16_frames_lean": ("stc007_device.h", "pcm1_bin_device.h", "pcm16_bin_device.h", "markerless_frames_device.h", "pcm16_frames_device.h", "markerless_chain_device.h", "markerless_frames_engine.inc", "pcm16_frames_engine.inc"),
+    "sdv_k_pcm16_prescan": ("stc007_device.h", "pcm1_bin_device.h", "pcm16_bin_device.h", "markerless_frames_device.h", "pcm16_frames_device.h", "markerless_chain_device.h", "markerless_frames_engine.inc", "pcm16_frames_engine.inc"),
     "sdv_k_ap_": ("audio_device.h", "audio_engine.inc"),
     "sdv_k_deemph": ("audio_device.h", "audio_deemph_device.h", "audio_engine.inc"),
     "sdv_k_resample": ("audio_device.h", "audio_resample_device.h", "audio_engine.inc"),
@@ -36,7 +36,7 @@ KERNEL_SOURCES = {
     "sdv_k_mlenc": ("encode_device.h", "encode_markerless_device.h", "encode_engine.inc", "encode_markerless_engine.inc"),
     "sdv_k_preemph": ("pcm_preemph_device.h", "pcm_condition_engine.inc"),
     "sdv_k_pcmrs": ("pcm_preemph_device.h", "pcm_resample_device.h", "pcm_condition_engine.inc"),
-    "sdv_k_pcm16_frames_bin": ("stc007_device.h", "pcm1_bin_device.h", "pcm16_bin_device.h", "pcm16_frames_device.h", "markerless_chain_device.h", "markerless_frames_engine.inc", "pcm16_frames_engine.inc"),
+    "sdv_k_pcm16_frames_bin": ("stc007_device.h", "pcm1_bin_device.h", "pcm16_bin_device.h", "markerless_frames_device.h", "pcm16_frames_device.h", "markerless_chain_device.h", "markerless_frames_engine.inc", "pcm16_frames_engine.inc"),
 }
 
 

@@ -10,18 +10,17 @@
 
 namespace sdvml {
 using namespace sdv;
-using sdvp1f::PrescanRes;
-using sdvp1f::prescan_ref_of;
-using sdvp1f::prescan_runs;
-using sdvp1f::COORD_CHECK_LINES;
+using sdvmf::PrescanRes;
+using sdvmf::prescan_ref_of;
+using sdvmf::prescan_runs;
+using sdvmf::COORD_CHECK_LINES;
+using sdvmf::link_holds;
+using sdvmf::v2d_of;
+using sdvp16f::v2d_of;
 using sdvp16f::State16;
 using sdvp16f::LV16;
 
-/* ---- what differs between the formats ---------------------------------------------------------------------------------------- */
-__device__ __forceinline__ sdv_v2d_state &v2d_of(sdv_v2d_state &s) { return s; }
-__device__ __forceinline__ const sdv_v2d_state &v2d_of(const sdv_v2d_state &s) { return s; }
-__device__ __forceinline__ sdv_v2d_state &v2d_of(State16 &s) { return s.s; }
-__device__ __forceinline__ const sdv_v2d_state &v2d_of(const State16 &s) { return s.s; }
+/* ---- what differs between the formats (v2d_of: with the state types) ------------------------------------------------------- */
 /* the window of last valid coordinates: its length, entry i, all of it filled with one pair */
 constexpr int last_valid_depth(const sdv_v2d_state *) { return COORD_HISTORY_DEPTH; }
 constexpr int last_valid_depth(const State16 *) { return LV16; }
@@ -38,8 +37,6 @@ __device__ __forceinline__ void fill_last_valid(State16 &p, sdv_coord c)
     for (int i = 0; i < COORD_HISTORY_DEPTH; i++) p.s.last_valid[i] = c;
     for (int i = 0; i < LV16 - COORD_HISTORY_DEPTH; i++) p.more[i] = c;
 }
-__device__ __forceinline__ bool link_holds(const FrameArgs &a, int f, const sdv_v2d_state &out, const sdv_v2d_state &next_in) { return sdvp1f::link_holds1(a, f, out, next_in); }
-__device__ __forceinline__ bool link_holds(const FrameArgs &a, int f, const State16 &out, const State16 &next_in) { return sdvp16f::link_holds16(a, f, out, next_in); }
 /* Is the first prediction of a call the sticky model (predict_state)?  PCM-16x0 has no Header lines: the first line of a field is always
  * marked bad and the worker falls back on its coordinate history behind it, so a stream keeps the coordinates it carries.  A PCM-1 field
  * opens with its Header line, and the frames decode with what their own prescan finds. */

@@ -22,14 +22,30 @@ template <class K, class A> static inline rt::status_t launch_chain_range(K kern
     return RT_LAUNCH_ITEMS(kernel, ([&](const A &x, int i) { kernel(x, i, i + 1); }), lo, hi - lo, 256, s, a, lo, hi);
 }
 
+/* the argument checks of sdv_pcm1_binarize_lines and sdv_pcm16x0_binarize_lines (the line-by-line front halves); *todo: there are lines to decode */
+template <class Fmt>
+static int check_lines_call(sdv_engine *e, const uint8_t *luma, size_t row_stride, int width, size_t n_lines, const void *out_lines, size_t lines_cap, bool *todo)
+{
+    *todo = false;
+    if (!e) return SDV_ERR_BAD_ARG;
+    if (!luma) { set_error(e, "null video"); return SDV_ERR_NULL_VIDEO; }
+    if (!out_lines) { set_error(e, "null output"); return SDV_ERR_NULL_PCM; }
+    if (width <= 0 || width > SDV_PX_BYTES || row_stride < (size_t)width) { set_error(e, "bad line geometry"); return SDV_ERR_BAD_ARG; }
+    if (width < Fmt::MIN_WIDTH) { set_error(e, Fmt::short_line()); return SDV_ERR_SHORT_LINE; }
+    if (n_lines == 0) return SDV_OK;
+    if (lines_cap / Fmt::LINES_PER_ROW < n_lines) { set_error(e, "output buffer too small: " + std::to_string(Fmt::LINES_PER_ROW * n_lines) + " " + Fmt::rec_noun() + " are needed"); return SDV_ERR_BAD_ARG; }
+    *todo = true;
+    return SDV_OK;
+}
+
 template <class Fmt>
 static int markerless_binarize_frames(sdv_engine *e, const uint8_t *luma, size_t row_stride, size_t frame_stride, int width, int height,
                                       int n_frames, uint32_t first_frame_no, unsigned flags, typename Fmt::Rec *out_lines, size_t lines_cap,
                                       sdv_frame_stats *out_stats, size_t stats_cap, void *stream)
 {
     typedef typename Fmt::State State;
-    using sdvp1f::COORD_CHECK_LINES;
-    using sdvp1f::PrescanRes;
+    using sdvmf::COORD_CHECK_LINES;
+    using sdvmf::PrescanRes;
     if (!e) return SDV_ERR_BAD_ARG;
     FrameFlagsConsumed flags_consumed(e);
     int rc = check_frame_call(e, luma, out_lines, out_stats, row_stride, frame_stride, width, height, n_frames, flags, lines_cap, stats_cap,

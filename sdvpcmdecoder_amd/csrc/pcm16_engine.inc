@@ -6,20 +6,17 @@
  * conv_queue, output offsets), ctrl (all at once), flags (in order), emit (all at once).  The stitcher's stream state (padding and Control Bit histories) stays in device memory between the
  * kernels and between calls; a call that fails puts back the copy taken at its start.
  */
+#include "stitch_stream.inc"
 /* The analysis of a batch does not depend on the decisions of the batch before it: where streams run beside each other (rt::CONCURRENT, the product
  * build) it runs on a stream of its own, ahead of the in-order kernels (which are single waves and leave the chip idle); the emulator build runs
  * everything in order on the caller's stream. */
 struct sdv_pcm16_stitcher {
     sdv_pcm16x0_stitch_settings st;
     /* (made by new sdv_pcm16_stitcher(): everything that is not a buffer starts as zero) */
-    rt::DevBuf<sdv_pcm16x0_bin_rec> d_carry; size_t n_carry;
-    rt::DevBuf<sdv_pcm16x0_bin_rec> d_carry_spare;
-    rt::DevBuf<uint32_t> d_blk_count, d_blk_ofs;
-    rt::DevBuf<uint8_t> d_svc;
-    rt::DevBuf<uint32_t> d_seg_end, d_marks, d_frasm_ofs, d_vblk_ofs; rt::DevBuf<uint64_t> d_pair_ofs;
-    rt::DevBuf<uint32_t> d_stat;
-    sdv_pcm16x0_bin_rec *vis_lines; size_t vis_lines_cap, vis_lines_n; rt::DevBuf<uint32_t> d_vline_ofs, d_field_src;       /* ... and its assembled sub-lines */
-    sdv_pcm16x0_block_rec *vis_blocks; size_t vis_blocks_cap, vis_blocks_n;       /* the visualiser's feed (caller's buffer) and what the last call made of it */
+    RecStream<sdv_pcm16x0_bin_rec> rs;          /* the records of the stream and their segments (stitch_stream.inc) */
+    rt::DevBuf<uint32_t> d_vblk_ofs, d_vline_ofs, d_field_src;
+    VisFeed<sdv_pcm16x0_block_rec> vis_blocks;  /* the visualiser's feed ... */
+    VisFeed<sdv_pcm16x0_bin_rec> vis_lines;     /* ... and its assembled sub-lines */
     rt::DevBuf<sdvp16::State16> d_state;               /* [0] the stream's state, [1] its copy at the start of the running call */
     bool state_valid;
     rt::DevBuf<sdvp16::Sub> d_rem, d_rem_slots;       /* conv_queue's remainder: behind the last call (FRAME_SUBS entries) / behind every batch of the running call */
@@ -67,7 +64,7 @@ int sdv_set_pcm16x0_stitch_settings(sdv_engine *e, const sdv_pcm16x0_stitch_sett
     if (st->format > SDV_P16_FORMAT_EI) { set_error(e, "unknown PCM-16x0 format"); return SDV_ERR_BAD_ARG; }
     sdv_pcm16_stitcher *t = pcm16_get(e);
     t->st = *st;
-    t->n_carry = 0; t->state_valid = false;         /* a fresh stitcher */
+    t->rs.n_carry = 0; t->state_valid = false;         /* a fresh stitcher */
     return SDV_OK;
 }
 
@@ -123,7 +120,7 @@ int sdv_set_pcm16x0_stitch_state(sdv_engine *e, const void *in, size_t n)
     RT_CHECK(rt::h2d(t->d_state, &b->st, sizeof(b->st), (rt::stream_t)0));
     RT_CHECK(rt::h2d(t->d_rem, b->rem, sizeof(b->rem), (rt::stream_t)0));
     RT_CHECK(rt::ssync((rt::stream_t)0));
-    t->state_valid = true; t->n_carry = 0;
+    t->state_valid = true; t->rs.n_carry = 0;
     return SDV_OK;
 }
 /* every ring filled with its most frequent entry: for an engine that joined the stream after a short warm-up and is about to compare
@@ -141,42 +138,23 @@ int sdv_saturate_pcm16x0_stitch_stats(sdv_engine *e)
     return sdv_set_pcm16x0_stitch_state(e, &b, sizeof(b));
 }
 
-int sdv_set_pcm16x0_stitch_block_output(sdv_engine *e, sdv_pcm16x0_block_rec *out_blocks, size_t blocks_cap)
-{
-    if (!e) return SDV_ERR_BAD_ARG;
-    sdv_pcm16_stitcher *t = pcm16_get(e);
-    t->vis_blocks = out_blocks; t->vis_blocks_cap = out_blocks ? blocks_cap : 0; t->vis_blocks_n = 0;
-    return SDV_OK;
-}
-size_t sdv_pcm16x0_stitch_block_count(sdv_engine *e) { return e && e->pcm16 ? e->pcm16->vis_blocks_n : 0; }
-int sdv_set_pcm16x0_stitch_line_output(sdv_engine *e, sdv_pcm16x0_bin_rec *out_lines, size_t lines_cap)
-{
-    if (!e) return SDV_ERR_BAD_ARG;
-    sdv_pcm16_stitcher *t = pcm16_get(e);
-    t->vis_lines = out_lines; t->vis_lines_cap = out_lines ? lines_cap : 0; t->vis_lines_n = 0;
-    return SDV_OK;
-}
-size_t sdv_pcm16x0_stitch_line_count(sdv_engine *e) { return e && e->pcm16 ? e->pcm16->vis_lines_n : 0; }
+int sdv_set_pcm16x0_stitch_block_output(sdv_engine *e, sdv_pcm16x0_block_rec *out_blocks, size_t blocks_cap) { if (!e) return SDV_ERR_BAD_ARG; pcm16_get(e)->vis_blocks.set(out_blocks, blocks_cap); return SDV_OK; }
+size_t sdv_pcm16x0_stitch_block_count(sdv_engine *e) { return e && e->pcm16 ? e->pcm16->vis_blocks.n : 0; }
+int sdv_set_pcm16x0_stitch_line_output(sdv_engine *e, sdv_pcm16x0_bin_rec *out_lines, size_t lines_cap) { if (!e) return SDV_ERR_BAD_ARG; pcm16_get(e)->vis_lines.set(out_lines, lines_cap); return SDV_OK; }
+size_t sdv_pcm16x0_stitch_line_count(sdv_engine *e) { return e && e->pcm16 ? e->pcm16->vis_lines.n : 0; }
 
 int sdv_pcm16x0_stitch_frames(sdv_engine *e, const sdv_pcm16x0_bin_rec *lines, size_t n_lines, sdv_sample_pair *out_pairs, size_t pairs_cap, size_t *n_pairs,
                               sdv_frame_asm_pcm16x0 *out_frames, size_t frames_cap, size_t *n_frames, void *stream)
 {
-    if (!e || !n_pairs || !n_frames) return SDV_ERR_BAD_ARG;
-    *n_pairs = 0; *n_frames = 0;
-    if (n_lines > 0 && !lines) { set_error(e, "null line buffer"); return SDV_ERR_NULL_LINES; }
-    if (!out_pairs || !out_frames) { set_error(e, "null output buffer"); return SDV_ERR_NULL_BLOCK; }
+    if (!e) return SDV_ERR_BAD_ARG;
     rt::stream_t s = (rt::stream_t)stream;
-    SDV_ON_DEVICE(e);
     sdv_pcm16_stitcher *t = pcm16_get(e);
-    const size_t total = t->n_carry + n_lines;
-    if (total == 0) return SDV_OK;
-    if (total >= 0x3FFFFFFFu) { set_error(e, "too many sub-line records in one call"); return SDV_ERR_BAD_ARG; }
-    sdvp16::RecSrc16 src; src.carry = t->d_carry; src.n_carry = (uint32_t)t->n_carry; src.recs = lines;
+    RecStream<sdv_pcm16x0_bin_rec> &rs = t->rs;
+    size_t total = 0;
+    { const int rc = rs.check_call(e, lines, n_lines, out_pairs, out_frames, n_pairs, n_frames, "sub-line", &total); if (rc != SDV_OK || total == 0) return rc; }
+    SDV_ON_DEVICE(e);
+    const sdvp16::RecSrc16 src = rs.src(lines);
 
-    /* 1. frame segments: positions of the END_FRAME records */
-    const size_t nblk = (total + sdvp16::SEG_CHUNK16 - 1) / sdvp16::SEG_CHUNK16;
-    RT_CHECK(rt::reserve_all(nblk, nblk, t->d_blk_count, t->d_blk_ofs));
-    RT_CHECK(t->d_stat.reserve(8));
     if (!t->d_state) { RT_CHECK(t->d_state.reserve(2)); t->state_valid = false; }
     RT_CHECK(t->d_rem.reserve(sdvp16::FRAME_SUBS));
     if (!t->state_valid) {      /* resetState (:64-85) */
@@ -186,36 +164,21 @@ int sdv_pcm16x0_stitch_frames(sdv_engine *e, const sdv_pcm16x0_bin_rec *lines, s
         RT_CHECK(rt::ssync(s));
         t->state_valid = true;
     }
-    RT_CHECK(t->d_svc.reserve(total, total + total / 4 + 4096));
-    sdvp16::SegArgs16 sa; sa.src = src; sa.n_recs = (uint32_t)total; sa.svc = t->d_svc; sa.block_count = t->d_blk_count; sa.block_ofs = t->d_blk_ofs;
-    sa.seg_end = NULL; sa.n_seg = 0; sa.marks = NULL; sa.stat = t->d_stat; sa.write = 0;
-    RT_LAUNCH64(sdv_k_pcm16_segments, nblk, sa, s);
-    std::vector<uint32_t> blk(nblk);
-    RT_CHECK(rt::d2h(blk.data(), t->d_blk_count, nblk * sizeof(uint32_t), s));
+    /* 1. frame segments: positions of the END_FRAME records */
     size_t n_seg = 0;
-    for (size_t i = 0; i < nblk; i++) { uint32_t c = blk[i]; blk[i] = (uint32_t)n_seg; n_seg += c; }
-    uint32_t last_end = 0;
-    if (n_seg > 0) {
-        RT_CHECK(rt::reserve_all(n_seg + 1, n_seg + 1 + n_seg / 8 + 16, t->d_seg_end, t->d_marks, t->d_frasm_ofs, t->d_vblk_ofs, t->d_vline_ofs, t->d_pair_ofs));
-        RT_CHECK(rt::h2d(t->d_blk_ofs, blk.data(), nblk * sizeof(uint32_t), s));
-        const uint32_t stat0[4] = { 0, 0xFFFFFFFFu, 0, 0 };
-        RT_CHECK(rt::h2d(t->d_stat, stat0, sizeof(stat0), s));
-        RT_CHECK(rt::dfill_bytes(t->d_marks, 0, (n_seg + 1) * sizeof(uint32_t), s));
-        sa.seg_end = t->d_seg_end; sa.n_seg = (uint32_t)n_seg; sa.marks = t->d_marks; sa.write = 1;
-        RT_LAUNCH64(sdv_k_pcm16_segments, nblk, sa, s);
-    }
+    { const int rc = rs.segment<sdvp16::SegArgs16>(e, sdv_k_pcm16_segments, sdvp16::SEG_CHUNK16, lines, total, s, &n_seg, t->d_vblk_ofs, t->d_vline_ofs); if (rc != SDV_OK) return rc; }
     /* EI: the analysis makes every frame's padding table for the padding the history held when the call began, and for all 81 only where that one does
      * not pass (pcm16_stitch_device.h, analyse_body).  The in-order pass says so when a frame treated that way needed more - then everything from
      * here on runs once more, with full tables. */
-    uint32_t stat[4] = { 0, 0, 0, 0 }; uint64_t tot_pairs = 0; uint32_t tot_frames = 0;
+    uint32_t stat[4] = { 0, 0, 0, 0 }; uint64_t tot_pairs = 0; uint32_t tot_frames = 0, last_end = 0;
     for (int attempt = 0;; attempt++) {
     const bool hint_on = attempt == 0 && n_seg > 0 && t->st.format == SDV_P16_FORMAT_EI && !dev_env("SDV_P16_NO_HINT");
     if (n_seg > 0) {
-        if (attempt > 0) { const uint32_t again[4] = { 0, 0xFFFFFFFFu, stat[2], 0 }; RT_CHECK(rt::h2d(t->d_stat, again, sizeof(again), s)); RT_CHECK(rt::ssync(s)); }
+        if (attempt > 0) { const uint32_t again[4] = { 0, 0xFFFFFFFFu, stat[2], 0 }; RT_CHECK(rt::h2d(rs.d_stat, again, sizeof(again), s)); RT_CHECK(rt::ssync(s)); }
 
         /* 2. output offsets: a running sum the carry kernel of every batch takes on (a frame's count depends on what waits in conv_queue) */
-        RT_CHECK(rt::dfill_bytes(t->d_pair_ofs, 0, sizeof(uint64_t), s));
-        RT_CHECK(rt::dfill_bytes(t->d_frasm_ofs, 0, sizeof(uint32_t), s));
+        RT_CHECK(rt::dfill_bytes(rs.d_pair_ofs, 0, sizeof(uint64_t), s));
+        RT_CHECK(rt::dfill_bytes(rs.d_frasm_ofs, 0, sizeof(uint32_t), s));
         RT_CHECK(rt::dfill_bytes(t->d_vblk_ofs, 0, sizeof(uint32_t), s));
         RT_CHECK(rt::dfill_bytes(t->d_vline_ofs, 0, sizeof(uint32_t), s));
 
@@ -225,23 +188,23 @@ int sdv_pcm16x0_stitch_frames(sdv_engine *e, const sdv_pcm16x0_bin_rec *lines, s
         const size_t c = n_seg + n_seg / 8 + 16, per_frame = 2 * sdvp16::SUBLINES_PF;
         RT_CHECK(rt::reserve_all(n_seg, c, t->d_ana, t->d_pick, t->d_choice, t->d_dec, t->d_ctrl));
         RT_CHECK(t->d_fields.reserve(n_seg * per_frame, c * per_frame));
-        if (t->vis_lines) RT_CHECK(t->d_field_src.reserve(n_seg * per_frame, c * per_frame));
+        if (t->vis_lines.p) RT_CHECK(t->d_field_src.reserve(n_seg * per_frame, c * per_frame));
         RT_CHECK(t->d_rem_slots.reserve(n_batches * sdvp16::FRAME_SUBS));
         RT_CHECK(rt::d2d(t->d_state + 1, t->d_state, sizeof(sdvp16::State16), s));
-        sdvp16::FrameArgs16s fa; fa.src = src; fa.seg_end = t->d_seg_end; fa.n_seg = (uint32_t)n_seg;
+        sdvp16::FrameArgs16s fa; fa.src = src; fa.seg_end = rs.d_seg_end; fa.n_seg = (uint32_t)n_seg;
         fa.cfg.format = t->st.format; fa.cfg.field_order = t->st.field_order; fa.cfg.p_correction = t->st.p_correction; fa.cfg.ignore_crc = t->st.use_ecc == 0;
         fa.cfg.mask_seams = t->st.mask_seams; fa.cfg.broke_mask = t->st.broke_mask; fa.cfg.sample_rate_preset = t->st.sample_rate_preset;
-        fa.marks = t->d_marks; fa.pair_ofs = t->d_pair_ofs; fa.frasm_ofs = t->d_frasm_ofs;
-        fa.vblk_ofs = t->vis_blocks ? t->d_vblk_ofs.p : NULL; fa.out_blocks = t->vis_blocks; fa.blocks_cap = t->vis_blocks_cap;
-        fa.vline_ofs = t->vis_lines ? t->d_vline_ofs.p : NULL; fa.out_lines = t->vis_lines; fa.lines_cap = t->vis_lines_cap; fa.field_src = NULL;
+        fa.marks = rs.d_marks; fa.pair_ofs = rs.d_pair_ofs; fa.frasm_ofs = rs.d_frasm_ofs;
+        fa.vblk_ofs = t->vis_blocks.p ? t->d_vblk_ofs.p : NULL; fa.out_blocks = t->vis_blocks.p; fa.blocks_cap = t->vis_blocks.cap;
+        fa.vline_ofs = t->vis_lines.p ? t->d_vline_ofs.p : NULL; fa.out_lines = t->vis_lines.p; fa.lines_cap = t->vis_lines.cap; fa.field_src = NULL;
         fa.state = t->d_state; fa.state_snap = hint_on ? t->d_state.p : NULL;      /* (the analysis reads the history as it stands while it runs: a hint, checked by what it is used for) */
         fa.out_pairs = out_pairs; fa.pairs_cap = pairs_cap; fa.out_frames = out_frames; fa.frames_cap = (uint32_t)(frames_cap > 0xFFFFFFFFu ? 0xFFFFFFFFu : frames_cap);
-        fa.stat = t->d_stat;
+        fa.stat = rs.d_stat;
         auto point_at = [&](size_t b0) {
             fa.seg_base = (uint32_t)b0; fa.n_batch = (uint32_t)(n_seg - b0 < batch ? n_seg - b0 : batch);
             fa.ana = t->d_ana + b0; fa.pick = t->d_pick + b0; fa.choice = t->d_choice + b0; fa.dec = t->d_dec + b0; fa.ctrl = t->d_ctrl + b0;
             fa.fields = t->d_fields + b0 * 2 * sdvp16::SUBLINES_PF;
-            fa.field_src = t->vis_lines ? t->d_field_src + b0 * 2 * sdvp16::SUBLINES_PF : NULL;
+            fa.field_src = t->vis_lines.p ? t->d_field_src + b0 * 2 * sdvp16::SUBLINES_PF : NULL;
             const size_t b = b0 / batch;
             fa.rem_in = b == 0 ? t->d_rem : t->d_rem_slots + (b - 1) * sdvp16::FRAME_SUBS; fa.rem_out = t->d_rem_slots + b * sdvp16::FRAME_SUBS;
         };
@@ -303,7 +266,7 @@ int sdv_pcm16x0_stitch_frames(sdv_engine *e, const sdv_pcm16x0_bin_rec *lines, s
             }
             RT_LAUNCH64(sdv_k_pcm16_flags, 1, fa, s_tail);
             RT_LAUNCH64(sdv_k_pcm16_emit, fa.n_batch, fa, s_tail);
-            if (t->vis_lines) RT_LAUNCH64(sdv_k_pcm16_emit_lines, fa.n_batch, fa, s_tail);
+            if (t->vis_lines.p) RT_LAUNCH64(sdv_k_pcm16_emit_lines, fa.n_batch, fa, s_tail);
         }
         if (three_chains) {     /* back to one stream */
             RT_CHECK(rt::record(t->side.joined, t->side.tail));
@@ -311,14 +274,10 @@ int sdv_pcm16x0_stitch_frames(sdv_engine *e, const sdv_pcm16x0_bin_rec *lines, s
         }
     }
 
-    /* 4. records after the last END_FRAME wait for the next call, like sub-lines in the reference's input queue */
-    if (n_seg > 0) {        /* status words, totals and the last END_FRAME in one small copy (sdv_k_stitch_tail) */
-        sdv_stitch_tail_args ta; ta.stat = t->d_stat; ta.pair_total = t->d_pair_ofs + n_seg; ta.frasm_total = t->d_frasm_ofs + n_seg; ta.last_end = t->d_seg_end + (n_seg - 1);
-        RT_LAUNCH64(sdv_k_stitch_tail, 1, ta, s);
-        uint32_t res[8];
-        RT_CHECK(rt::d2h(res, t->d_stat, sizeof(res), s));
-        memcpy(stat, res, sizeof(stat)); tot_pairs = (uint64_t)res[4] | ((uint64_t)res[5] << 32); tot_frames = res[6]; last_end = res[7];
-    } else RT_CHECK(rt::ssync(s));
+    /* 4. what the call made */
+    RecStream<sdv_pcm16x0_bin_rec>::Tail tail;
+    { const int rc = rs.read_tail(e, n_seg, s, &tail); if (rc != SDV_OK) return rc; }
+    memcpy(stat, tail.stat, sizeof(stat)); tot_pairs = tail.pairs; tot_frames = tail.frames; last_end = tail.last_end;
     if (dev_env("SDV_P16_HINT_TRACE")) fprintf(stderr, "[p16 hint] attempt %d: hint %s, %zu frames, needs full tables: %u\n", attempt, hint_on ? "on" : "off", n_seg, stat[3]);
     if (hint_on && stat[3] && !stat[0]) {       /* a frame needed more than the one padding: the histories back to where the call began, and once more */
         RT_CHECK(rt::d2d(t->d_state, t->d_state + 1, sizeof(sdvp16::State16), s));
@@ -328,11 +287,11 @@ int sdv_pcm16x0_stitch_frames(sdv_engine *e, const sdv_pcm16x0_bin_rec *lines, s
     break;
     }
     *n_pairs = (size_t)tot_pairs; *n_frames = tot_frames;
-    t->vis_blocks_n = 0;
-    if (n_seg > 0 && t->vis_blocks) { uint32_t nb = 0; RT_CHECK(rt::d2h(&nb, t->d_vblk_ofs + n_seg, sizeof(nb), s)); t->vis_blocks_n = nb; }
-    t->vis_lines_n = 0;
-    if (n_seg > 0 && t->vis_lines) { uint32_t nl = 0; RT_CHECK(rt::d2h(&nl, t->d_vline_ofs + n_seg, sizeof(nl), s)); t->vis_lines_n = nl; }
-    const bool too_small = tot_pairs > pairs_cap || tot_frames > frames_cap || t->vis_blocks_n > t->vis_blocks_cap || t->vis_lines_n > t->vis_lines_cap;
+    t->vis_blocks.n = 0;
+    if (n_seg > 0 && t->vis_blocks.p) { uint32_t nb = 0; RT_CHECK(rt::d2h(&nb, t->d_vblk_ofs + n_seg, sizeof(nb), s)); t->vis_blocks.n = nb; }
+    t->vis_lines.n = 0;
+    if (n_seg > 0 && t->vis_lines.p) { uint32_t nl = 0; RT_CHECK(rt::d2h(&nl, t->d_vline_ofs + n_seg, sizeof(nl), s)); t->vis_lines.n = nl; }
+    const bool too_small = tot_pairs > pairs_cap || tot_frames > frames_cap || t->vis_blocks.n > t->vis_blocks.cap || t->vis_lines.n > t->vis_lines.cap;
     if (stat[0] || too_small) {
         /* a failed call leaves the stream where it was: the histories are put back, the lines of the call are not taken */
         if (n_seg > 0) { RT_CHECK(rt::d2d(t->d_state, t->d_state + 1, sizeof(sdvp16::State16), s)); RT_CHECK(rt::ssync(s)); }
@@ -343,26 +302,16 @@ int sdv_pcm16x0_stitch_frames(sdv_engine *e, const sdv_pcm16x0_bin_rec *lines, s
             return SDV_ERR_UNSUPPORTED;
         }
         set_error(e, "output buffers too small: " + std::to_string((unsigned long long)tot_pairs) + " sample pairs and " + std::to_string(tot_frames) + " frame descriptors are needed" +
-                     (t->vis_blocks ? ", " + std::to_string(t->vis_blocks_n) + " blocks for the visualiser" : std::string()) +
-                     (t->vis_lines ? ", " + std::to_string(t->vis_lines_n) + " assembled sub-line records" : std::string()));
+                     (t->vis_blocks.p ? ", " + std::to_string(t->vis_blocks.n) + " blocks for the visualiser" : std::string()) +
+                     (t->vis_lines.p ? ", " + std::to_string(t->vis_lines.n) + " assembled sub-line records" : std::string()));
         return SDV_ERR_BAD_ARG;
     }
     if (n_seg > 0) {            /* what the last frame left in conv_queue (State16::rem_n says how much of it counts) */
         const size_t n_batches = (n_seg + (size_t)SDV_P16_STITCH_BATCH - 1) / (size_t)SDV_P16_STITCH_BATCH;
         RT_CHECK(rt::d2d(t->d_rem, t->d_rem_slots + (n_batches - 1) * sdvp16::FRAME_SUBS, sdvp16::FRAME_SUBS * sizeof(sdvp16::Sub), s));
     }
-    const size_t keep_from = n_seg > 0 ? (size_t)last_end + 1 : 0, n_keep = total - keep_from;
-    if (n_keep > 0) {
-        RT_CHECK(t->d_carry_spare.reserve(n_keep, n_keep + n_keep / 2 + 1024));
-        size_t w = 0;
-        if (keep_from < t->n_carry) { RT_CHECK(rt::d2d(t->d_carry_spare, t->d_carry + keep_from, (t->n_carry - keep_from) * sizeof(sdv_pcm16x0_bin_rec), s)); w = t->n_carry - keep_from; }
-        const size_t from_lines = keep_from > t->n_carry ? keep_from - t->n_carry : 0;
-        if (from_lines < n_lines) RT_CHECK(rt::d2d(t->d_carry_spare + w, lines + from_lines, (n_lines - from_lines) * sizeof(sdv_pcm16x0_bin_rec), s));
-        RT_CHECK(rt::ssync(s));
-        t->d_carry.swap(t->d_carry_spare);
-    }
-    t->n_carry = n_keep;
-    return SDV_OK;
+    /* records after the last END_FRAME wait for the next call, like sub-lines in the reference's input queue */
+    return rs.keep_behind(e, n_seg > 0, last_end, lines, n_lines, s);
 }
 
 } // extern "C"

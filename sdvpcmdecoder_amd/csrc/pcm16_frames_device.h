@@ -29,26 +29,20 @@
 #define SDV_P16_ABLATE 0        /* developer aid: 1 no line decode, 2 no per-part bookkeeping, 3 no record store (outputs are wrong) */
 #endif
 #include "pcm16_bin_device.h"
-#include "pcm1_frames_device.h"
+#include "markerless_frames_device.h"
 
 namespace sdvp16f {
 using namespace sdv;
 using namespace sdvp16;
-using sdvp1f::PrescanRes;
-using sdvp1f::prescan_ref_of;
-using sdvp1f::frame_buf_lines;
-using sdvp1f::frame_buf_row;
-using sdvp1f::prescan_runs;
-using sdvp1f::ctx_for_line;
-using sdvp1f::COORD_CHECK_LINES;
-using sdvp1f::COORD_CHECK_PARTS;
-using sdvp1f::sweep_flag_matters;
+using namespace sdvmf;
 
 enum { P16_LINES_PF = 245 };                                    /* PCM16X0DataStitcher::LINES_PF, pcm16x0datastitcher.h:124 */
 enum { LV16 = COORD_HISTORY_DEPTH * P16_SUBLINES };             /* 27 */
 
 /* the chain state of a PCM-16x0 stream: sdv_v2d_state with a last-valid window of 27 (entries 9.. in `more`) */
 struct State16 { sdv_v2d_state s; sdv_coord more[LV16 - COORD_HISTORY_DEPTH]; };
+__device__ __forceinline__ sdv_v2d_state &v2d_of(State16 &s) { return s.s; }
+__device__ __forceinline__ const sdv_v2d_state &v2d_of(const State16 &s) { return s.s; }
 
 struct FrameArgs16 {
     FrameArgs f;                    /* geometry, flags, stats, scratch as for STC-007 (f.recs, f.states_in/out unused) */
@@ -72,7 +66,7 @@ __device__ inline void prescan_body(const FrameArgs16 &a16, Lds16 &lds, int f, i
         if (row >= 0) {
             sdvp1b::stage_row(lds.p.w.px, a.luma + (size_t)f * a.frame_stride + (size_t)row * a.row_stride, a.width);
             K1_T(tq1_); K1_ADD(16, tq0_, tq1_);
-            /* both values of the Binarizer's sticky sweep flag where it matters (pcm1_frames_device.h, PrescanRes) */
+            /* both values of the Binarizer's sticky sweep flag where it matters (markerless_frames_device.h, PrescanRes) */
             for (int variant = 0; variant < (sweep_flag_matters(a.preset) ? 2 : 1); variant++) {
                 BinCtx c; Bin b;
                 b.in_black = b.in_white = b.in_ref = 0; coords_clear(b.in_coord);
@@ -124,19 +118,8 @@ __device__ inline void load_state16(V2D16 &w, Lds16 &lds, const State16 *s, cons
     w.lw0 = w.lw1 = w.lw2 = 0;
 }
 
-__device__ inline bool link_holds16(const FrameArgs &a, int f, const State16 &out, State16 next_in)
-{
-    if (prescan_runs(a, f + 1)) next_in.s.bin = out.s.bin;             /* reset before it is read (prescanCoordinates :221) */
-    uint32_t x[sizeof(State16) / 4], y[sizeof(State16) / 4];
-    __builtin_memcpy(x, &out, sizeof(out));
-    __builtin_memcpy(y, &next_in, sizeof(next_in));
-    bool same = true;
-    for (unsigned i = 0; i < sizeof(State16) / 4; i++) same = same && (x[i] == y[i]);
-    return same;
-}
-
 /* The chain after frame f, a dword per lane (State16 is 48 dwords: the pattern of v2d_store_state, stc007_device.h - put together by one lane on the
- * stack it was the frame kernel's scratch memory); the link to frame f+1 is checked by the frame itself, as link_holds16 does. */
+ * stack it was the frame kernel's scratch memory); the link to frame f+1 is checked by the frame itself, as sdvmf::link_holds does. */
 __device__ inline uint32_t state16_half(const V2D16 &w, const Lds16 &lds, const FrameArgs &a, int h)
 {
     const V2D &v = w.v;
@@ -190,64 +173,12 @@ __device__ inline void store_state16(const V2D16 &w, const Lds16 &lds, const Fra
     if (lane == 0) a.flag[f] = fl;
 }
 
-__device__ inline void begin_frame16(V2D16 &w, const FrameArgs16 &a16, Lds16 &lds, int f)   /* :772-822 */
-{
-    const FrameArgs &a = a16.f;
-    V2D &v = w.v;
-    w.pre_variant = 0;
-    v.field_state = FIELD_NEW;
-    v.good_coords_in_field = v.pcm_lines_in_field = 0;
-    if (v.reset_stats) {
-        v.reset_stats = false;
-        v.n_last = v.nfv = v.nfi = v.n_long = 0;
-        coords_clear(v.frame_avg);
-        bin_set_good_parameters_reset(v.bin, a.preset);
-    }
-    coords_clear(v.frame_avg);
-    if (!a.preset.en_force_coords) {
-        if (prescan_runs(a, f)) {
-            bin_set_good_parameters_reset(v.bin, a.preset);
-            uint32_t keys[COORD_CHECK_LINES]; uint8_t refs[COORD_CHECK_LINES]; int n = 0;
-            for (int k = 0; k < COORD_CHECK_LINES; k++) {
-                const int variant = (sweep_flag_matters(a.preset) && v.bin.do_ref_lvl_sweep) ? 1 : 0;
-                w.pre_variant = (uint8_t)(w.pre_variant | (variant << k));
-                const PrescanRes r = a16.prescan[((size_t)variant * a.n_total + f) * COORD_CHECK_LINES + k];
-                if (uni(r.valid)) { keys[n] = uniu(coords_key(r.start, r.stop)); refs[n] = (uint8_t)uni(r.ref); n++; }
-                if (uni(r.pad[1])) v.bin.do_ref_lvl_sweep = a.mode == SDV_MODE_INSANE;
-            }
-            for (int i = 1; i < n; i++)
-                for (int j = i; j > 0; j--) {
-                    if (keys[j - 1] > keys[j]) { const uint32_t t = keys[j]; keys[j] = keys[j - 1]; keys[j - 1] = t; }
-                    if (refs[j - 1] > refs[j]) { const uint8_t t = refs[j]; refs[j] = refs[j - 1]; refs[j - 1] = t; }
-                }
-            if (n > 0) { v.frame_avg = key_to_coords(keys[n / 2], a.doubled != 0); w.prescan_ref = refs[n / 2]; }
-        }
-        if (!coords_valid(v.frame_avg)) { uint32_t k; if (median_keys(lds.p.w.long_keys, v.n_long, &k)) v.frame_avg = key_to_coords(k, a.doubled != 0); }
-        else v.bin.in_ref = w.prescan_ref;
-        if (coords_valid(v.frame_avg)) bin_set_data_coordinates2(v.bin, v.frame_avg.start, v.frame_avg.stop);
-    }
-}
-
-__device__ inline void set_good_parameters_p16(Bin &b, const sdv_bin_preset &ps, const L16 &l)   /* binarizer.cpp:353-377 */
-{
-    if (crc_valid_ignore_forced(l)) { b.in_ref = l.ref_level; bin_set_data_coordinates(b, l.coords); bin_set_bw_levels(b, ps, l.black, l.white); }
-}
-
 __device__ inline void service_line16(V2D16 &w, const FrameArgs &a, L16 &wl, uint8_t srv)       /* :1006-1114 */
 {
-    V2D &v = w.v;
     p16_clear(wl);
     set_service(wl, srv);
-    if (srv == SDV_SRV_NEW_FILE || srv == SDV_SRV_END_FILE) {
-        v.line_in_field_cnt = 0;
-        v.n_last = v.nfv = v.nfi = v.n_long = 0;
-        if (srv == SDV_SRV_END_FILE || !coords_valid(v.frame_avg)) bin_set_good_parameters_reset(v.bin, a.preset);
-    } else if (srv == SDV_SRV_END_FIELD) {
-        v.field_state = FIELD_NEW;
-        v.line_in_field_cnt = 0;
-        v.good_coords_in_field = 0; v.pcm_lines_in_field = 0;
-        w.lw0 = w.lw1 = w.lw2 = 0;
-    }
+    service_state(w.v, a, srv);
+    if (srv == SDV_SRV_END_FIELD) w.lw0 = w.lw1 = w.lw2 = 0;
 }
 
 /* one part of a regular line, after Binarizer::processLine: VideoToDigital :1115-1634 (PCM-16x0 branches) */
@@ -267,56 +198,31 @@ __device__ inline void post_part16(V2D16 &w, const FrameArgs &a, Lds16 &lds, L16
         v.q_line_length = (uint16_t)a.width;
         if (a.check_line_copy) {
             if (v.field_state == FIELD_UNSAFE) {
-                set_good_parameters_p16(v.bin, ps, wl);
+                set_good_parameters(v.bin, ps, wl);
                 if (ps.en_first_line_dup) { wl.forced_bad = true; force_bad_line = true; }
             } else {
                 const uint64_t lw = pick3_u64(part, w.lw0, w.lw1, w.lw2);
                 const int diff = __popcll(((wl.v >> 16) ^ lw) & 0x00FF00FF00FFull);     /* per word the XOR is truncated to uint8_t */
                 const int16_t s0 = (int16_t)get_word(wl, 0), s2 = (int16_t)get_word(wl, 2);
                 const bool almost_silent = (!(s0 >= 4) && !(s0 < -4)) || (!(s2 >= 4) && !(s2 < -4));                      /* pcm16x0subline.cpp:291-318 */
-                if (!almost_silent && diff <= (P16_DATA / BIT_DIFF_THRES_DIV)) { wl.forced_bad = true; if (!even_line) v.q_dup_odd++; else v.q_dup_even++; }
+                if (!almost_silent && diff <= (P16_DATA / BIT_DIFF_THRES_DIV)) { wl.forced_bad = true; count_dup(v, even_line); }
             }
         }
         if (crc_valid_ignore_forced(wl)) {
             const uint32_t key = coords_key(wl.coords.start, wl.coords.stop);
-            SDV_WAVE_SYNC();
-            {   /* the window moves up by one when it is full: every lane carries one entry (no serial chain through LDS) */
-                const int ln = lane_id();
-                const bool full = v.n_last == LV16;
-                const uint32_t moved = (full && ln < LV16 - 1) ? lds.lv_keys16[ln + 1] : 0u;
-                SDV_WAVE_SYNC();
-                if (full && ln < LV16 - 1) lds.lv_keys16[ln] = moved;
-                if (ln == 0) lds.lv_keys16[full ? LV16 - 1 : v.n_last] = key;
-            }
-            if (v.n_last < LV16) v.n_last++;
-            SDV_WAVE_SYNC();
+            push_last_valid<LV16>(lds.lv_keys16, v, key);
             fv_keys[v.nfv++] = key;
-            if (a.coordinate_damper && !ps.en_force_coords && (v.n_last > (COORD_HISTORY_DEPTH / 2))) {
-                Coords target; coords_clear(target);
-                uint32_t k;
-                if (median_keys(lds.lv_keys16, v.n_last, &k)) target = key_to_coords(k, false);
-                if (!coords_valid(target)) target = v.frame_avg;
-                if (coords_valid(target)) {
-                    const int16_t ds = (int16_t)(wl.coords.start - target.start), de = (int16_t)(wl.coords.stop - target.stop);
-                    const uint8_t in_delta = (uint8_t)(get_ppb(wl) * 3);
-                    if (((int)ds <= -(int)in_delta) || ((int)ds >= (int)in_delta) || ((int)de <= -(int)in_delta) || ((int)de >= (int)in_delta)) { wl.forced_bad = true; force_bad_line = true; }
-                }
-            }
+            if (damper_forces_bad(v, a, lds.lv_keys16, wl)) { wl.forced_bad = true; force_bad_line = true; }
         }
-        if (crc_valid(wl)) set_good_parameters_p16(v.bin, ps, wl);
-        else { if (!even_line) v.q_bad_odd++; else v.q_bad_even++; }
+        if (crc_valid(wl)) set_good_parameters(v.bin, ps, wl);
+        else count_bad(v, even_line);
         if (part == 2) v.field_state = FIELD_INIT;
     } else {
         if (v.q_line_length == 0) v.q_line_length = (uint16_t)a.width;
         if (coords_valid(wl.coords)) fi_keys[v.nfi++] = coords_key(wl.coords.start, wl.coords.stop);
         if (count_has_data) {
-            Coords preset_coords; coords_clear(preset_coords);
-            if (!even_line) v.q_bad_odd++; else v.q_bad_even++;
-            if (!ps.en_force_coords) {
-                uint32_t k;
-                if (median_keys(lds.lv_keys16, v.n_last, &k)) preset_coords = key_to_coords(k, a.doubled != 0);
-                if (!coords_valid(preset_coords)) preset_coords = v.frame_avg;
-            }
+            count_bad(v, even_line);
+            const Coords preset_coords = preset_behind_unreadable(v, a, lds.lv_keys16);
             if (part == 2) {
                 v.field_state = FIELD_INIT;
                 bin_set_data_coordinates(v.bin, preset_coords);
@@ -331,21 +237,12 @@ __device__ inline void post_part16(V2D16 &w, const FrameArgs &a, Lds16 &lds, L16
             bin_set_bw_levels(v.bin, ps, 0, 0);
         }
     }
-    if (!even_line) v.q_odd++; else v.q_even++;
-    if (count_has_pcm) {
-        if (!even_line) v.q_pcm_odd++; else v.q_pcm_even++;
-        v.pcm_lines_in_field++;
+    count_line(v, even_line, count_has_pcm, [&w, &wl, part]() __attribute__((always_inline)) {
         const uint64_t nw = wl.v >> 16;
         w.lw0 = part == 0 ? nw : w.lw0; w.lw1 = part == 1 ? nw : w.lw1; w.lw2 = part == 2 ? nw : w.lw2;
-    }
-    v.line_in_field_cnt++;
+    });
 }
 
-#ifdef SDV_EMU
-__device__ inline uint32_t lane_read32(uint32_t x, uint32_t idx) { return (uint32_t)__shfl((int)x, (int)idx); }
-#else
-__device__ inline uint32_t lane_read32(uint32_t x, uint32_t idx) { return (uint32_t)__builtin_amdgcn_readlane((int)x, (int)uniu(idx)); }
-#endif
 /* ---- the tape plays: a part that reads from what its predecessor left preset ------------------------------------------------------- */
 /* Binarizer::processLine for a part whose levels, reference level and coordinates are preset and that reads valid on the first rung of
  * the ladder (hysteresis 0, shift 0) is stage STG_INPUT_ALL and nothing else (binarizer.cpp:774-931): one LDS byte per lane, two ballots,
@@ -353,51 +250,17 @@ __device__ inline uint32_t lane_read32(uint32_t x, uint32_t idx) { return (uint3
  * lane samples in each of the three parts, the levels with their clipping test, the cut-off counts - is kept while the tuning stays the
  * same (on a tape that plays: for the whole frame).  Anything else - no complete presets, forced coordinates, a part that does not read
  * at once - goes through process_line_p16 from the start. */
-struct Lean16 {
-    uint32_t key_coords, key_levels;        /* what `x` etc. were computed for; key_levels = 0xFFFFFFFF: nothing yet */
-    uint16_t x0, x1, x2, x_ctrl;            /* lane's pixel in the left / middle / right part (named members: an array indexed by the part puts the frame's state into scratch memory); the Control Bit's pixel */
-    uint8_t low, high, bits_l, bits_r;
-    bool usable;
-    uint32_t psm, hpsm; int16_t pso;
-};
-__device__ inline void lean16_reset(Lean16 &n) { n.key_levels = 0xFFFFFFFFu; n.key_coords = 0; n.usable = false; }
+/* the tuning of sdvmf::LeanBase and lane's pixel in the left / middle / right part (named members: an array indexed by the part puts the frame's state
+ * into scratch memory); the Control Bit's pixel */
+struct Lean16 : LeanBase { uint16_t x0, x1, x2, x_ctrl; };
 /* true when parts can be read the lean way under the tuning in b (and n describes that tuning) */
 __device__ inline bool lean16_prepare(Lean16 &n, const BinCtx &c, const Bin &b)
 {
-    if (c.ps.en_force_coords) return false;
-    if (!(are_bw_levels_preset(b, c.ps) && is_ref_level_preset(b, c.ps) && coords_valid(b.in_coord))) return false;
-    if (!(b.in_ref < b.in_white && b.in_ref > b.in_black)) return false;
-    if (!(c.scan_end > c.scan_start && P16_BITS <= (c.scan_end - c.scan_start))) return false;
-    const uint32_t kc = coords_key(b.in_coord.start, b.in_coord.stop) , kl = (uint32_t)b.in_black | ((uint32_t)b.in_white << 8) | ((uint32_t)b.in_ref << 16) | ((uint32_t)(b.in_coord.doubled ? 1 : 0) << 24);
-    if (kc != n.key_coords || kl != n.key_levels) {
-        n.key_coords = kc; n.key_levels = kl;
-        L16 t; p16_clear(t);
-        t.pixel_start = c.scan_start; t.pixel_stop = c.scan_end;
-        t.coords = b.in_coord;
-        set_ppb(t, t.coords);
-        n.psm = t.psm; n.hpsm = t.hpsm; n.pso = t.pso;
+    return lean_prepare<L16, P16_BITS>(n, c, b, [&n](const L16 &t) {
         const int lane = lane_id();
         n.x0 = (uint16_t)pixel_of(t, part_start_bit((uint8_t)PART_LEFT) + lane, 0); n.x1 = (uint16_t)pixel_of(t, part_start_bit((uint8_t)PART_MIDDLE) + lane, 0); n.x2 = (uint16_t)pixel_of(t, part_start_bit((uint8_t)PART_RIGHT) + lane, 0);
         n.x_ctrl = (uint16_t)pixel_of(t, 2 * P16_DATA, 0);
-        n.low = get_low_level(b.in_ref, 0); n.high = get_high_level(b.in_ref, 0);
-        n.usable = !(n.low <= b.in_black) && !(n.high >= b.in_white);
-        /* pickCutBitsUpPCM16X0 (binarizer.cpp:6599-7013): how many cells the picture cuts off at either end */
-        t.black = b.in_black; t.white = b.in_white; t.ref_level = b.in_ref;
-        for (int side = 0; side < 2; side++) {
-            const bool left = side == 0;
-            int max_cut = left ? c.ps.left_bit_pick : c.ps.right_bit_pick; if (c.mode == SDV_MODE_DRAFT) max_cut /= 2;
-            int first = left ? c.scan_start : c.scan_end, bits = 0;
-            const int half_ppb = ((int)get_ppb(t) + 1) / 2;
-            for (int i = 0; i < max_cut; i++) {
-                const int cur = pixel_of(t, left ? i : P16_BITS - 1 - i, 0);
-                if ((left ? (cur - first) : (first - cur)) >= half_ppb) break;
-                if (i == 0) first = cur;
-                bits = i + 1;
-            }
-            if (left) n.bits_l = (uint8_t)bits; else n.bits_r = (uint8_t)bits;
-        }
-    }
-    return n.usable && c.force_bit_picker;
+    });
 }
 __device__ inline bool lean_part16(Lean16 &n, const BinCtx &c, const Bin &b, uint8_t part, const uint8_t *px_row, L16 &out)
 {
@@ -469,7 +332,7 @@ __device__ inline int batch16(V2D16 &w, const FrameArgs16 &a16, Lds16 &lds, cons
 #pragma unroll
         for (int d = 0; d < D; d++) {
             const uint32_t o = (uint32_t)(d < n_lines ? d : n_lines - 1) * rs2;
-            q[d][0] = sdvp1f::lean_load_u8(row0 + (o + x0)); q[d][1] = sdvp1f::lean_load_u8(row0 + (o + x1)); q[d][2] = sdvp1f::lean_load_u8(row0 + (o + x2)); q[d][3] = sdvp1f::lean_load_u8(row0 + (o + xc));
+            q[d][0] = lean_load_u8(row0 + (o + x0)); q[d][1] = lean_load_u8(row0 + (o + x1)); q[d][2] = lean_load_u8(row0 + (o + x2)); q[d][3] = lean_load_u8(row0 + (o + xc));
         }
         uint32_t ra0 = 0, ra1 = 0, rb0 = 0, rb1 = 0;
         for (int j0 = 0; j0 < n_lines; j0 += D) {
@@ -481,7 +344,7 @@ __device__ inline int batch16(V2D16 &w, const FrameArgs16 &a16, Lds16 &lds, cons
                 const uint32_t cbit = uniu(pc < ref ? 0u : 1u);
                 {
                     const int jn = j + D < n_lines ? j + D : n_lines - 1; const uint32_t o = (uint32_t)jn * rs2;
-                    q[d][0] = sdvp1f::lean_load_u8(row0 + (o + x0)); q[d][1] = sdvp1f::lean_load_u8(row0 + (o + x1)); q[d][2] = sdvp1f::lean_load_u8(row0 + (o + x2)); q[d][3] = sdvp1f::lean_load_u8(row0 + (o + xc));
+                    q[d][0] = lean_load_u8(row0 + (o + x0)); q[d][1] = lean_load_u8(row0 + (o + x1)); q[d][2] = lean_load_u8(row0 + (o + x2)); q[d][3] = lean_load_u8(row0 + (o + xc));
                 }
                 ra0 = write_lane(ra0, (uint32_t)a0, 3 * j); ra1 = write_lane(ra1, (uint32_t)(a0 >> 32), 3 * j); rb0 = write_lane(rb0, (uint32_t)b0, 3 * j); rb1 = write_lane(rb1, (uint32_t)(b0 >> 32), 3 * j);
                 ra0 = write_lane(ra0, (uint32_t)a1, 3 * j + 1); ra1 = write_lane(ra1, (uint32_t)(a1 >> 32), 3 * j + 1); rb0 = write_lane(rb0, (uint32_t)b1, 3 * j + 1); rb1 = write_lane(rb1, (uint32_t)(b1 >> 32), 3 * j + 1);
@@ -588,12 +451,11 @@ __device__ inline void frame_body16(const FrameArgs16 &a16, Lds16 &lds, int f)
     const uint8_t *frame = a.luma + (size_t)f * a.frame_stride;
     uint32_t *fv_keys = a.scratch + (size_t)f * 6u * (size_t)a.height;         /* three sub-lines per line, valid + invalid lists */
     uint32_t *fi_keys = fv_keys + 3 * a.height;
-    size_t rec_base = (size_t)f * (size_t)(3 * a.height + 3);
-    if (a.new_file_frame >= 0 && f > a.new_file_frame) rec_base += 1;
-    sdv_pcm16x0_bin_rec *rec = a16.recs16 + rec_base;
+    sdv_pcm16x0_bin_rec *rec = a16.recs16 + rec_base(a, f, P16_SUBLINES);
     const bool doubled = a.doubled != 0;
 
-    begin_frame16(w, a16, lds, f);
+    w.pre_variant = 0;
+    begin_frame(v, w.prescan_ref, a, a16.prescan, lds.p.w.long_keys, f, [&w](int k, int variant) { w.pre_variant = (uint8_t)(w.pre_variant | (variant << k)); });
     /* the rows the prescan has read: their VideoLine carries scan_done into the main pass */
     int pre_row[COORD_CHECK_LINES]; bool pre_done[COORD_CHECK_LINES];
     for (int k = 0; k < COORD_CHECK_LINES; k++) { pre_row[k] = -1; pre_done[k] = false; }
@@ -603,7 +465,7 @@ __device__ inline void frame_body16(const FrameArgs16 &a16, Lds16 &lds, int f)
     }
     const int n_field[2] = { (a.height + 1) / 2, a.height / 2 };
     uint16_t line_num = 0;
-    Lean16 lean; lean16_reset(lean);
+    Lean16 lean; lean_reset(lean);
     const bool empty_frame = frame_is_empty(a, f);
 #if SDV_P16_STAMPS && !defined(SDV_EMU)
     unsigned long long p16_stamp[4] = { 0, 0, 0, 0 };
@@ -689,12 +551,7 @@ __device__ inline void frame_body16(const FrameArgs16 &a16, Lds16 &lds, int f)
     v.q_odd = v.q_even = P16_LINES_PF;                                  /* :1643-1652 */
     v.q_pcm_odd = (uint16_t)(v.q_pcm_odd / P16_SUBLINES); v.q_pcm_even = (uint16_t)(v.q_pcm_even / P16_SUBLINES);
     v.q_bad_odd = (uint16_t)(v.q_bad_odd / P16_SUBLINES); v.q_bad_even = (uint16_t)(v.q_bad_even / P16_SUBLINES);
-    {   /* the median of the frame's valid coordinates is what v2d_end_frame pushes into long_valid_coords (:1668-1682) */
-        __syncthreads();        /* (keys stored to global memory by other lanes than the ones that read them now) */
-        uint32_t mk = 0; bool pushed = median_keys(fv_keys, v.nfv, &mk);
-        if (pushed) { const Coords mc = key_to_coords(mk, false); pushed = coords_valid(mc); }
-        if (lane_id() == 0) { uint2 m; m.x = pushed ? mk : 0u; m.y = pushed ? 1u : 0u; a16.frame_med[f] = m; }
-    }
+    store_frame_median(a16.frame_med, f, fv_keys, v.nfv);
     v2d_end_frame(v, a, lds.p.w, frame_no, fv_keys, fi_keys, &a.stats[f]);
     emit_rec(wl, frame_no, line_num, false, rec++);
     store_state16(w, lds, a16, f);
@@ -708,29 +565,7 @@ __device__ inline void frame_body16(const FrameArgs16 &a16, Lds16 &lds, int f)
 #ifndef SDV_P16_WAVES_PER_EU
 #define SDV_P16_WAVES_PER_EU 3
 #endif
-/* two builds of the two kernels: MODE_INSANE (with the reference level sweep) and every other mode (process_line_p1) */
-#define SDV_P16F_KERNELS(SUFFIX, INSANE) \
-__global__ void __launch_bounds__(64, SDV_P16_WAVES_PER_EU) sdv_k_pcm16_prescan##SUFFIX(sdvp16f::FrameArgs16 a) \
-{ \
-    __shared__ sdvp16f::Lds16 lds; \
-    const int i = (int)blockIdx.x, f = a.f.frame_list ? a.f.frame_list[i / sdvp16f::COORD_CHECK_LINES] : a.f.frame_lo + i / sdvp16f::COORD_CHECK_LINES; \
-    sdvp16f::prescan_body<INSANE>(a, lds, f, i % sdvp16f::COORD_CHECK_LINES); \
-} \
-__global__ void __launch_bounds__(64, SDV_P16_WAVES_PER_EU) sdv_k_pcm16_frames_bin##SUFFIX(sdvp16f::FrameArgs16 a) \
-{ \
-    __shared__ sdvp16f::Lds16 lds; \
-    const int f = a.f.frame_list ? a.f.frame_list[blockIdx.x] : a.f.frame_lo + (int)blockIdx.x; \
-    sdvp16f::frame_body16<INSANE>(a, lds, f); \
-}
-SDV_P16F_KERNELS(, false)
-SDV_P16F_KERNELS(_insane, true)
 #ifndef SDV_P16F_LEAN_WAVES_PER_EU
 #define SDV_P16F_LEAN_WAVES_PER_EU 4
 #endif
-/* the lean build of the frame kernel (every mode: what it holds - parts that read from what they inherit - is the same in all of them) */
-__global__ void __launch_bounds__(64, SDV_P16F_LEAN_WAVES_PER_EU) sdv_k_pcm16_frames_lean(sdvp16f::FrameArgs16 a)
-{
-    __shared__ sdvp16f::Lds16 lds;
-    const int f = a.f.frame_list ? a.f.frame_list[blockIdx.x] : a.f.frame_lo + (int)blockIdx.x;
-    sdvp16f::frame_body16<false, true>(a, lds, f);
-}
+SDV_MLF_KERNELS(pcm16, sdvp16f::FrameArgs16, sdvp16f::Lds16, sdvp16f::prescan_body, sdvp16f::frame_body16, SDV_P16_WAVES_PER_EU, SDV_P16_WAVES_PER_EU, SDV_P16F_LEAN_WAVES_PER_EU)

@@ -38,13 +38,8 @@ extern "C" int sdv_pcm16x0_binarize_lines(sdv_engine *e, const uint8_t *luma, si
                                           const sdv_bin_state *presets, uint32_t frame_number, uint16_t first_line, uint16_t line_step,
                                           unsigned flags, int coord_search, sdv_pcm16x0_bin_rec *out_lines, size_t lines_cap, uint8_t *out_scan_done, void *stream)
 {
-    if (!e) return SDV_ERR_BAD_ARG;
-    if (!luma) { set_error(e, "null video"); return SDV_ERR_NULL_VIDEO; }
-    if (!out_lines) { set_error(e, "null output"); return SDV_ERR_NULL_PCM; }
-    if (width <= 0 || width > SDV_PX_BYTES || row_stride < (size_t)width) { set_error(e, "bad line geometry"); return SDV_ERR_BAD_ARG; }
-    if (width < sdvp16::P16_BITS) { set_error(e, "line shorter than the 193 bit cells of a PCM-16x0 line"); return SDV_ERR_SHORT_LINE; }
-    if (n_lines == 0) return SDV_OK;
-    if (lines_cap / 3 < n_lines) { set_error(e, "output buffer too small: " + std::to_string(3 * n_lines) + " sub-line records are needed"); return SDV_ERR_BAD_ARG; }
+    bool todo = false;
+    { const int rc = check_lines_call<Pcm16Frames>(e, luma, row_stride, width, n_lines, out_lines, lines_cap, &todo); if (rc != SDV_OK || !todo) return rc; }
     SDV_ON_DEVICE(e);
     sdvp16::LineArgs16 a;
     memset(&a, 0, sizeof(a));

@@ -44,7 +44,7 @@ enum { IBLK_DELIM = 45, MAX_PAD_SI = 35, MAX_PAD_EI = 81, MAX_SIL_SI = 34, MAX_S
 enum { BIT_EMPH = 0, BIT_RATE = 3, BIT_MODE = 6, BIT_CODE = 9 };
 enum { DS_NO_DATA, DS_SILENCE, DS_BROKE, DS_NO_PAD, DS_OK };
 enum { ORDER_TFF = 1, ORDER_BFF = 2 };
-enum { FF_NEW_FILE = 1, FF_END_FILE = 2 };
+using sdvss::FF_NEW_FILE; using sdvss::FF_END_FILE;
 /* reasons a frame cannot be stitched by this engine */
 enum { FE_FOREIGN = 1, FE_TOO_LONG = 2, FE_MARKS = 16 };
 
@@ -90,38 +90,12 @@ __device__ inline Sub compact(const sdv_pcm16x0_bin_rec &r, uint32_t frame, uint
     return s;
 }
 
-struct RecSrc16 {
-    const sdv_pcm16x0_bin_rec *carry; uint32_t n_carry; const sdv_pcm16x0_bin_rec *recs;
-    __device__ inline const sdv_pcm16x0_bin_rec &at(uint32_t i) const { return i < n_carry ? carry[i] : recs[i - n_carry]; }
-};
+typedef sdvss::RecSrc<sdv_pcm16x0_bin_rec> RecSrc16;
 struct Cfg16 { uint8_t format, field_order, p_correction, ignore_crc, mask_seams, broke_mask; uint16_t sample_rate_preset; };
 
-/* ---- segments (as for PCM-1: END_FRAME positions, file tags per segment) ------------------------------------------------ */
-struct SegArgs16 { RecSrc16 src; uint32_t n_recs; uint8_t *svc; uint32_t *block_count; const uint32_t *block_ofs; uint32_t *seg_end; uint32_t n_seg; uint32_t *marks; uint32_t *stat; int write; };
+/* ---- segments (stitch_stream_device.h) ------------------------------------------------------------------------------------- */
+struct SegArgs16 : sdvss::SegArgs<sdv_pcm16x0_bin_rec> {};    /* (a type of its own: the kernel's symbol stays as it was) */
 enum { SEG_CHUNK16 = 1024 };
-__device__ inline void seg_body(const SegArgs16 &a, uint32_t blk, int lane)
-{
-    const uint32_t lo = blk * SEG_CHUNK16;
-    uint32_t hi = lo + SEG_CHUNK16; if (hi > a.n_recs) hi = a.n_recs;
-    uint32_t cnt = 0;
-    const uint32_t base = a.write ? a.block_ofs[blk] : 0u;
-    for (uint32_t c = lo; c < hi; c += 64) {
-        const uint32_t i = c + (uint32_t)lane;
-        uint8_t srv = SDV_SRV_NO;
-        if (i < hi) { if (a.write) srv = a.svc[i]; else { srv = a.src.at(i).service_type; a.svc[i] = srv; } }
-        const uint64_t m = __ballot(srv == SDV_SRV_END_FRAME);
-        if (a.write) {
-            const uint32_t seg = base + cnt + (uint32_t)__popcll(m & lanemask_lt(lane));
-            if (srv == SDV_SRV_END_FRAME) a.seg_end[seg] = i;
-            else if ((srv == SDV_SRV_NEW_FILE || srv == SDV_SRV_END_FILE) && seg < a.n_seg) {
-                atomicOr(&a.marks[seg], srv == SDV_SRV_NEW_FILE ? (uint32_t)FF_NEW_FILE : (uint32_t)FF_END_FILE);
-                atomicAdd(&a.stat[2], 1u);
-            }
-        }
-        cnt += (uint32_t)__popcll(m);
-    }
-    if (!a.write && lane == 0) a.block_count[blk] = cnt;
-}
 /* ---- PCM16X0DataBlock + PCM16X0Deinterleaver::processBlock on three sub-lines ----------------------------------------------- */
 enum { L1 = 0, L2 = 1, L3 = 2, W_L = 0, W_R = 1, W_P = 2 };
 enum { AUD_ORIG, AUD_FIX_P, AUD_BROKEN };
@@ -1840,7 +1814,7 @@ __device__ inline void emit_body(const FrameArgs16s &a, uint32_t kb, int lane)
 }
 } // namespace sdvp16
 
-__global__ void __launch_bounds__(64) sdv_k_pcm16_segments(sdvp16::SegArgs16 a) { sdvp16::seg_body(a, blockIdx.x, (int)threadIdx.x); }
+__global__ void __launch_bounds__(64) sdv_k_pcm16_segments(sdvp16::SegArgs16 a) { sdvss::seg_body<sdv_pcm16x0_bin_rec, sdvp16::SEG_CHUNK16>(a, blockIdx.x, (int)threadIdx.x); }
 __global__ void __launch_bounds__(64) sdv_k_pcm16_analyse(sdvp16::FrameArgs16s a)
 {
     __shared__ sdvp16::AnaLds lds;

@@ -16,21 +16,14 @@
  *                        the model of the states: markerless_chain_device.h).
  */
 #pragma once
-#include "pcm1_bin_device.h"
+#include "markerless_frames_device.h"
 
 namespace sdvp1f {
 using namespace sdv;
 using namespace sdvp1b;
+using namespace sdvmf;
 
-enum { COORD_CHECK_LINES = 4, COORD_CHECK_PARTS = COORD_CHECK_LINES + 2 };      /* videotodigital.h:101-102 */
 enum { P1_LINES_PF = 245 };                                                     /* PCM1DataStitcher::LINES_PF, pcm1datastitcher.h:103 */
-
-struct PrescanRes { int16_t start, stop; uint8_t ref, valid, pad[2]; };         /* one prescan line: the coordinates and level it read valid with */
-/* pad[1]: the line found levels, i.e. it went through binarizer.cpp:1104 and left Binarizer::do_ref_lvl_sweep at "the mode is MODE_INSANE".
- * That member is the one thing a prescan line takes over from whatever the Binarizer did before (it enters the level validation, :3409),
- * and it only matters when min_valid_crcs > min_contrast: then every prescan line is decoded for both values of it (second half of the
- * array) and the frame picks, line after line, the variant its own flag calls for. */
-__device__ __forceinline__ bool sweep_flag_matters(const sdv_bin_preset &ps) { return ps.min_valid_crcs > ps.min_contrast; }
 
 struct FrameArgs1 {
     FrameArgs f;                    /* geometry, flags, states, stats, scratch as for STC-007 (f.recs unused) */
@@ -38,39 +31,6 @@ struct FrameArgs1 {
     PrescanRes *prescan;            /* [n_total][COORD_CHECK_LINES] */
     uint2 *frame_med;               /* [n_total] what frame f pushed into the multi-frame history: {coordinate key, 1} or {0, 0} (nothing) */
 };
-
-/* sdv_v2d_state::_pad[1] carries prescan_ref (videotodigital.cpp:703, 730: a local of the worker, 128 at its start) as its distance
- * from 128, so that an all-zero pad is the fresh worker for every format */
-__device__ __forceinline__ uint8_t prescan_ref_of(const sdv_v2d_state &s) { return (uint8_t)(s._pad[1] ^ 128); }
-
-/* lines in the frame buffer of frame f (waitForOneFrame, :84-145): the rows, END_FIELD twice, END_FRAME, the NEW_FILE line in
- * front of a file's first frame, END_FILE in the filler frame behind its last */
-__device__ __forceinline__ int frame_buf_lines(const FrameArgs &a, int f) { return a.height + 3 + (f == a.new_file_frame ? 1 : 0) + (f == a.end_file_frame ? 1 : 0); }
-/* does the worker prescan frame f? (prescanCoordinates :171-200, called in every mode but DRAFT, :796-801) */
-__device__ __forceinline__ bool prescan_runs(const FrameArgs &a, int f)
-{
-    return !a.preset.en_force_coords && a.mode != SDV_MODE_DRAFT && frame_buf_lines(a, f) > COORD_CHECK_PARTS;
-}
-/* row of the picture at index i of frame f's buffer, or -1 for a service line */
-__device__ inline int frame_buf_row(const FrameArgs &a, int f, int i)
-{
-    if (f == a.end_file_frame) return -1;                   /* FILLER lines carry no pixels */
-    if (frame_is_empty(a, f)) return -1;                    /* nor do the lines of a dropped frame */
-    if (f == a.new_file_frame) { if (i == 0) return -1; i--; }
-    const int n0 = (a.height + 1) / 2, n1 = a.height / 2;
-    if (i < n0) return 2 * i;
-    i -= n0 + 1;
-    if (i >= 0 && i < n1) return 2 * i + 1;
-    return -1;
-}
-
-__device__ inline void ctx_for_line(const FrameArgs &a, BinCtx &c, Bin &b)
-{
-    c.ps = a.preset; c.mode = a.mode; c.scan_start = 0; c.scan_end = (uint16_t)(a.width - 1);
-    c.force_bit_picker = true;      /* binarizer.cpp:82 */
-    bin_set_mode(b, a.mode);
-    b.scan_start = c.scan_start; b.scan_end = c.scan_end; b.vl_doubled = a.doubled != 0;
-}
 
 /* ---- prescan: block = (frame, k) ------------------------------------------------------------------------------------------ */
 template <bool kInsane>
@@ -121,20 +81,6 @@ __device__ inline void v2d1_load_state(V2D1 &w, WaveLds &lds, const sdv_v2d_stat
     w.prescan_ref = (uint8_t)uni(prescan_ref_of(*s));
 }
 
-/* Was frame f+1 started from what frame f handed on?  Like for STC-007 (byte for byte), with one difference: when the worker
- * prescans frame f+1 it resets its Binarizer first (prescanCoordinates :221), so what frame f left preset there does not reach
- * frame f+1 and does not count. */
-__device__ inline bool link_holds1(const FrameArgs &a, int f, const sdv_v2d_state &out, sdv_v2d_state next_in)
-{
-    if (prescan_runs(a, f + 1)) next_in.bin = out.bin;
-    uint32_t x[sizeof(sdv_v2d_state) / 4], y[sizeof(sdv_v2d_state) / 4];
-    __builtin_memcpy(x, &out, sizeof(out));
-    __builtin_memcpy(y, &next_in, sizeof(next_in));
-    bool same = true;
-    for (unsigned i = 0; i < sizeof(sdv_v2d_state) / 4; i++) same = same && (x[i] == y[i]);
-    return same;
-}
-
 /* The chain after frame f; the link to frame f+1 is checked by the frame itself: when the worker prescans frame
  * f+1 it resets its Binarizer first (prescanCoordinates :221), so what frame f left preset there does not reach frame f+1 and does
  * not count. */
@@ -162,68 +108,16 @@ __device__ inline void v2d1_store_state(const V2D1 &w, const WaveLds &lds, sdv_v
     o._pad[0] = 0; o._pad[1] = (uint8_t)(w.prescan_ref ^ 128);
     *s = o;
     const int f = (int)(s - a.states_out);
-    a.flag[f] = (f + 1 < a.n_total && !link_holds1(a, f, o, a.states_in[f + 1])) ? VF_BREAK : VF_OK;
-}
-
-/* :772-822 start-of-frame work, with the prescan results of this frame */
-__device__ inline void v2d1_begin_frame(V2D1 &w, const FrameArgs1 &a1, WaveLds &lds, int f)
-{
-    const FrameArgs &a = a1.f;
-    V2D &v = w.v;
-    v.field_state = FIELD_NEW;
-    v.good_coords_in_field = v.pcm_lines_in_field = 0;
-    if (v.reset_stats) {
-        v.reset_stats = false;
-        v.n_last = v.nfv = v.nfi = v.n_long = 0;
-        coords_clear(v.frame_avg);
-        bin_set_good_parameters_reset(v.bin, a.preset);
-    }
-    coords_clear(v.frame_avg);
-    if (!a.preset.en_force_coords) {
-        if (prescan_runs(a, f)) {
-            bin_set_good_parameters_reset(v.bin, a.preset);                             /* :221 */
-            /* the lines that read valid, sorted like std::sort under CoordinatePair::operator< / by level; the middle ones (:322-336) */
-            uint32_t keys[COORD_CHECK_LINES]; uint8_t refs[COORD_CHECK_LINES]; int n = 0;
-            for (int k = 0; k < COORD_CHECK_LINES; k++) {
-                const int variant = (sweep_flag_matters(a.preset) && v.bin.do_ref_lvl_sweep) ? 1 : 0;
-                const PrescanRes r = a1.prescan[((size_t)variant * a.n_total + f) * COORD_CHECK_LINES + k];
-                if (uni(r.valid)) { keys[n] = uniu(coords_key(r.start, r.stop)); refs[n] = (uint8_t)uni(r.ref); n++; }
-                if (uni(r.pad[1])) v.bin.do_ref_lvl_sweep = a.mode == SDV_MODE_INSANE;
-            }
-            for (int i = 1; i < n; i++)
-                for (int j = i; j > 0; j--) {
-                    if (keys[j - 1] > keys[j]) { const uint32_t t = keys[j]; keys[j] = keys[j - 1]; keys[j - 1] = t; }
-                    if (refs[j - 1] > refs[j]) { const uint8_t t = refs[j]; refs[j] = refs[j - 1]; refs[j - 1] = t; }
-                }
-            if (n > 0) { v.frame_avg = key_to_coords(keys[n / 2], a.doubled != 0); w.prescan_ref = refs[n / 2]; }
-        }
-        if (!coords_valid(v.frame_avg)) { uint32_t k; if (median_keys(lds.long_keys, v.n_long, &k)) v.frame_avg = key_to_coords(k, a.doubled != 0); }
-        else v.bin.in_ref = w.prescan_ref;                                              /* setReferenceLevel(prescan_ref) */
-        if (coords_valid(v.frame_avg)) bin_set_data_coordinates2(v.bin, v.frame_avg.start, v.frame_avg.stop);
-    }
-}
-
-__device__ inline void set_good_parameters_p1(Bin &b, const sdv_bin_preset &ps, const L1 &l)   /* binarizer.cpp:353-377 */
-{
-    if (crc_valid_ignore_forced(l)) { b.in_ref = l.ref_level; bin_set_data_coordinates(b, l.coords); bin_set_bw_levels(b, ps, l.black, l.white); }
+    a.flag[f] = (f + 1 < a.n_total && !link_holds(a, f, o, a.states_in[f + 1])) ? VF_BREAK : VF_OK;
 }
 
 /* service lines: Binarizer::processLine :539-568 + VideoToDigital :1006-1114 */
 __device__ inline void v2d1_service_line(V2D1 &w, const FrameArgs &a, L1 &wl, uint8_t srv)
 {
-    V2D &v = w.v;
     p1_clear(wl);
     set_service(wl, srv);
-    if (srv == SDV_SRV_NEW_FILE || srv == SDV_SRV_END_FILE) {
-        v.line_in_field_cnt = 0;
-        v.n_last = v.nfv = v.nfi = v.n_long = 0;
-        if (srv == SDV_SRV_END_FILE || !coords_valid(v.frame_avg)) bin_set_good_parameters_reset(v.bin, a.preset);
-    } else if (srv == SDV_SRV_END_FIELD) {
-        v.field_state = FIELD_NEW;
-        v.line_in_field_cnt = 0;
-        v.good_coords_in_field = 0; v.pcm_lines_in_field = 0;
-        for (int i = 0; i < 8; i++) v.last_words[i] = 0;           /* last_pcm1_line.clear(): the data words are zero */
-    }
+    service_state(w.v, a, srv);
+    if (srv == SDV_SRV_END_FIELD) for (int i = 0; i < 8; i++) w.v.last_words[i] = 0;           /* last_pcm1_line.clear(): the data words are zero */
 }
 
 __device__ inline int16_t p1_get_sample(uint16_t w)     /* pcm1line.cpp:188-222 */
@@ -255,7 +149,7 @@ __device__ inline void v2d1_post_line(V2D1 &w, const FrameArgs &a, WaveLds &lds,
         v.q_line_length = (uint16_t)a.width;
         if (a.check_line_copy) {
             if (v.field_state == FIELD_UNSAFE) {
-                set_good_parameters_p1(v.bin, ps, wl);
+                set_good_parameters(v.bin, ps, wl);
                 if (ps.en_first_line_dup) wl.forced_bad = true;
             } else {
                 int diff = 0, silent = 0;
@@ -265,49 +159,24 @@ __device__ inline void v2d1_post_line(V2D1 &w, const FrameArgs &a, WaveLds &lds,
                     const int16_t smp = p1_get_sample(wd);
                     if (!(smp >= 8) && !(smp < -8)) silent++;
                 }
-                if (!(silent >= 2) && diff <= (P1_BITS / BIT_DIFF_THRES_DIV)) { wl.forced_bad = true; if (!even_line) v.q_dup_odd++; else v.q_dup_even++; }
+                if (!(silent >= 2) && diff <= (P1_BITS / BIT_DIFF_THRES_DIV)) { wl.forced_bad = true; count_dup(v, even_line); }
             }
         }
         if (crc_valid_ignore_forced(wl)) {
             const uint32_t key = coords_key(wl.coords.start, wl.coords.stop);
-            SDV_WAVE_SYNC();
-            {   /* the window moves up by one when it is full: every lane carries one entry (no serial chain through LDS) */
-                const int ln = lane_id();
-                const bool full = v.n_last == COORD_HISTORY_DEPTH;
-                const uint32_t moved = (full && ln < COORD_HISTORY_DEPTH - 1) ? lds.lv_keys[ln + 1] : 0u;
-                SDV_WAVE_SYNC();
-                if (full && ln < COORD_HISTORY_DEPTH - 1) lds.lv_keys[ln] = moved;
-                if (ln == 0) lds.lv_keys[full ? COORD_HISTORY_DEPTH - 1 : v.n_last] = key;
-            }
-            if (v.n_last < COORD_HISTORY_DEPTH) v.n_last++;
-            SDV_WAVE_SYNC();
+            push_last_valid<COORD_HISTORY_DEPTH>(lds.lv_keys, v, key);
             fv_keys[v.nfv++] = key;
-            if (a.coordinate_damper && !ps.en_force_coords && (v.n_last > (COORD_HISTORY_DEPTH / 2))) {
-                Coords target; coords_clear(target);
-                uint32_t k;
-                if (median_keys(lds.lv_keys, v.n_last, &k)) target = key_to_coords(k, false);
-                if (!coords_valid(target)) target = v.frame_avg;
-                if (coords_valid(target)) {
-                    const int16_t ds = (int16_t)(wl.coords.start - target.start), de = (int16_t)(wl.coords.stop - target.stop);
-                    const uint8_t in_delta = (uint8_t)(get_ppb(wl) * 3);
-                    if (((int)ds <= -(int)in_delta) || ((int)ds >= (int)in_delta) || ((int)de <= -(int)in_delta) || ((int)de >= (int)in_delta)) wl.forced_bad = true;
-                }
-            }
+            if (damper_forces_bad(v, a, lds.lv_keys, wl)) wl.forced_bad = true;
         }
-        if (crc_valid(wl)) set_good_parameters_p1(v.bin, ps, wl);
-        else { if (!even_line) v.q_bad_odd++; else v.q_bad_even++; }
+        if (crc_valid(wl)) set_good_parameters(v.bin, ps, wl);
+        else count_bad(v, even_line);
         v.field_state = FIELD_INIT;
     } else {
         if (v.q_line_length == 0) v.q_line_length = (uint16_t)a.width;
         if (coords_valid(wl.coords)) fi_keys[v.nfi++] = coords_key(wl.coords.start, wl.coords.stop);
         if (count_has_data) {
-            Coords preset_coords; coords_clear(preset_coords);
-            if (!even_line) v.q_bad_odd++; else v.q_bad_even++;
-            if (!ps.en_force_coords) {
-                uint32_t k;
-                if (median_keys(lds.lv_keys, v.n_last, &k)) preset_coords = key_to_coords(k, a.doubled != 0);
-                if (!coords_valid(preset_coords)) preset_coords = v.frame_avg;
-            }
+            count_bad(v, even_line);
+            const Coords preset_coords = preset_behind_unreadable(v, a, lds.lv_keys);
             v.field_state = FIELD_INIT;
             bin_set_data_coordinates(v.bin, preset_coords);
             bin_set_bw_levels(v.bin, ps, 0, 0);
@@ -315,13 +184,7 @@ __device__ inline void v2d1_post_line(V2D1 &w, const FrameArgs &a, WaveLds &lds,
             bin_set_bw_levels(v.bin, ps, 0, 0);
         }
     }
-    if (!even_line) v.q_odd++; else v.q_even++;
-    if (count_has_pcm) {
-        if (!even_line) v.q_pcm_odd++; else v.q_pcm_even++;
-        v.pcm_lines_in_field++;
-        for (int i = 0; i < 6; i++) v.last_words[i] = get_word(wl, i);
-    }
-    v.line_in_field_cnt++;
+    count_line(v, even_line, count_has_pcm, [&v, &wl]() __attribute__((always_inline)) { for (int i = 0; i < 6; i++) v.last_words[i] = get_word(wl, i); });
 }
 
 /* ---- the tape plays: lines that read from what their predecessor left preset ----------------------------------------------------------- */
@@ -331,64 +194,15 @@ __device__ inline void v2d1_post_line(V2D1 &w, const FrameArgs &a, WaveLds &lds,
 #ifndef SDV_P1_CAPTURE_D
 #define SDV_P1_CAPTURE_D 8          /* batch1: lines in flight */
 #endif
-#ifdef SDV_EMU
-__device__ __forceinline__ uint8_t lean_load_u8(const uint8_t *p) { return *p; }
-#else
-__device__ __forceinline__ uint8_t lean_load_u8(const uint8_t *p) { return __builtin_nontemporal_load(p); }      /* read once */
-#endif
-#ifdef SDV_EMU
-__device__ inline uint32_t lane_read32(uint32_t x, uint32_t idx) { return (uint32_t)__shfl((int)x, (int)idx); }
-#else
-__device__ inline uint32_t lane_read32(uint32_t x, uint32_t idx) { return (uint32_t)__builtin_amdgcn_readlane((int)x, (int)uniu(idx)); }
-extern "C" __device__ uint32_t sdv_llvm_writelane1(uint32_t val, uint32_t lane, uint32_t old) __asm("llvm.amdgcn.writelane.i32");
-#endif
-__device__ __forceinline__ uint32_t park_lane(uint32_t old, uint32_t val, int lane)
-{
-#ifdef SDV_EMU
-    return lane_id() == lane ? val : old;
-#else
-    return sdv_llvm_writelane1(val, (uint32_t)lane, old);
-#endif
-}
-/* What depends on the tuning only: the pixels a lane samples (cells lane and lane + 64), the levels with their clipping test, the cells
- * the picture cuts off at either end (pickCutBitsUpPCM1, binarizer.cpp:6116-6596).  Kept while the tuning stays the same. */
-struct Lean1 {
-    uint32_t key_coords, key_levels;
-    uint16_t x0, x1;
-    uint8_t low, high, bits_l, bits_r;
-    bool usable;
-    uint32_t psm, hpsm; int16_t pso;
-};
-__device__ inline void lean1_reset(Lean1 &n) { n.key_levels = 0xFFFFFFFFu; n.key_coords = 0; n.usable = false; }
+/* The tuning of sdvmf::LeanBase and the pixels a lane samples: cells lane and lane + 64 */
+struct Lean1 : LeanBase { uint16_t x0, x1; };
 __device__ inline bool lean1_prepare(Lean1 &n, const BinCtx &c, const Bin &b)
 {
-    if (c.ps.en_force_coords) return false;
-    if (!(are_bw_levels_preset(b, c.ps) && is_ref_level_preset(b, c.ps) && coords_valid(b.in_coord))) return false;
-    if (!(b.in_ref < b.in_white && b.in_ref > b.in_black)) return false;
-    if (!(c.scan_end > c.scan_start && P1_BITS <= (c.scan_end - c.scan_start))) return false;
-    const uint32_t kc = coords_key(b.in_coord.start, b.in_coord.stop), kl = (uint32_t)b.in_black | ((uint32_t)b.in_white << 8) | ((uint32_t)b.in_ref << 16) | ((uint32_t)(b.in_coord.doubled ? 1 : 0) << 24);
-    if (kc != n.key_coords || kl != n.key_levels) {
-        n.key_coords = kc; n.key_levels = kl;
-        L1 t; p1_clear(t);
-        t.pixel_start = c.scan_start; t.pixel_stop = c.scan_end;
-        t.coords = b.in_coord;
-        set_ppb(t, t.coords);
-        n.psm = t.psm; n.hpsm = t.hpsm; n.pso = t.pso;
+    return lean_prepare<L1, P1_BITS>(n, c, b, [&n](const L1 &t) {
         const int lane = lane_id();
         n.x0 = (uint16_t)pixel_of(t, lane, 0);
         n.x1 = (uint16_t)pixel_of(t, lane + 64 < P1_BITS ? lane + 64 : P1_BITS - 1, 0);
-        n.low = get_low_level(b.in_ref, 0); n.high = get_high_level(b.in_ref, 0);
-        n.usable = !(n.low <= b.in_black) && !(n.high >= b.in_white);
-        int max_cut = c.ps.left_bit_pick; if (c.mode == SDV_MODE_DRAFT) max_cut /= 2;
-        int first = c.scan_start, left_bits = 0, right_bits = 0;
-        const int half_ppb = ((int)get_ppb(t) + 1) / 2;
-        for (int i = 0; i < max_cut; i++) { const int cur = pixel_of(t, i, 0); if ((cur - first) >= half_ppb) break; if (i == 0) first = cur; left_bits = i + 1; }
-        first = c.scan_end;
-        max_cut = c.ps.right_bit_pick; if (c.mode == SDV_MODE_DRAFT) max_cut /= 2;
-        for (int i = 0; i < max_cut; i++) { const int cur = pixel_of(t, P1_BITS - 1 - i, 0); if ((first - cur) >= half_ppb) break; if (i == 0) first = cur; right_bits = i + 1; }
-        n.bits_l = (uint8_t)left_bits; n.bits_r = (uint8_t)right_bits;
-    }
-    return n.usable && c.force_bit_picker;
+    });
 }
 /* one read of a line under the tuning in n: the cells as two masks (cell b = bit b), the CRC over them; false when the CRC does not match
  * or the line is a Header (*header says which: a Header is read, all 94 cells of it - the first rung of the ladder takes it, pick_cut_bits
@@ -477,8 +291,8 @@ __device__ inline int batch1(V2D1 &w, const FrameArgs &a, WaveLds &lds, const Le
                 const uint8_t p0 = q[d][0], p1 = q[d][1];
                 const uint64_t a_lo = __ballot(p0 > lo), b_lo = __ballot(p0 >= hi), a_hi = __ballot(second && p1 > lo), b_hi = __ballot(second && p1 >= hi);
                 { const int jn = j + D < n_lines ? j + D : n_lines - 1; const uint32_t o = (uint32_t)jn * rs2; q[d][0] = lean_load_u8(row0 + (o + x0)); q[d][1] = lean_load_u8(row0 + (o + x1)); }
-                ra0 = park_lane(ra0, (uint32_t)a_lo, j); ra1 = park_lane(ra1, (uint32_t)(a_lo >> 32), j); ra2 = park_lane(ra2, (uint32_t)a_hi, j);
-                rb0 = park_lane(rb0, (uint32_t)b_lo, j); rb1 = park_lane(rb1, (uint32_t)(b_lo >> 32), j); rb2 = park_lane(rb2, (uint32_t)b_hi, j);
+                ra0 = write_lane(ra0, (uint32_t)a_lo, j); ra1 = write_lane(ra1, (uint32_t)(a_lo >> 32), j); ra2 = write_lane(ra2, (uint32_t)a_hi, j);
+                rb0 = write_lane(rb0, (uint32_t)b_lo, j); rb1 = write_lane(rb1, (uint32_t)(b_lo >> 32), j); rb2 = write_lane(rb2, (uint32_t)b_hi, j);
             }
         }
         uint64_t s_lo, s_hi;
@@ -573,14 +387,12 @@ __device__ inline void frame_body1(const FrameArgs1 &a1, P1Lds &lds, int f)
     const uint8_t *frame = a.luma + (size_t)f * a.frame_stride;
     uint32_t *fv_keys = a.scratch + (size_t)f * 2u * (size_t)a.height;
     uint32_t *fi_keys = fv_keys + a.height;
-    size_t rec_base = (size_t)f * (size_t)(a.height + 3);
-    if (a.new_file_frame >= 0 && f > a.new_file_frame) rec_base += 1;
-    sdv_pcm1_bin_rec *rec = a1.recs1 + rec_base;
+    sdv_pcm1_bin_rec *rec = a1.recs1 + rec_base(a, f, 1);
     const bool doubled = a.doubled != 0;
 
-    v2d1_begin_frame(w, a1, lds.w, f);
+    begin_frame(v, w.prescan_ref, a, a1.prescan, lds.w.long_keys, f, [](int, int) {});
     const bool empty_frame = frame_is_empty(a, f);
-    Lean1 lean; lean1_reset(lean);
+    Lean1 lean; lean_reset(lean);
     const int n_field[2] = { (a.height + 1) / 2, a.height / 2 };
     uint16_t line_num = 0;
     if (f == a.new_file_frame) { v2d1_service_line(w, a, wl, SDV_SRV_NEW_FILE); emit_rec(wl, frame_no, 0, false, rec++); }
@@ -632,12 +444,7 @@ __device__ inline void frame_body1(const FrameArgs1 &a1, P1Lds &lds, int f)
     line_num = (uint16_t)(line_num + 2);
     v2d1_service_line(w, a, wl, SDV_SRV_END_FRAME);
     v.q_odd = v.q_even = P1_LINES_PF;                               /* :1638-1642 */
-    {   /* the median of the frame's valid coordinates is what v2d_end_frame pushes into long_valid_coords (:1668-1682) */
-        __syncthreads();        /* (keys stored to global memory by other lanes than the ones that read them now) */
-        uint32_t mk = 0; bool pushed = median_keys(fv_keys, v.nfv, &mk);
-        if (pushed) { const Coords mc = key_to_coords(mk, false); pushed = coords_valid(mc); }
-        if (lane_id() == 0) { uint2 m; m.x = pushed ? mk : 0u; m.y = pushed ? 1u : 0u; a1.frame_med[f] = m; }
-    }
+    store_frame_median(a1.frame_med, f, fv_keys, v.nfv);
     v2d_end_frame(v, a, lds.w, frame_no, fv_keys, fi_keys, &a.stats[f]);
     emit_rec(wl, frame_no, line_num, false, rec++);
     v2d1_store_state(w, lds.w, &a.states_out[f], a);
@@ -645,32 +452,10 @@ __device__ inline void frame_body1(const FrameArgs1 &a1, P1Lds &lds, int f)
 
 } // namespace sdvp1f
 
-/* two builds of the two kernels: MODE_INSANE (with the reference level sweep) and every other mode (process_line_p1) */
 #ifndef SDV_P1PRE_WAVES_PER_EU
 #define SDV_P1PRE_WAVES_PER_EU SDV_P1B_WAVES_PER_EU
 #endif
-#define SDV_P1F_KERNELS(SUFFIX, INSANE) \
-__global__ void __launch_bounds__(64, SDV_P1PRE_WAVES_PER_EU) sdv_k_pcm1_prescan##SUFFIX(sdvp1f::FrameArgs1 a) \
-{ \
-    __shared__ sdvp1b::P1Lds lds; \
-    const int i = (int)blockIdx.x, f = a.f.frame_list ? a.f.frame_list[i / sdvp1f::COORD_CHECK_LINES] : a.f.frame_lo + i / sdvp1f::COORD_CHECK_LINES; \
-    sdvp1f::prescan_body<INSANE>(a, lds, f, i % sdvp1f::COORD_CHECK_LINES); \
-} \
-__global__ void __launch_bounds__(64, SDV_P1B_WAVES_PER_EU) sdv_k_pcm1_frames_bin##SUFFIX(sdvp1f::FrameArgs1 a) \
-{ \
-    __shared__ sdvp1b::P1Lds lds; \
-    const int f = a.f.frame_list ? a.f.frame_list[blockIdx.x] : a.f.frame_lo + (int)blockIdx.x; \
-    sdvp1f::frame_body1<INSANE>(a, lds, f); \
-}
-SDV_P1F_KERNELS(, false)
-SDV_P1F_KERNELS(_insane, true)
 #ifndef SDV_P1F_LEAN_WAVES_PER_EU
 #define SDV_P1F_LEAN_WAVES_PER_EU 4
 #endif
-/* the lean build of the frame kernel (every mode: what it holds - lines that read from what they inherit - is the same in all of them) */
-__global__ void __launch_bounds__(64, SDV_P1F_LEAN_WAVES_PER_EU) sdv_k_pcm1_frames_lean(sdvp1f::FrameArgs1 a)
-{
-    __shared__ sdvp1b::P1Lds lds;
-    const int f = a.f.frame_list ? a.f.frame_list[blockIdx.x] : a.f.frame_lo + (int)blockIdx.x;
-    sdvp1f::frame_body1<false, true>(a, lds, f);
-}
+SDV_MLF_KERNELS(pcm1, sdvp1f::FrameArgs1, sdvp1b::P1Lds, sdvp1f::prescan_body, sdvp1f::frame_body1, SDV_P1PRE_WAVES_PER_EU, SDV_P1B_WAVES_PER_EU, SDV_P1F_LEAN_WAVES_PER_EU)

@@ -18,6 +18,7 @@
 #define SDV_PCM1_STITCH_DEVICE_H
 #include "../../include/sdvpcm.h"
 #include "stc007_stitch_device.h"
+#include "stitch_stream_device.h"
 
 namespace sdvp1 {
 using sdvs::lanemask_lt;
@@ -25,51 +26,19 @@ using sdvs::uni;
 
 enum { LINES_PF = 245, SUBLINES_PF = 735, MIN_GOOD = 245 * 4 / 5, BUF_TRIM = 3 * 640, BIT_RANGE = 1 << 12, BIT_SIGN = 1 << 11, WORD_MASK = (1 << 13) - 1 };
 enum { ORDER_TFF = 1, ORDER_BFF = 2 };
-/* per-frame marks found by the flags pass */
-enum { FF_NEW_FILE = 1, FF_END_FILE = 2, FF_FOREIGN = 4 };
+using sdvss::FF_NEW_FILE; using sdvss::FF_END_FILE; using sdvss::FF_FOREIGN;       /* per-frame marks (stitch_stream_device.h) */
 /* reasons a frame cannot be stitched statelessly (the reference would read sub-lines left over from earlier frames, or hold lines back) */
 enum { FE_FOREIGN = 1, FE_TOO_LONG = 2, FE_MARKS = 16 };
 
-struct RecSrc1 {
-    const sdv_pcm1_line_rec *carry; uint32_t n_carry; const sdv_pcm1_line_rec *recs;
-    __device__ inline const sdv_pcm1_line_rec &at(uint32_t i) const { return i < n_carry ? carry[i] : recs[i - n_carry]; }
-};
+typedef sdvss::RecSrc<sdv_pcm1_line_rec> RecSrc1;
 struct Cfg1 { uint8_t field_order, auto_offset, ignore_crc; int8_t odd_offset, even_offset; };
 
-/* ---- segments: positions of the END_FRAME records, and the file tags of every frame ------------------------------- */
-/* Pass 0 counts the END_FRAMEs of every 4096-record chunk and leaves each record's service type in a byte array (5 MB for a
- * 10 000-frame batch instead of the 157 MB of records); after the host's prefix sum, pass 1 works from those bytes: it writes
- * the segment ends and tags segment k (= the number of END_FRAMEs ahead of a record) with the NEW_FILE / END_FILE records in it.
- * The frame kernel, which sees the frame numbers, confirms the tags. */
-struct SegArgs1 { RecSrc1 src; uint32_t n_recs; uint8_t *svc; uint32_t *block_count; const uint32_t *block_ofs; uint32_t *seg_end; uint32_t n_seg; uint32_t *marks; uint32_t *stat; int write; };
+/* ---- segments (stitch_stream_device.h), 1024 records per workgroup ------------------------------------------------- */
+struct SegArgs1 : sdvss::SegArgs<sdv_pcm1_line_rec> {};       /* (a type of its own: the kernel's symbol stays as it was) */
 #ifndef SDV_P1_SEG_CHUNK
 #define SDV_P1_SEG_CHUNK 1024
 #endif
 enum { SEG_CHUNK1 = SDV_P1_SEG_CHUNK };
-__device__ inline void seg_body(const SegArgs1 &a, uint32_t blk, int lane)
-{
-    const uint32_t lo = blk * SEG_CHUNK1;
-    uint32_t hi = lo + SEG_CHUNK1; if (hi > a.n_recs) hi = a.n_recs;
-    uint32_t cnt = 0;
-    const uint32_t base = a.write ? a.block_ofs[blk] : 0u;
-#pragma unroll 4
-    for (uint32_t c = lo; c < hi; c += 64) {
-        const uint32_t i = c + (uint32_t)lane;
-        uint8_t srv = SDV_SRV_NO;
-        if (i < hi) { if (a.write) srv = a.svc[i]; else { srv = a.src.at(i).service_type; a.svc[i] = srv; } }
-        const uint64_t m = __ballot(srv == SDV_SRV_END_FRAME);
-        if (a.write) {
-            const uint32_t seg = base + cnt + (uint32_t)__popcll(m & lanemask_lt(lane));
-            if (srv == SDV_SRV_END_FRAME) a.seg_end[seg] = i;
-            else if ((srv == SDV_SRV_NEW_FILE || srv == SDV_SRV_END_FILE) && seg < a.n_seg) {
-                atomicOr(&a.marks[seg], srv == SDV_SRV_NEW_FILE ? (uint32_t)FF_NEW_FILE : (uint32_t)FF_END_FILE);
-                atomicAdd(&a.stat[2], 1u);
-            }
-        }
-        cnt += (uint32_t)__popcll(m);
-    }
-    if (!a.write && lane == 0) a.block_count[blk] = cnt;
-}
 
 /* ---- output offsets: exclusive scan of the per-frame output counts, one workgroup --------------------------------- */
 struct ScanArgs1 { uint32_t *marks; uint32_t n_seg; uint64_t *pair_ofs; uint32_t *frasm_ofs; const uint32_t *stat; RecSrc1 src; const uint32_t *seg_end; };   /* n_seg + 1 entries each */
@@ -697,17 +666,9 @@ __device__ inline void conv_body(const ConvArgs1 &a, size_t i)
 } // namespace sdvp1
 
 __global__ void __launch_bounds__(64) sdv_k_pcm1_bin_to_line(sdvp1::ConvArgs1 a) { sdvp1::conv_body(a, (size_t)blockIdx.x * 64u + threadIdx.x); }
-__global__ void __launch_bounds__(64) sdv_k_pcm1_segments(sdvp1::SegArgs1 a) { sdvp1::seg_body(a, blockIdx.x, (int)threadIdx.x); }
+__global__ void __launch_bounds__(64) sdv_k_pcm1_segments(sdvp1::SegArgs1 a) { sdvss::seg_body<sdv_pcm1_line_rec, sdvp1::SEG_CHUNK1>(a, blockIdx.x, (int)threadIdx.x); }
 __global__ void __launch_bounds__(64) sdv_k_pcm1_scan(sdvp1::ScanArgs1 a) { sdvp1::scan_body(a, (int)threadIdx.x); }
-/* What the host wants to know at the end of a stitch call (PCM-1 and PCM-16x0 engines) lies in four places; this puts it behind the four status
- * words so that one small copy brings all of it: stat[4..5] = pairs of the call, stat[6] = frame descriptors, stat[7] = index of the last END_FRAME. */
-struct sdv_stitch_tail_args { uint32_t *stat; const uint64_t *pair_total; const uint32_t *frasm_total; const uint32_t *last_end; };
-__global__ void __launch_bounds__(64) sdv_k_stitch_tail(sdv_stitch_tail_args a)
-{
-    if (threadIdx.x != 0) return;
-    const uint64_t p = *a.pair_total;
-    a.stat[4] = (uint32_t)p; a.stat[5] = (uint32_t)(p >> 32); a.stat[6] = *a.frasm_total; a.stat[7] = *a.last_end;
-}
+SDV_STITCH_TAIL_KERNEL      /* sdv_k_stitch_tail (stitch_stream_device.h), used by the PCM-1 and PCM-16x0 engines */
 __global__ void __launch_bounds__(64) sdv_k_pcm1_hist(sdvp1::HistArgs1 a) { sdvp1::hist_body(a, (int)threadIdx.x); }
 struct sdv_p1_hist_clear_args { void *hist; };
 __global__ void __launch_bounds__(64) sdv_k_pcm1_hist_clear(sdv_p1_hist_clear_args a) { sdvp1::hist_clear_body(a.hist, (int)threadIdx.x); }

@@ -90,14 +90,14 @@ COVERED_BY = {
         "emulator only: the refusal (stitch_engine.inc:482) is decided behind the read-back of a pipelined round whose turn kernel has already written the "
         "caller's buffers (direct_pairs = out_pairs, stitch_engine.inc:405-407)",
     "test_pcm1::test_emu_refuses_what_the_reference_never_finishes":
-        "emulator only: FE_FOREIGN is read back (pcm1_engine.inc:140, :150) after the frame kernel has written pairs and descriptors to the caller (:120-124)",
+        "emulator only: FE_FOREIGN is read back (pcm1_engine.inc:111, :122; stitch_stream.inc, read_tail) after the frame kernel has written pairs and descriptors to the caller (:95-99)",
     "test_pcm16::test_emu_refuses_what_the_reference_never_finishes":
-        "emulator only: FE_FOREIGN is read back (pcm16_engine.inc:319, :339) after the emit kernels have written pairs and descriptors to the caller (:305)",
+        "emulator only: FE_FOREIGN is read back (pcm16_engine.inc:279, :300; stitch_stream.inc, read_tail) after the emit kernels have written pairs and descriptors to the caller (:268)",
     # argument checks of the per-line entries: host code ahead of any device work, the same in both builds; not among the call-by-call tests twinned so far
     "test_stc_lines::test_emu_lines_refuse_bad_arguments": "emulator only: the checks of sdv_binarize_lines are the host's, ahead of its first launch (engine.inc:510-517)",
-    "test_pcm1_front::test_emu_argument_checks": "emulator only: the checks of sdv_pcm1_binarize_lines are the host's, ahead of its launch (pcm1_engine.inc:221-227)",
+    "test_pcm1_front::test_emu_argument_checks": "emulator only: the checks of sdv_pcm1_binarize_lines are the host's, ahead of its launch (check_lines_call, markerless_frames_engine.inc:27-40)",
     "test_pcm16_front::test_emu_lines_argument_checks":
-        "emulator only: the checks of sdv_pcm16x0_binarize_lines are the host's, ahead of its launch (pcm16_frames_engine.inc:41-47); the rows nothing is preset for "
+        "emulator only: the checks of sdv_pcm16x0_binarize_lines are the host's, ahead of its launch (check_lines_call, markerless_frames_engine.inc:27-40); the rows nothing is preset for "
         "that follow them are an input like those of test_gpu_lines_match_oracle",
 }
 NOT_YET_TWINNED = [
