@@ -11,14 +11,16 @@
  *       8-bit luma frames of a PCM-1600/1610/1630 tape -> sdv_pcm16x0_binarize_frames (VideoToDigital with TYPE_PCM16X0) ->
  *       sdv_pcm16x0_stitch_frames (the PCM16X0DataStitcher worker's body); the sub-line records never leave the device
  *
- *   decode_tape wav <luma.raw> <width> <height> <n_frames> <out.wav> [<mask mode 0..6>] [auto|force] [44100]
+ *   decode_tape wav <luma.raw> <width> <height> <n_frames> <out.wav> [<mask mode 0..6>] [auto|force] [44100] [deskew-r|deskew-l]
  *       the whole chain of the application for an STC-007 file: sdv_binarize_frames -> sdv_stitch_frames -> sdv_audio_process (the
  *       AudioProcessor worker's loop, linear interpolation of dropouts by default) -> sdv_wav_pack + sdv_wav_header: the file SamplesToWAV
  *       writes, byte for byte; nothing but the luma goes to the device and nothing but the 16-bit PCM comes back.  With `auto` or `force`
  *       the 50/15 us de-emphasis network (sdv_audio_deemphasis) runs on the file's pairs in front of sdv_wav_pack - `force` is the one for
  *       an STC-007 tape recorded with emphasis, whose pairs never carry the flag `auto` goes by; the reference leaves this to an audio editor.
  *       With `44100` the file's pairs - an NTSC tape runs at 44 056 Hz - are resampled to 44 100 Hz (sdv_audio_resample, flush = 1) behind the
- *       de-emphasis, and the header says 44 100 Hz
+ *       de-emphasis, and the header says 44 100 Hz.  With `deskew-r` (or `deskew-l`) the right (left) channel is delayed by half a sample in the
+ *       same call (SDV_RESAMPLE_DELAY_RIGHT / _LEFT): the converter of a PCM-F1 samples the two channels half a period apart.  `deskew-r` is the
+ *       usual case - left converted first - but not a verified one: listen to a mono fold-down
  *   decode_tape ingest <video.raw> <pixfmt> <src_w> <src_h> <src_row_stride> <n_frames> <l,r,t,b> <bw|r|g|b> <off|on|auto> <luma.out>
  *       captured frames as the video decoder delivers them (pixfmt: gray8 uyvy422 yuyv422 v210 gray10le rgb24 bgr24 rgb0 bgr0; rows
  *       src_row_stride bytes apart, frames src_h rows apart) -> sdv_ingest_frames: crop, channel, 8-bit luma, 2x doubling -> the plane the
@@ -144,11 +146,13 @@ int main(int argc, char **argv)
     sdv_sample_pair *d_pairs = NULL;
     size_t n_pairs = 0, n_frames = 0;
     int rc = 0;
-    /* wav: the optional last words, `auto|force` and behind it `44100` */
+    /* wav: the optional last words, `auto|force`, behind it `44100` and behind that `deskew-r|deskew-l` */
     const bool wav = mode == "wav";
-    const int resample = wav && std::string(argv[argc - 1]) == "44100" ? 1 : 0;
-    const std::string last_arg = wav ? argv[argc - 1 - resample] : "";
-    const int deemph = last_arg == "auto" ? SDV_DEEMPH_AUTO : last_arg == "force" ? SDV_DEEMPH_FORCE : SDV_DEEMPH_OFF, wav_tail = (deemph != SDV_DEEMPH_OFF ? 1 : 0) + resample;
+    const std::string skew_arg = wav ? argv[argc - 1] : "";
+    const int deskew = skew_arg == "deskew-r" ? SDV_RESAMPLE_DELAY_RIGHT : skew_arg == "deskew-l" ? SDV_RESAMPLE_DELAY_LEFT : 0, skew_words = deskew ? 1 : 0;
+    const int resample = wav && argc - skew_words > 2 && std::string(argv[argc - 1 - skew_words]) == "44100" ? 1 : 0;
+    const std::string last_arg = wav && argc - skew_words - resample > 2 ? argv[argc - 1 - skew_words - resample] : "";
+    const int deemph = last_arg == "auto" ? SDV_DEEMPH_AUTO : last_arg == "force" ? SDV_DEEMPH_FORCE : SDV_DEEMPH_OFF, wav_tail = (deemph != SDV_DEEMPH_OFF ? 1 : 0) + resample + skew_words;
     if (mode == "stc007" && argc == 8) {
         const int width = atoi(argv[3]), height = atoi(argv[4]), n = atoi(argv[5]);
         if (!read_file(argv[2], in) || in.size() != (size_t)width * height * n) { fprintf(stderr, "cannot read %s\n", argv[2]); return 1; }
@@ -188,10 +192,11 @@ int main(int argc, char **argv)
         HIP_OK(hipMalloc((void **)&d_frames, frames_cap * sizeof(sdv_frame_asm)));
         HIP_OK(hipMalloc((void **)&d_audio, (pairs_cap + 1024) * sizeof(sdv_sample_pair)));
         HIP_OK(hipMalloc((void **)&d_purges, purges_cap * sizeof(sdv_audio_purge)));
-        /* with `44100`: room for every pair of the audio stage resampled (the bound grows with the pairs of the call) */
-        if (resample) SDV_OKAY(sdv_set_resample(eng, SDV_RESAMPLE_TO_44100));
+        /* with `44100` and / or `deskew-*`: room for every pair of the audio stage through sdv_audio_resample (the bound grows with the pairs of the call) */
+        const int rs_mode = (resample ? SDV_RESAMPLE_TO_44100 : SDV_RESAMPLE_OFF) | deskew;
+        if (rs_mode) SDV_OKAY(sdv_set_resample(eng, rs_mode));
         const size_t res_cap = sdv_audio_resample_room(eng, pairs_cap + 1024);
-        if (resample) HIP_OK(hipMalloc((void **)&d_resampled, res_cap * sizeof(sdv_sample_pair)));
+        if (rs_mode) HIP_OK(hipMalloc((void **)&d_resampled, res_cap * sizeof(sdv_sample_pair)));
         HIP_OK(hipMalloc((void **)&d_pcm, res_cap * 2 * sizeof(int16_t)));
         HIP_OK(hipMemcpy(d_luma, in.data(), in.size(), hipMemcpyHostToDevice));
         SDV_OKAY(sdv_set_mode(eng, SDV_MODE_NORMAL));
@@ -216,7 +221,7 @@ int main(int argc, char **argv)
                 SDV_OKAY(sdv_audio_deemphasis(eng, d_audio + a, b - a, d_audio + a, NULL));
             }
             const sdv_sample_pair *d_file = d_audio + a; size_t n_file = b - a;
-            if (resample) {                         /* the file's range, closed behind its last pair */
+            if (rs_mode) {                          /* the file's range, closed behind its last pair */
                 size_t n_res = 0;
                 SDV_OKAY(sdv_audio_resample(eng, d_file, n_file, 1, d_resampled, res_cap, &n_res, NULL));
                 d_file = d_resampled; n_file = n_res;

@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define SDV_ABI_VERSION 12  /* 2: output capacities on sdv_binarize_frames / sdv_pcm1_binarize_lines; 3: sdv_audio_process, sdv_wav_pack, sdv_wav_header, sdv_decode_frames (additions only);
+#define SDV_ABI_VERSION 13  /* 2: output capacities on sdv_binarize_frames / sdv_pcm1_binarize_lines; 3: sdv_audio_process, sdv_wav_pack, sdv_wav_header, sdv_decode_frames (additions only);
                              * 4: sdv_pcm16x0_binarize_lines, sdv_audio_stalled, sdv_set_frame_flags, sdv_double_width, sdv_vis_render_lines (additions); the calls that used to refuse PCM-16x0 frames of the wrong size and the
                              * AudioProcessor's dead ends now follow the reference; the PCM-16x0 stitch state blob grew by conv_queue's remainder;
                              * 5: sdv_run_info grew by frames_met (at its end), sdv_binarize_lines (addition);
@@ -32,7 +32,9 @@ extern "C" {
                              * 11: sdv_preemphasis_coeffs, sdv_reset_preemphasis, sdv_pcm_preemphasis, sdv_pcm_preemphasis_clipped, sdv_pcm_resample_taps, sdv_reset_pcm_resample,
                              * sdv_pcm_resample_pending, sdv_pcm_resample_room, sdv_pcm_resample (additions only);
                              * 12: out_fmt in sdv_encode_desc and sdv_encode_markerless_desc, in bytes that were padding (0, SDV_PIX_GRAY8, is what they meant); *row_bytes of
-                             * the two geometry calls follows it */
+                             * the two geometry calls follows it;
+                             * 13: SDV_RESAMPLE_DELAY_RIGHT / _LEFT as bits of sdv_set_resample's mode, SDV_RESAMPLE_PHASE_HALF for sdv_resample_taps (values that were refused
+                             * or gave zeros); sdv_audio_resample_pending and _room count the skew stage in */
 
 /* ---- status codes ---------------------------------------------------------------------------
  * 0..4 mirror Binarizer::LB_RET_* (binarizer.h:268-275); 16.. mirror STC007Deinterleaver::DI_RET_*
@@ -1035,14 +1037,42 @@ int sdv_audio_deemphasis(sdv_engine *e, const sdv_sample_pair *pairs, size_t n, 
 #define SDV_RESAMPLE_L 1001
 #define SDV_RESAMPLE_M 1000
 #define SDV_RESAMPLE_HALF 64        /* taps on each side of an output: 128 per phase */
-enum { SDV_RESAMPLE_OFF = 0, SDV_RESAMPLE_TO_44100 = 1 };
-/* h[phase][0 .. 127] (phase 0 .. 1000; anything else: zeros).  Host memory, no engine. */
+/* The skew stage: one channel half a sampling period later (no reference equivalent).  The processors of the PCM-F1 family (PCM-F1, 501ES, 601, 701)
+ * convert both channels with one time-shared converter, so the two channels of a pair are sampled half a period (11.3 us) apart; the machine's own
+ * playback undoes that, a digital transfer does not, and the stereo image of the file is skewed by half a sample (a mono fold-down rolls off by about
+ * 3 dB at 11 kHz).  This is general knowledge of the hardware, not something the reference states, and which channel a machine converts first is not
+ * verified here: SDV_RESAMPLE_DELAY_RIGHT ("left is converted first, so delay the right channel") is the usual case, SDV_RESAMPLE_DELAY_LEFT the
+ * other one, and the default is neither.
+ * With a delay bit or-ed to SDV_RESAMPLE_OFF or SDV_RESAMPLE_TO_44100 (one bit, not both) sdv_audio_resample is two stages: stage A is exactly what the
+ * call does without the bit - the byte copy, or the resampler above - and stage B, the skew stage, runs on A's output.
+ * Taps.  One row, all in double, for k = 0 .. 127: d = k - 63.5, g[k] = sinc(d) w(d) with the window above, h[k] = g[k] / sum_k g[k] - the prototype
+ * above at phase 1/2.  h[k] = h[127 - k], h[63] = h[64] = 0.63640, sum |h| = 3.1436 (outputs clamp); the magnitude is within 2e-5 dB of 1 up to
+ * 20 kHz and -0.02 dB at 21 kHz.
+ * Segments.  B's input is walked in order.  A service pair (service_type != 0) is copied unchanged and ends an open segment; a maximal run of other
+ * pairs with the same sample_rate is a segment (a change of rate ends one segment and starts the next).  Behind stage A with SDV_RESAMPLE_TO_44100
+ * the former 44 056 Hz pairs carry 44100: they and a neighbouring run of true 44 100 Hz pairs are one segment.  A segment continues across the calls
+ * of a stream; it ends at a service pair, at a change of rate, or at the end of a call made with flush != 0.
+ * A finished segment z[0 .. n-1] yields n pairs.  Output m is z[m] in every field - the other channel's word and all flags bit for bit - except the
+ * audio_word of the delayed channel c (right for SDV_RESAMPLE_DELAY_RIGHT, left for SDV_RESAMPLE_DELAY_LEFT):
+ *   y = sum_k h[k] z_c[clamp(m - 64 + k, 0, n - 1)]  (the signal half a sample before z[m]; edge hold: no click at the ends, DC passes exactly; the
+ *   sum runs in double in the order of k), audio_word = y rounded to the nearest integer (halves to even), clamped to -32768 .. 32767.
+ * With SDV_RESAMPLE_TO_44100 the delayed channel is therefore rounded twice, once by A and once by B.
+ * Latency.  Without flush B emits only those outputs of its open segment with m + 63 below the number of pairs the segment has seen; the rest - at
+ * most 63 pairs - wait in the engine (B's last 127 input pairs, on the device).  flush flushes A, then B.  Any split of a stream into calls gives
+ * the concatenated output of one call, under the condition above.  sdv_set_resample with other delay bits than those that are set is refused
+ * (SDV_ERR_BAD_ARG: flush or reset first) while B holds waiting pairs; without a delay bit nothing ever waits in B. */
+enum { SDV_RESAMPLE_OFF = 0, SDV_RESAMPLE_TO_44100 = 1,
+       SDV_RESAMPLE_DELAY_RIGHT = 4, SDV_RESAMPLE_DELAY_LEFT = 8 };     /* or-ed to either of the two; not both */
+#define SDV_RESAMPLE_PHASE_HALF (-1)    /* sdv_resample_taps: the half-sample row of the skew stage */
+/* h[phase][0 .. 127] (phase 0 .. 1000), the skew stage's row (SDV_RESAMPLE_PHASE_HALF); anything else: zeros.  Host memory, no engine. */
 void sdv_resample_taps(int phase, double taps[128]);
-/* The mode (SDV_RESAMPLE_OFF when the engine is made); anything else: SDV_ERR_BAD_ARG.  The state stays as it is. */
+/* The mode (SDV_RESAMPLE_OFF when the engine is made): 0, 1, 4, 5, 8 or 9; anything else: SDV_ERR_BAD_ARG, as is a change of the delay bits while
+ * the skew stage holds waiting pairs.  A refused call leaves the mode as it was; the state stays as it is. */
 int sdv_set_resample(sdv_engine *e, int mode);
-/* No open segment, nothing pending. */
+/* No open segment, nothing pending, in either stage. */
 int sdv_reset_resample(sdv_engine *e);
-/* Pairs of the open segment that still owe outputs (at most SDV_RESAMPLE_HALF; 0 behind a flush). */
+/* Pairs that still owe outputs: those of the resampler's open segment (at most SDV_RESAMPLE_HALF) plus, with a delay bit, those of the skew
+ * stage's (at most SDV_RESAMPLE_HALF - 1); 0 behind a flush. */
 size_t sdv_audio_resample_pending(const sdv_engine *e);
 /* An upper bound of *n_out for the next call with n_pairs pairs, whatever they hold and with or without flush. */
 size_t sdv_audio_resample_room(const sdv_engine *e, size_t n_pairs);

@@ -221,7 +221,7 @@ ASM_LINE_DTYPE = np.dtype(AsmLineRec)
 
 
 # ---- constants: the header's enums and #defines without the SDV_ prefix ----------------------------------------------------------------
-ABI_VERSION = 12
+ABI_VERSION = 13
 OK, ERR_NULL_VIDEO, ERR_NULL_PCM, ERR_SHORT_LINE, ERR_NO_COORD, ERR_NULL_LINES, ERR_NULL_BLOCK, ERR_NO_DATA = 0, 1, 2, 3, 4, 16, 17, 18
 ERR_BAD_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED = -1, -2, -3, -4
 PCM_PCM1, PCM_PCM16X0, PCM_STC007 = 0, 1, 2
@@ -246,6 +246,7 @@ DROP_IGNORE, DROP_MUTE_BLOCK, DROP_MUTE_WORD, DROP_HOLD_BLOCK, DROP_HOLD_WORD, D
 AP_BUF_SIZE, AP_MIN_VALID_BEFORE, AP_MAX_RAMP_DOWN, AP_MAX_RAMP_UP, AP_PURGE_NEW_FILE, AP_PURGE_END_FILE, AP_PURGE_STOP = 512, 3, 192, 32, 1, 2, 3
 DEEMPH_OFF, DEEMPH_AUTO, DEEMPH_FORCE, DEEMPH_TILE, DEEMPH_WARMUP = 0, 1, 2, 1024, 128
 RESAMPLE_L, RESAMPLE_M, RESAMPLE_HALF, RESAMPLE_OFF, RESAMPLE_TO_44100 = 1001, 1000, 64, 0, 1
+RESAMPLE_DELAY_RIGHT, RESAMPLE_DELAY_LEFT, RESAMPLE_PHASE_HALF = 4, 8, -1
 PREEMPH_TILE, PREEMPH_WARMUP, PCM_RESAMPLE_L, PCM_RESAMPLE_M = 1024, 32, 1000, 1001
 AL_FORCED_BAD, AL_MARKERS, AL_CRC_VALID = 1, 2, 4
 VIS_STC007_LINES, VIS_PCM1_LINES, VIS_PCM16X0_LINES, VIS_STC007_BLOCKS_NTSC, VIS_STC007_BLOCKS_PAL, VIS_STC007_ASM_NTSC, VIS_STC007_ASM_PAL = 0, 1, 2, 3, 4, 5, 6

@@ -30,6 +30,7 @@ KERNEL_SOURCES = {
     "sdv_k_ap_": ("audio_device.h", "audio_engine.inc"),
     "sdv_k_deemph": ("audio_device.h", "audio_deemph_device.h", "audio_engine.inc"),
     "sdv_k_resample": ("audio_device.h", "audio_resample_device.h", "audio_engine.inc"),
+    "sdv_k_skew": ("audio_device.h", "audio_resample_device.h", "audio_skew_device.h", "audio_engine.inc"),
     "sdv_k_ingest": ("ingest_device.h", "ingest_engine.inc"),
     "sdv_k_encode": ("encode_device.h", "encode_engine.inc"),
     "sdv_k_encode_raster_packed": ("encode_device.h", "encode_packed_device.h", "encode_engine.inc"),

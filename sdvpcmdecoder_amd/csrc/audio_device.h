@@ -691,3 +691,4 @@ __global__ void __launch_bounds__(64) sdv_k_wav_pack(sdva::WavArgs a) { sdva::wa
 
 #include "audio_deemph_device.h"      /* sdv_audio_deemphasis: the de-emphasis network behind the AudioProcessor */
 #include "audio_resample_device.h"    /* sdv_audio_resample: 44 056 Hz segments of the stream to 44 100 Hz */
+#include "audio_skew_device.h"        /* sdv_audio_resample with a delay bit: one channel half a sample later */

@@ -7,7 +7,8 @@
  * stretch, bitmaps only), a read-back of the per-stretch results, the sample work of the listed windows, a second read-back (mask
  * counts, the plan check), and - unless the caller's buffer was the work array - emit.  The stream state - what waits in the window,
  * the masking mode, the running sample index - is replaced only when the call succeeds.  sdv_audio_deemphasis (two launches,
- * nothing read back), sdv_audio_resample (three launches, the count read back) and sdv_decode_frames (the workers of a format back to back)
+ * nothing read back), sdv_audio_resample (three launches, with a delay bit a fourth, the count read back once) and sdv_decode_frames (the workers of
+ * a format back to back)
  * live here too, this being the last include of both builds.
  */
 #include <algorithm>
@@ -35,6 +36,12 @@ struct sdv_audio {
     rt::DevBuf<sdv_sample_pair> d_rs_hist, d_rs_hist_spare;
     rt::DevBuf<double> d_rs_taps;
     rt::DevBuf<sdva::RsSum> d_rs_sums; rt::DevBuf<sdva::RsStart> d_rs_starts; rt::DevBuf<sdva::RsResult> d_rs_result;
+    /* ... its skew stage (a delay bit in rs_mode): the pairs its open segment has seen (SK_MANY: more than its history holds), its last SK_HIST
+     * pairs (on the device), the half-sample row, the resampler's output where the stage follows it, the call's result */
+    uint32_t sk_seen; bool sk_taps_ready;
+    rt::DevBuf<sdv_sample_pair> d_sk_hist, d_sk_hist_spare, d_sk_mid;
+    rt::DevBuf<double> d_sk_taps;
+    rt::DevBuf<sdva::SkResult> d_sk_result;
 };
 
 static sdv_audio *audio_get(sdv_engine *e)
@@ -432,11 +439,12 @@ static double rs_bessel_i0(double x)
 }
 void sdv_resample_taps(int phase, double taps[128])
 {
-    if (phase < 0 || phase >= SDV_RESAMPLE_L) { for (int k = 0; k < 128; k++) taps[k] = 0.0; return; }
+    if (phase != SDV_RESAMPLE_PHASE_HALF && (phase < 0 || phase >= SDV_RESAMPLE_L)) { for (int k = 0; k < 128; k++) taps[k] = 0.0; return; }
+    const double frac = phase == SDV_RESAMPLE_PHASE_HALF ? 0.5 : (double)phase / (double)SDV_RESAMPLE_L;
     const double beta = 12.0, pi = 3.14159265358979323846, i0_beta = rs_bessel_i0(beta);
     long double sum = 0.0L;             /* (the normalisation must not cost the rows their gain of 1 at DC) */
     for (int k = 0; k < 128; k++) {
-        const double d = (double)(k - (SDV_RESAMPLE_HALF - 1)) - (double)phase / (double)SDV_RESAMPLE_L;
+        const double d = (double)(k - (SDV_RESAMPLE_HALF - 1)) - frac;
         double r = 1.0 - (d / SDV_RESAMPLE_HALF) * (d / SDV_RESAMPLE_HALF);
         if (r < 0.0) r = 0.0;
         const double w = rs_bessel_i0(beta * sqrt(r)) / i0_beta, x = pi * d;
@@ -447,11 +455,20 @@ void sdv_resample_taps(int phase, double taps[128])
     for (int k = 0; k < 128; k++) taps[k] /= total;
 }
 
+enum { RS_DELAY_BITS = SDV_RESAMPLE_DELAY_RIGHT | SDV_RESAMPLE_DELAY_LEFT };
+static size_t sk_waiting(const sdv_audio *t) { return (size_t)std::min<uint32_t>(t->sk_seen, (uint32_t)sdva::SK_WAIT); }
+
 int sdv_set_resample(sdv_engine *e, int mode)
 {
     if (!e) return SDV_ERR_BAD_ARG;
-    if (mode != SDV_RESAMPLE_OFF && mode != SDV_RESAMPLE_TO_44100) { set_error(e, "no such resampling mode"); return SDV_ERR_BAD_ARG; }
-    audio_get(e)->rs_mode = mode;
+    const int delay = mode & RS_DELAY_BITS;
+    if (mode < 0 || (mode & ~(SDV_RESAMPLE_TO_44100 | RS_DELAY_BITS)) || delay == RS_DELAY_BITS) { set_error(e, "no such resampling mode"); return SDV_ERR_BAD_ARG; }
+    sdv_audio *t = audio_get(e);
+    if (delay != (t->rs_mode & RS_DELAY_BITS) && t->sk_seen > 0) {
+        set_error(e, "the skew stage holds waiting pairs of the delay that is set: flush (sdv_audio_resample) or reset (sdv_reset_resample) first");
+        return SDV_ERR_BAD_ARG;
+    }
+    t->rs_mode = mode;
     return SDV_OK;
 }
 
@@ -459,14 +476,14 @@ int sdv_reset_resample(sdv_engine *e)
 {
     if (!e) return SDV_ERR_BAD_ARG;
     sdv_audio *t = audio_get(e);
-    t->rs_seen = 0; t->rs_emitted = 0;
+    t->rs_seen = 0; t->rs_emitted = 0; t->sk_seen = 0;
     return SDV_OK;
 }
 
 size_t sdv_audio_resample_pending(const sdv_engine *e)
 {
     if (!e || !e->audio) return 0;
-    return (size_t)std::min<uint64_t>(e->audio->rs_seen, (uint64_t)SDV_RESAMPLE_HALF);
+    return (size_t)std::min<uint64_t>(e->audio->rs_seen, (uint64_t)SDV_RESAMPLE_HALF) + sk_waiting(e->audio);
 }
 
 /* outputs the first j pairs of a segment own (sdva::rs_owned) */
@@ -475,10 +492,98 @@ static uint64_t rs_owned_host(uint64_t j) { return j == 0 ? 0 : j + (j - 1) / SD
 size_t sdv_audio_resample_room(const sdv_engine *e, size_t n_pairs)
 {
     if (!e || !e->audio || e->audio->rs_mode == SDV_RESAMPLE_OFF) return n_pairs;
+    /* (the skew stage puts out one pair per pair it is given, and what waited in it) */
+    if (!(e->audio->rs_mode & SDV_RESAMPLE_TO_44100)) return n_pairs + sk_waiting(e->audio);
     /* what the open segment owes when it ends, and per new pair one output and one more per thousand (a segment of n new pairs owns
      * n + floor((n - 1) / 1000); n pairs that continue the open one at most ceil(n 1001 / 1000) more than it owes) */
     const sdv_audio *t = e->audio;
-    return (size_t)(rs_owned_host(t->rs_seen) - t->rs_emitted) + n_pairs + n_pairs / SDV_RESAMPLE_M + 2;
+    return (size_t)(rs_owned_host(t->rs_seen) - t->rs_emitted) + n_pairs + n_pairs / SDV_RESAMPLE_M + 2 + sk_waiting(t);
+}
+
+/* The resampler's three launches for one call, its result left in d_rs_result (the caller reads it back, or the skew stage does on the device). */
+static int rs_queue(sdv_engine *e, sdv_audio *t, const sdv_sample_pair *pairs, size_t n_pairs, int flush, sdv_sample_pair *out_pairs, size_t out_cap, rt::stream_t s)
+{
+    if (!t->rs_taps_ready) {
+        /* the table, transposed: the 64 lanes of a wave walk neighbouring phases of one tap */
+        std::vector<double> tab((size_t)sdva::RS_TAPS * sdva::RS_PITCH, 0.0);
+        double row[128];
+        for (int p = 0; p < SDV_RESAMPLE_L; p++) { sdv_resample_taps(p, row); for (int k = 0; k < 128; k++) tab[(size_t)k * sdva::RS_PITCH + p] = row[k]; }
+        RT_CHECK(t->d_rs_taps.reserve(tab.size()));
+        RT_CHECK(rt::h2d(t->d_rs_taps, tab.data(), tab.size() * sizeof(double), s));
+        RT_CHECK(rt::ssync(s));
+        t->rs_taps_ready = true;
+    }
+    const size_t n_tiles = (n_pairs + sdva::RS_TILE - 1) / sdva::RS_TILE;
+    RT_CHECK(rt::reserve_all(sdva::RS_HIST, sdva::RS_HIST, t->d_rs_hist, t->d_rs_hist_spare));
+    RT_CHECK(t->d_rs_result.reserve(1));
+    RT_CHECK(t->d_rs_sums.reserve(n_tiles + 1, n_tiles + n_tiles / 8 + 64));
+    RT_CHECK(t->d_rs_starts.reserve(n_tiles + 1, n_tiles + n_tiles / 8 + 64));
+    sdva::RsArgs a; memset(&a, 0, sizeof(a));
+    a.in = pairs; a.out = out_pairs; a.n = (int64_t)n_pairs; a.out_cap = out_cap; a.hist = t->d_rs_hist; a.hist_out = t->d_rs_hist_spare;
+    a.taps = t->d_rs_taps; a.sums = t->d_rs_sums; a.starts = t->d_rs_starts; a.result = t->d_rs_result;
+    a.seen0 = t->rs_seen; a.emitted0 = t->rs_emitted; a.n_tiles = (uint32_t)n_tiles; a.flush = flush ? 1 : 0;
+    RT_LAUNCH64(sdv_k_resample_classify, n_tiles, a, s);
+    RT_LAUNCH64(sdv_k_resample_scan, 1, a, s);
+    RT_LAUNCH64(sdv_k_resample_emit, n_tiles ? n_tiles : 1, a, s);
+    return SDV_OK;
+}
+
+/* sdv_audio_resample with a delay bit: stage A - the copy (the skew stage then reads the caller's pairs where they lie) or the resampler, into a
+ * buffer of the engine - and the skew stage behind it, which takes the resampler's count from device memory.  One read-back, behind both. */
+static int audio_resample_skewed(sdv_engine *e, sdv_audio *t, const sdv_sample_pair *pairs, size_t n_pairs, int flush, sdv_sample_pair *out_pairs, size_t out_cap, size_t *n_out, void *stream)
+{
+    if (n_pairs > 0 && !pairs) { set_error(e, "null sample pair buffer"); return SDV_ERR_NULL_LINES; }
+    if (n_pairs >= 0x7FFF0000u) { set_error(e, "too many sample pairs in one call"); return SDV_ERR_BAD_ARG; }
+    const bool to_44100 = (t->rs_mode & SDV_RESAMPLE_TO_44100) != 0;
+    const size_t room = sdv_audio_resample_room(e, n_pairs), room_a = room - sk_waiting(t);
+    const bool run_a = to_44100 && (n_pairs > 0 || (flush && t->rs_seen > 0));
+    if (!run_a && n_pairs == 0 && !(flush && t->sk_seen > 0)) {
+        /* nothing in and no tail to put out */
+        if (flush || !to_44100) { t->rs_seen = 0; t->rs_emitted = 0; }
+        if (flush) t->sk_seen = 0;
+        return SDV_OK;
+    }
+    if (!out_pairs) { set_error(e, "null output buffer"); return SDV_ERR_NULL_BLOCK; }
+    if (out_cap < room) {
+        set_error(e, "output buffer too small: room for " + std::to_string((unsigned long long)room) + " sample pairs is needed (sdv_audio_resample_room)");
+        return SDV_ERR_BAD_ARG;
+    }
+    if (pairs && (const char *)pairs < (const char *)(out_pairs + out_cap) && (const char *)out_pairs < (const char *)(pairs + n_pairs)) {
+        set_error(e, "the output overlaps the input"); return SDV_ERR_BAD_ARG;
+    }
+    SDV_ON_DEVICE(e);
+    rt::stream_t s = (rt::stream_t)stream;
+    if (!t->sk_taps_ready) {
+        double row[128];
+        sdv_resample_taps(SDV_RESAMPLE_PHASE_HALF, row);
+        RT_CHECK(t->d_sk_taps.reserve(128));
+        RT_CHECK(rt::h2d(t->d_sk_taps, row, sizeof(row), s));
+        RT_CHECK(rt::ssync(s));
+        t->sk_taps_ready = true;
+    }
+    RT_CHECK(rt::reserve_all(sdva::SK_HIST, sdva::SK_HIST, t->d_sk_hist, t->d_sk_hist_spare));
+    RT_CHECK(t->d_sk_result.reserve(1));
+    sdva::SkArgs a; memset(&a, 0, sizeof(a));
+    a.in = pairs; a.n = (int64_t)n_pairs;
+    if (run_a) {
+        RT_CHECK(t->d_sk_mid.reserve(room_a, room_a + room_a / 8 + 4096));
+        const int rc = rs_queue(e, t, pairs, n_pairs, flush, t->d_sk_mid, room_a, s);
+        if (rc != SDV_OK) return rc;
+        a.in = t->d_sk_mid; a.n = (int64_t)room_a; a.a_result = t->d_rs_result;
+    }
+    a.out = out_pairs; a.out_cap = out_cap; a.hist = t->d_sk_hist; a.hist_out = t->d_sk_hist_spare; a.taps = t->d_sk_taps; a.result = t->d_sk_result;
+    a.seen0 = t->sk_seen; a.flush = flush ? 1 : 0; a.channel = (t->rs_mode & SDV_RESAMPLE_DELAY_RIGHT) ? 1 : 0;
+    const size_t n_tiles = ((size_t)a.n + sdva::SK_TILE - 1) / sdva::SK_TILE;
+    RT_LAUNCH64(sdv_k_skew, n_tiles ? n_tiles : 1, a, s);
+    sdva::SkResult res;
+    RT_CHECK(rt::d2h(&res, t->d_sk_result, sizeof(res), s));
+    if (res.n_out > out_cap || (run_a && res.a.n_out > room_a)) { set_error(e, "internal: the resampler counted more outputs than sdv_audio_resample_room allows"); return SDV_ERR_HIP; }
+    if (run_a) { t->d_rs_hist.swap(t->d_rs_hist_spare); t->rs_seen = res.a.seen; t->rs_emitted = res.a.emitted; }
+    else if (flush || !to_44100) { t->rs_seen = 0; t->rs_emitted = 0; }
+    t->d_sk_hist.swap(t->d_sk_hist_spare);
+    t->sk_seen = res.seen;
+    *n_out = (size_t)res.n_out;
+    return SDV_OK;
 }
 
 int sdv_audio_resample(sdv_engine *e, const sdv_sample_pair *pairs, size_t n_pairs, int flush, sdv_sample_pair *out_pairs, size_t out_cap, size_t *n_out, void *stream)
@@ -486,6 +591,7 @@ int sdv_audio_resample(sdv_engine *e, const sdv_sample_pair *pairs, size_t n_pai
     if (!e || !n_out) return SDV_ERR_BAD_ARG;
     *n_out = 0;
     sdv_audio *t = audio_get(e);
+    if (t->rs_mode & RS_DELAY_BITS) return audio_resample_skewed(e, t, pairs, n_pairs, flush, out_pairs, out_cap, n_out, stream);
     if (n_pairs > 0 && !pairs) { set_error(e, "null sample pair buffer"); return SDV_ERR_NULL_LINES; }
     if (n_pairs >= 0x7FFF0000u) { set_error(e, "too many sample pairs in one call"); return SDV_ERR_BAD_ARG; }
     const size_t room = sdv_audio_resample_room(e, n_pairs);
@@ -509,28 +615,8 @@ int sdv_audio_resample(sdv_engine *e, const sdv_sample_pair *pairs, size_t n_pai
         *n_out = n_pairs;
         return SDV_OK;
     }
-    if (!t->rs_taps_ready) {
-        /* the table, transposed: the 64 lanes of a wave walk neighbouring phases of one tap */
-        std::vector<double> tab((size_t)sdva::RS_TAPS * sdva::RS_PITCH, 0.0);
-        double row[128];
-        for (int p = 0; p < SDV_RESAMPLE_L; p++) { sdv_resample_taps(p, row); for (int k = 0; k < 128; k++) tab[(size_t)k * sdva::RS_PITCH + p] = row[k]; }
-        RT_CHECK(t->d_rs_taps.reserve(tab.size()));
-        RT_CHECK(rt::h2d(t->d_rs_taps, tab.data(), tab.size() * sizeof(double), s));
-        RT_CHECK(rt::ssync(s));
-        t->rs_taps_ready = true;
-    }
-    const size_t n_tiles = (n_pairs + sdva::RS_TILE - 1) / sdva::RS_TILE;
-    RT_CHECK(rt::reserve_all(sdva::RS_HIST, sdva::RS_HIST, t->d_rs_hist, t->d_rs_hist_spare));
-    RT_CHECK(t->d_rs_result.reserve(1));
-    RT_CHECK(t->d_rs_sums.reserve(n_tiles + 1, n_tiles + n_tiles / 8 + 64));
-    RT_CHECK(t->d_rs_starts.reserve(n_tiles + 1, n_tiles + n_tiles / 8 + 64));
-    sdva::RsArgs a; memset(&a, 0, sizeof(a));
-    a.in = pairs; a.out = out_pairs; a.n = (int64_t)n_pairs; a.out_cap = out_cap; a.hist = t->d_rs_hist; a.hist_out = t->d_rs_hist_spare;
-    a.taps = t->d_rs_taps; a.sums = t->d_rs_sums; a.starts = t->d_rs_starts; a.result = t->d_rs_result;
-    a.seen0 = t->rs_seen; a.emitted0 = t->rs_emitted; a.n_tiles = (uint32_t)n_tiles; a.flush = flush ? 1 : 0;
-    RT_LAUNCH64(sdv_k_resample_classify, n_tiles, a, s);
-    RT_LAUNCH64(sdv_k_resample_scan, 1, a, s);
-    RT_LAUNCH64(sdv_k_resample_emit, n_tiles ? n_tiles : 1, a, s);
+    const int rc = rs_queue(e, t, pairs, n_pairs, flush, out_pairs, out_cap, s);
+    if (rc != SDV_OK) return rc;
     sdva::RsResult res;
     RT_CHECK(rt::d2h(&res, t->d_rs_result, sizeof(res), s));
     if (res.n_out > out_cap) { set_error(e, "internal: the resampler counted more outputs than sdv_audio_resample_room allows"); return SDV_ERR_HIP; }

@@ -14,7 +14,7 @@ from .abi import (  # noqa: F401  (what this module defined before abi.py: impor
     LINE_DTYPE, STATS_DTYPE, DEINT_LINE_DTYPE, BLOCK_DTYPE, PAIR_DTYPE, AUDIO_PURGE_DTYPE,
     BinPreset, IngestDesc, EncodeDesc, EncodeMarkerlessDesc, DeintSettings, StitchSettings, Pcm1StitchSettings, Pcm16x0StitchSettings, StitchInfo, RunInfo,
     PCM_PCM1, PCM_PCM16X0, PCM_STC007, TYPE_M2, MODE_DRAFT, MODE_FAST, MODE_NORMAL, MODE_INSANE, FLAG_NEW_FILE, FLAG_DOUBLED, FLAG_END_FILE, FRAME_EMPTY,
-    DEEMPH_OFF, DEEMPH_AUTO, DEEMPH_FORCE, RESAMPLE_OFF, RESAMPLE_TO_44100,
+    DEEMPH_OFF, DEEMPH_AUTO, DEEMPH_FORCE, RESAMPLE_OFF, RESAMPLE_TO_44100, RESAMPLE_DELAY_RIGHT, RESAMPLE_DELAY_LEFT, RESAMPLE_PHASE_HALF,
     PIX_GRAY8, PIX_UYVY422, PIX_YUYV422, PIX_V210, PIX_GRAY10LE, PIX_RGB24, PIX_BGR24, PIX_RGB0, PIX_BGR0, PIX_FORMATS, COLOR_BW, COLOR_R, COLOR_G, COLOR_B,
     INGEST_DOUBLE_OFF, INGEST_DOUBLE_ON, INGEST_DOUBLE_AUTO, ENC_NTSC, ENC_PAL, ENC_14BIT, ENC_16BIT, ENC_TFF, ENC_BFF, ENC_CTRL_COPY_PROHIBITED, ENC_CTRL_EMPHASIS,
     ENC_FMT_PCM1, ENC_FMT_PCM16X0_SI, ENC_FMT_PCM16X0_EI, ENC_ML_EMPHASIS, ENC_ML_RATE_44100, ENC_ML_CODE,
@@ -894,7 +894,9 @@ class Engine:
 
     # ---- 44 056 Hz -> 44 100 Hz: beyond the reference, which writes the NTSC rate into the WAV header ---------------------
     def set_resample(self, mode: int):
-        """RESAMPLE_OFF (the default: audio_resample copies) / RESAMPLE_TO_44100."""
+        """RESAMPLE_OFF (the default: audio_resample copies) / RESAMPLE_TO_44100, either with RESAMPLE_DELAY_RIGHT or RESAMPLE_DELAY_LEFT or-ed to it: the
+        skew stage behind it delays that channel by half a sample (the PCM-F1 family samples its channels half a period apart; "left first, so delay
+        the right channel" is the usual case, not a verified one).  A change of the delay while pairs wait in the skew stage is refused: flush or reset first."""
         self._check(self.lib.sdv_set_resample(self._h, int(mode)))
 
     def reset_resample(self):
@@ -907,7 +909,9 @@ class Engine:
     def audio_resample(self, pairs, flush=False, out=None, stream=None):
         """One burst of the stream through the 1001 / 1000 resampler: (n, 12) sdv_sample_pair -> (n_out, 12) on the device; segments of
         44 056 Hz pairs leave at 44 100 Hz, everything else as it came.  Without flush the last 64 pairs of an open segment wait in the
-        engine for the next call.  out: a buffer of at least sdv_audio_resample_room pairs that does not overlap `pairs`."""
+        engine for the next call.  With a delay bit in the mode the skew stage runs behind that (behind the copy, with RESAMPLE_OFF): one pair out per
+        pair in, the delayed channel's word filtered, up to 63 more pairs waiting.  out: a buffer of at least sdv_audio_resample_room pairs that
+        does not overlap `pairs`."""
         import torch
         _check_out(pairs, 12, pairs.device, "pairs")
         n = pairs.shape[0]
@@ -922,7 +926,7 @@ class Engine:
         return out[:n_out.value]
 
     def resample_taps(self, phase: int):
-        """The 128 taps of a phase (0 .. 1000), as a tuple of floats."""
+        """The 128 taps of a phase (0 .. 1000), or of the skew stage's half-sample row (RESAMPLE_PHASE_HALF), as a tuple of floats."""
         c = (C.c_double * 128)()
         self.lib.sdv_resample_taps(int(phase), c)
         return tuple(c)
