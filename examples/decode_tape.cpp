@@ -11,9 +11,10 @@
  *       8-bit luma frames of a PCM-1600/1610/1630 tape -> sdv_pcm16x0_binarize_frames (VideoToDigital with TYPE_PCM16X0) ->
  *       sdv_pcm16x0_stitch_frames (the PCM16X0DataStitcher worker's body); the sub-line records never leave the device
  *
- *   decode_tape wav <luma.raw> <width> <height> <n_frames> <out.wav> [<mask mode 0..6>] [auto|force] [44100] [deskew-r|deskew-l]
+ *   decode_tape wav <luma.raw> <width> <height> <n_frames> <out.wav> [<mask mode 0..6, 8, 9>] [auto|force] [44100] [deskew-r|deskew-l]
  *       the whole chain of the application for an STC-007 file: sdv_binarize_frames -> sdv_stitch_frames -> sdv_audio_process (the
- *       AudioProcessor worker's loop, linear interpolation of dropouts by default) -> sdv_wav_pack + sdv_wav_header: the file SamplesToWAV
+ *       AudioProcessor worker's loop, linear interpolation of dropouts by default; 8 and 9, SDV_DROP_INTER_CUBIC_BLOCK / _WORD, interpolate runs of up to six
+ *       samples cubically, which the reference cannot) -> sdv_wav_pack + sdv_wav_header: with the modes 0..6 the file SamplesToWAV
  *       writes, byte for byte; nothing but the luma goes to the device and nothing but the 16-bit PCM comes back.  With `auto` or `force`
  *       the 50/15 us de-emphasis network (sdv_audio_deemphasis) runs on the file's pairs in front of sdv_wav_pack - `force` is the one for
  *       an STC-007 tape recorded with emphasis, whose pairs never carry the flag `auto` goes by; the reference leaves this to an audio editor.

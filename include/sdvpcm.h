@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define SDV_ABI_VERSION 13  /* 2: output capacities on sdv_binarize_frames / sdv_pcm1_binarize_lines; 3: sdv_audio_process, sdv_wav_pack, sdv_wav_header, sdv_decode_frames (additions only);
+#define SDV_ABI_VERSION 14  /* 2: output capacities on sdv_binarize_frames / sdv_pcm1_binarize_lines; 3: sdv_audio_process, sdv_wav_pack, sdv_wav_header, sdv_decode_frames (additions only);
                              * 4: sdv_pcm16x0_binarize_lines, sdv_audio_stalled, sdv_set_frame_flags, sdv_double_width, sdv_vis_render_lines (additions); the calls that used to refuse PCM-16x0 frames of the wrong size and the
                              * AudioProcessor's dead ends now follow the reference; the PCM-16x0 stitch state blob grew by conv_queue's remainder;
                              * 5: sdv_run_info grew by frames_met (at its end), sdv_binarize_lines (addition);
@@ -34,7 +34,8 @@ extern "C" {
                              * 12: out_fmt in sdv_encode_desc and sdv_encode_markerless_desc, in bytes that were padding (0, SDV_PIX_GRAY8, is what they meant); *row_bytes of
                              * the two geometry calls follows it;
                              * 13: SDV_RESAMPLE_DELAY_RIGHT / _LEFT as bits of sdv_set_resample's mode, SDV_RESAMPLE_PHASE_HALF for sdv_resample_taps (values that were refused
-                             * or gave zeros); sdv_audio_resample_pending and _room count the skew stage in */
+                             * or gave zeros); sdv_audio_resample_pending and _room count the skew stage in;
+                             * 14: SDV_DROP_INTER_CUBIC_BLOCK / _WORD as modes of sdv_set_audio_masking (values that were refused), SDV_AP_CUBIC_MAX_RUN (additions only) */
 
 /* ---- status codes ---------------------------------------------------------------------------
  * 0..4 mirror Binarizer::LB_RET_* (binarizer.h:268-275); 16.. mirror STC007Deinterleaver::DI_RET_*
@@ -929,7 +930,46 @@ typedef struct sdv_audio_purge {
     uint8_t _pad[3];
 } sdv_audio_purge;
 
-/* setMasking(mode).  Like the slot it takes effect with the next window; it does not touch what waits in the window. */
+/* Cubic interpolation of short dropouts (no reference equivalent: the best the reference has is rangeLinearInterpolation).  Two modes beside
+ * AudioProcessor::DROP_*; 7 (SDV_DROP_MAX) stays what setMasking ignores.  Everything about them is that of SDV_DROP_INTER_LIN_BLOCK / _WORD -
+ * SDV_DROP_INTER_CUBIC_BLOCK replaces word validity by block validity exactly as SDV_DROP_INTER_LIN_BLOCK does -: the feed schedule, the
+ * windows, which samples become valid in which scan, the ramps into and out of a mute, forced zeros, the end-of-file ramp, purges, indices, how
+ * many pairs leave, stalls.  The one exception is the value written into a sample of a plain region: a run of invalid samples that has a valid
+ * sample on both sides and gets no ramp (the one region of a short run, see sdv_audio_process).  For such a region, per channel:
+ *   - positions: a and b are the window entries of the valid samples below and above the run;
+ *   - outer neighbours: p = a - 1 and q = b + 1 are the entries just outside them;
+ *   - position within the run: L = b - a, and for the sample at entry i, t = i - a, with 1 <= t <= L - 1;
+ *   - node values: va, vb, vp, vq are the words at those entries;
+ *   - eligibility: the region is cubic when all of the following hold, otherwise the sample gets exactly the value the linear mode gives:
+ *       L - 1 <= SDV_AP_CUBIC_MAX_RUN;
+ *       p >= 0 and q < n, where n is the pairs in the window at this scan;
+ *       entries p and q both carry SDV_SF_WORD_VALID and not SDV_SF_WORD_MASKED in the channel's state before this scan writes anything;
+ *   - value: for a cubic region, in integers, the Lagrange cubic through the nodes -1, 0, L, L + 1 over the common denominator
+ *     D = L (L + 1) (L + 2):
+ *       c_p = - L * t * (L - t) * (L + 1 - t)
+ *       c_a = (L + 2) * (t + 1) * (L - t) * (L + 1 - t)
+ *       c_b = (L + 2) * (t + 1) * t * (L + 1 - t)
+ *       c_q = - L * (t + 1) * t * (L - t)
+ *       N = c_p vp + c_a va + c_b vb + c_q vq
+ *       x = floor((2 N + D) / (2 D))      (floor division, halves go up)
+ *     and x is then clamped to -32768 .. 32767.  c_p + c_a + c_b + c_q = D; a single missing sample (L = 2) gets (-vp + 4 va + 4 vb - vq) / 6.
+ *     For L <= 7 every |c| is below 1848 and |2 N + D| is below 2^31, so 32-bit arithmetic suffices.  Unlike the linear mode there is no
+ *     va == vb shortcut;
+ *   - flags: as for every fill, the sample becomes SDV_SF_WORD_VALID, and where x differs from the word that stood there it becomes
+ *     SDV_SF_WORD_MASKED and counts in *n_masked;
+ *   - unchanged parts: ramp segments and the end-of-file ramp stay linear in these modes, because they run to or from a forced zero.
+ * The result depends on the window a run is scanned in: a run whose `above` is the window's last entry (q = n), or whose outer neighbour was
+ * itself filled (masked), is linear - the same kind of dependence the fixed feed schedule of sdv_audio_process already has.
+ * The cap is 6 because a block is a run of three per channel, two adjacent blocks are six, and beyond that a cubic whose end slopes come from
+ * adjacent samples overshoots: on a 5 kHz tone of unit amplitude at 44 056 Hz a run of 6 errs by 1.76 linearly and 1.44 cubically, a run of 8
+ * by 1.97 and 2.52.  Where it loses to the line: a single-sample cubic is better than linear below fs / 3 (about 14.7 kHz) and worse above it
+ * (on a 997 Hz tone of unit amplitude 6.8e-5 against 1.0e-2).  The modes are opt-in. */
+enum { SDV_DROP_INTER_CUBIC_BLOCK = 8, SDV_DROP_INTER_CUBIC_WORD = 9 };
+#define SDV_AP_CUBIC_MAX_RUN 6
+
+/* setMasking(mode): SDV_DROP_IGNORE .. SDV_DROP_INTER_LIN_WORD (0..6), SDV_DROP_INTER_CUBIC_BLOCK (8), SDV_DROP_INTER_CUBIC_WORD (9); 7, anything
+ * negative and anything above 9: SDV_ERR_BAD_ARG, the mode stays as it was.  Like the slot it takes effect with the next window; it does not
+ * touch what waits in the window. */
 int sdv_set_audio_masking(sdv_engine *e, int drop_mode);
 /* A freshly constructed AudioProcessor (audioprocessor.cpp:3-36): empty window, sample index 0, masking as set. */
 int sdv_reset_audio(sdv_engine *e);

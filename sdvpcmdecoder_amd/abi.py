@@ -221,7 +221,7 @@ ASM_LINE_DTYPE = np.dtype(AsmLineRec)
 
 
 # ---- constants: the header's enums and #defines without the SDV_ prefix ----------------------------------------------------------------
-ABI_VERSION = 13
+ABI_VERSION = 14
 OK, ERR_NULL_VIDEO, ERR_NULL_PCM, ERR_SHORT_LINE, ERR_NO_COORD, ERR_NULL_LINES, ERR_NULL_BLOCK, ERR_NO_DATA = 0, 1, 2, 3, 4, 16, 17, 18
 ERR_BAD_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED = -1, -2, -3, -4
 PCM_PCM1, PCM_PCM16X0, PCM_STC007 = 0, 1, 2
@@ -243,6 +243,7 @@ ENC_FMT_PCM1, ENC_FMT_PCM16X0_SI, ENC_FMT_PCM16X0_EI, ENC_ML_EMPHASIS, ENC_ML_RA
 P1B_SHORT, P1B_EMPHASIS, P1W_CRC_OK, P1W_PICKED_LEFT, P1W_PICKED_WORD, P1S_BW_SET, P1S_CRC_VALID, P1S_SKIP = 1, 2, 1, 2, 4, 1, 2, 128
 P16_FORMAT_AUTO, P16_FORMAT_SI, P16_FORMAT_EI, P16B_EVEN_ORDER, P16B_EI_FORMAT, P16B_EMPHASIS, P16B_CODE = 0, 1, 2, 1, 2, 4, 8
 DROP_IGNORE, DROP_MUTE_BLOCK, DROP_MUTE_WORD, DROP_HOLD_BLOCK, DROP_HOLD_WORD, DROP_INTER_LIN_BLOCK, DROP_INTER_LIN_WORD, DROP_MAX = 0, 1, 2, 3, 4, 5, 6, 7
+DROP_INTER_CUBIC_BLOCK, DROP_INTER_CUBIC_WORD, AP_CUBIC_MAX_RUN = 8, 9, 6
 AP_BUF_SIZE, AP_MIN_VALID_BEFORE, AP_MAX_RAMP_DOWN, AP_MAX_RAMP_UP, AP_PURGE_NEW_FILE, AP_PURGE_END_FILE, AP_PURGE_STOP = 512, 3, 192, 32, 1, 2, 3
 DEEMPH_OFF, DEEMPH_AUTO, DEEMPH_FORCE, DEEMPH_TILE, DEEMPH_WARMUP = 0, 1, 2, 1024, 128
 RESAMPLE_L, RESAMPLE_M, RESAMPLE_HALF, RESAMPLE_OFF, RESAMPLE_TO_44100 = 1001, 1000, 64, 0, 1

@@ -30,7 +30,7 @@ namespace sdva {
 enum { WIN = SDV_AP_BUF_SIZE, KEEP = SDV_AP_MIN_VALID_BEFORE, RAMP_DOWN = SDV_AP_MAX_RAMP_DOWN, RAMP_UP = SDV_AP_MAX_RAMP_UP,
        STRIDE = WIN - KEEP, SCAN_MIN = KEEP + RAMP_DOWN + RAMP_UP, PLAY_MIN = SCAN_MIN + 1, CALC_MULT = 16 };
 enum { END_OPEN = 0, END_NEW_FILE = 1, END_END_FILE = 2 };      /* what ends a stretch: the end of the call, or a tag */
-enum { HOW_MUTE = 0, HOW_HOLD = 1, HOW_LIN = 2 };
+enum { HOW_MUTE = 0, HOW_HOLD = 1, HOW_LIN = 2, HOW_CUBIC = 3 };      /* HOW_CUBIC: window_body<true>, in its plain regions only; fill_value never sees it */
 enum { MAX_TAGS = 65536 };
 enum { RES_STALLED = 1, RES_PLAN_MISMATCH = 2 };
 enum { MIN_ADVANCE = RAMP_DOWN - 1 };      /* a full window that does not stall puts out at least 191 pairs: what bounds the window list */
@@ -205,8 +205,23 @@ __device__ __forceinline__ int16_t fill_value(int how, int i, int a, int b, int 
     return (int16_t)((step * (i - a) + base + CALC_MULT / 2) / CALC_MULT);
 }
 
+/* SDV_DROP_INTER_CUBIC_*: the sample t behind `a` of a plain region with L = b - a <= SDV_AP_CUBIC_MAX_RUN + 1 whose outer neighbours vp (at a - 1) and vq
+ * (at b + 1) qualify - the Lagrange cubic through the nodes -1, 0, L, L + 1 over D = L (L + 1) (L + 2), as include/sdvpcm.h states it.  Every |c| is below
+ * 1848 and |2 N + D| below 2^31 for L <= 7: 32-bit arithmetic throughout. */
+__device__ __forceinline__ int16_t cubic_value(int t, int L, int vp, int va, int vb, int vq)
+{
+    const int32_t u = L - t, w = L + 1 - t, D = L * (L + 1) * (L + 2);
+    const int32_t cp = -L * t * u * w, ca = (L + 2) * (t + 1) * u * w, cb = (L + 2) * (t + 1) * t * w, cq = -L * (t + 1) * t * u;
+    const int32_t num = 2 * (cp * vp + ca * va + cb * vb + cq * vq) + D, den = 2 * D;
+    int32_t x = num / den;
+    if (num % den < 0) x--;             /* floor: halves go up */
+    return (int16_t)(x < -32768 ? -32768 : x > 32767 ? 32767 : x);
+}
+
 /* scanBuffer + fixBadSamples for both channels + the count outputAudio can put out, for the n pairs at w[0..n).
- * Returns the number of pairs that leave from the front; `masked` gets the guiAddMask count. */
+ * Returns the number of pairs that leave from the front; `masked` gets the guiAddMask count.  CUBIC: HOW_CUBIC, a build of its own - the other modes run
+ * the code they ran before there was one. */
+template <bool CUBIC>
 __device__ inline uint32_t window_body(sdv_sample_pair *w, int n, bool file_end, int how, WinLds &lds, uint32_t &masked, int lane)
 {
     uint32_t d0[8], d1[8];
@@ -218,6 +233,7 @@ __device__ inline uint32_t window_body(sdv_sample_pair *w, int n, bool file_end,
     }
     __syncthreads();
     uint32_t changed = 0;
+    const int how_reg = CUBIC ? (int)HOW_LIN : how;      /* ramps, and plain regions that are not cubic: as the linear mode */
     for (int ch = 0; ch < 2; ch++) {
         uint64_t vm[8];
         for (int j = 0; j < 8; j++) vm[j] = __ballot(lane + 64 * j < n && (lds.flg[ch][lane + 64 * j] & SDV_SF_WORD_VALID));
@@ -233,7 +249,7 @@ __device__ inline uint32_t window_body(sdv_sample_pair *w, int n, bool file_end,
                 const uint64_t lo = vm[j] & ((1ull << lane) - 1ull), hi = lane == 63 ? 0ull : (vm[j] & (~0ull << (lane + 1)));
                 const int below = lo ? 64 * j + 63 - __clzll((unsigned long long)lo) : top[j];      /* good_end */
                 const int above = hi ? 64 * j + __ffsll((unsigned long long)hi) - 1 : bot[j];       /* good_at_the_end */
-                int a = -1, b = -1, va = 0, vb = 0; bool point = false;
+                int a = -1, b = -1, va = 0, vb = 0; bool point = false, plain = false;
                 if (below >= 0) {
                     const int vbelow = lds.val[ch][below];
                     if (above < 0) {
@@ -256,12 +272,19 @@ __device__ inline uint32_t window_body(sdv_sample_pair *w, int n, bool file_end,
                             if (i < up) { a = below; b = up; va = vbelow; vb = 0; }
                             else if (i == up) point = true;
                             else { a = up; b = above; va = 0; vb = vabove; }
-                        } else { a = below; b = above; va = vbelow; vb = vabove; }
+                        } else { a = below; b = above; va = vbelow; vb = vabove; plain = true; }
                     }
                 }
                 if (point) { v = 0; f |= SDV_SF_WORD_VALID | SDV_SF_WORD_MASKED; }         /* sampleMute (:495-508) */
                 else if (a >= 0) {
-                    const int16_t x = fill_value(how, i, a, b, va, vb);
+                    bool cubic = false; int vp = 0, vq = 0;
+                    if (CUBIC && plain && b - a - 1 <= SDV_AP_CUBIC_MAX_RUN && a >= 1 && b + 1 < n) {
+                        /* the outer neighbours as they stood before this scan (what the scan writes waits in nv / nf until the barrier) */
+                        const uint8_t fp = lds.flg[ch][a - 1], fq = lds.flg[ch][b + 1];
+                        cubic = (fp & (SDV_SF_WORD_VALID | SDV_SF_WORD_MASKED)) == SDV_SF_WORD_VALID && (fq & (SDV_SF_WORD_VALID | SDV_SF_WORD_MASKED)) == SDV_SF_WORD_VALID;
+                        vp = lds.val[ch][a - 1]; vq = lds.val[ch][b + 1];
+                    }
+                    const int16_t x = cubic ? cubic_value(i - a, b - a, vp, va, vb, vq) : fill_value(how_reg, i, a, b, va, vb);
                     if (x != v) { v = x; f |= SDV_SF_WORD_MASKED; changed++; }
                     f |= SDV_SF_WORD_VALID;
                 }
@@ -611,6 +634,7 @@ __device__ inline void plan_body(const PlanArgs &a, uint32_t s, PlanLds &lds, in
 
 /* ---- the sample work of the listed windows ---------------------------------------------------------------------------- */
 struct ExecArgs { const Stretch *st; uint32_t n_st; sdv_sample_pair *w; const WinRec *wins; const uint32_t *win_base; StretchResult *res; uint32_t n_slots; uint8_t how; };
+template <bool CUBIC>
 __device__ inline void exec_body(const ExecArgs &a, uint32_t slot, WinLds &lds, int lane)
 {
     if (slot >= a.n_slots) return;
@@ -623,7 +647,7 @@ __device__ inline void exec_body(const ExecArgs &a, uint32_t slot, WinLds &lds, 
     for (;;) {
         const WinRec rec = a.wins[a.win_base[s] + k];
         uint32_t mk = 0;
-        const uint32_t pops = window_body(a.w + rec.w_pos, (int)rec.n, rec.file_end != 0, a.how, lds, mk, lane);
+        const uint32_t pops = window_body<CUBIC>(a.w + rec.w_pos, (int)rec.n, rec.file_end != 0, a.how, lds, mk, lane);
         masked += mk;
         if (lane == 0 && pops != rec.pops) atomicOr(&a.res[s].flags, (uint32_t)RES_PLAN_MISMATCH);
         k++;
@@ -684,7 +708,12 @@ __global__ void __launch_bounds__(64) sdv_k_ap_plan(sdva::PlanArgs a)
 __global__ void __launch_bounds__(64) sdv_k_ap_windows(sdva::ExecArgs a)
 {
     __shared__ sdva::WinLds lds;
-    sdva::exec_body(a, blockIdx.x, lds, (int)threadIdx.x);
+    sdva::exec_body<false>(a, blockIdx.x, lds, (int)threadIdx.x);
+}
+__global__ void __launch_bounds__(64) sdv_k_ap_windows_cubic(sdva::ExecArgs a)       /* a.how == HOW_CUBIC */
+{
+    __shared__ sdva::WinLds lds;
+    sdva::exec_body<true>(a, blockIdx.x, lds, (int)threadIdx.x);
 }
 __global__ void __launch_bounds__(64) sdv_k_ap_emit(sdva::EmitArgs a) { sdva::emit_body(a, blockIdx.x, (int)threadIdx.x); }
 __global__ void __launch_bounds__(64) sdv_k_wav_pack(sdva::WavArgs a) { sdva::wav_body(a, (size_t)blockIdx.x * 64u + threadIdx.x); }

@@ -67,7 +67,8 @@ extern "C" {
 int sdv_set_audio_masking(sdv_engine *e, int drop_mode)
 {
     if (!e) return SDV_ERR_BAD_ARG;
-    if (drop_mode < 0 || drop_mode >= SDV_DROP_MAX) { set_error(e, "no such masking mode"); return SDV_ERR_BAD_ARG; }     /* setMasking ignores it (:1534) */
+    const bool cubic = drop_mode == SDV_DROP_INTER_CUBIC_BLOCK || drop_mode == SDV_DROP_INTER_CUBIC_WORD;      /* (no reference equivalent) */
+    if ((drop_mode < 0 || drop_mode >= SDV_DROP_MAX) && !cubic) { set_error(e, "no such masking mode"); return SDV_ERR_BAD_ARG; }     /* setMasking ignores it (:1534) */
     audio_get(e)->mask_mode = drop_mode;
     return SDV_OK;
 }
@@ -187,7 +188,7 @@ static int audio_process_span(sdv_engine *e, sdv_audio *t, const sdv_sample_pair
         sdva::PrepArgs pa; pa.pairs = pairs; pa.carry = t->d_carry; pa.st = t->d_st; pa.n_st = (uint32_t)n_st; pa.total_w = total_w; pa.w = work;
         pa.bad1 = t->d_bad1; pa.bad2 = t->d_bad2; pa.bad3 = t->d_bad3; pa.ignore = ignore ? 1 : 0;
         pa.v0 = t->d_v0; pa.v1 = t->d_v1; pa.m0 = t->d_m0; pa.m1 = t->d_m1; pa.has_mi = t->d_count + 1;
-        pa.by_block = (mode == SDV_DROP_MUTE_BLOCK || mode == SDV_DROP_HOLD_BLOCK || mode == SDV_DROP_INTER_LIN_BLOCK) ? 1 : 0;
+        pa.by_block = (mode == SDV_DROP_MUTE_BLOCK || mode == SDV_DROP_HOLD_BLOCK || mode == SDV_DROP_INTER_LIN_BLOCK || mode == SDV_DROP_INTER_CUBIC_BLOCK) ? 1 : 0;
         RT_LAUNCH64(sdv_k_ap_prepare, ((size_t)total_w + 255) / 256, pa, s);
         sdva::SummArgs sm; sm.bad2 = t->d_bad2; sm.n_blocks = (uint32_t)n2; sm.bad3 = t->d_bad3;
         RT_LAUNCH64(sdv_k_ap_summary, n3, sm, s);
@@ -223,8 +224,9 @@ static int audio_process_span(sdv_engine *e, sdv_audio *t, const sdv_sample_pair
         if (listed > 0) {
             sdva::ExecArgs xa; xa.st = t->d_st; xa.n_st = (uint32_t)n_st; xa.w = work; xa.wins = t->d_wins; xa.win_base = t->d_win_base; xa.res = t->d_res;
             xa.n_slots = n_st == 1 ? res[0].n_win : (uint32_t)n_slots;
-            xa.how = (mode == SDV_DROP_MUTE_BLOCK || mode == SDV_DROP_MUTE_WORD) ? sdva::HOW_MUTE : (mode == SDV_DROP_HOLD_BLOCK || mode == SDV_DROP_HOLD_WORD) ? sdva::HOW_HOLD : sdva::HOW_LIN;
-            RT_LAUNCH64(sdv_k_ap_windows, xa.n_slots, xa, s);
+            xa.how = (mode == SDV_DROP_MUTE_BLOCK || mode == SDV_DROP_MUTE_WORD) ? sdva::HOW_MUTE : (mode == SDV_DROP_HOLD_BLOCK || mode == SDV_DROP_HOLD_WORD) ? sdva::HOW_HOLD :
+                     (mode == SDV_DROP_INTER_CUBIC_BLOCK || mode == SDV_DROP_INTER_CUBIC_WORD) ? sdva::HOW_CUBIC : sdva::HOW_LIN;
+            if (xa.how == sdva::HOW_CUBIC) RT_LAUNCH64(sdv_k_ap_windows_cubic, xa.n_slots, xa, s); else RT_LAUNCH64(sdv_k_ap_windows, xa.n_slots, xa, s);
             RT_CHECK(rt::d2h(res.data(), t->d_res, n_st * sizeof(sdva::StretchResult), s));
             for (size_t k = 0; k < n_st; k++) {
                 masked += res[k].masked;

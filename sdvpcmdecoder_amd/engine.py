@@ -798,7 +798,8 @@ class Engine:
 
     # ---- AudioProcessor / SamplesToWAV -----------------------------------------------------------
     def set_audio_masking(self, drop_mode: int):
-        """AudioProcessor::setMasking (audioprocessor.cpp:1532-1574): SDV_DROP_* 0..6."""
+        """AudioProcessor::setMasking (audioprocessor.cpp:1532-1574): SDV_DROP_* 0..6, and the two modes the reference does not have,
+        abi.DROP_INTER_CUBIC_BLOCK (8) and abi.DROP_INTER_CUBIC_WORD (9): cubic interpolation of runs of up to abi.AP_CUBIC_MAX_RUN samples."""
         self._check(self.lib.sdv_set_audio_masking(self._h, int(drop_mode)))
 
     def reset_audio(self):
