@@ -27,16 +27,16 @@ KERNEL_SOURCES = {
     "sdv_k_pcm1_prescan": ("stc007_device.h", "pcm1_bin_device.h", "markerless_frames_device.h", "pcm1_frames_device.h", "markerless_chain_device.h", "markerless_frames_engine.inc", "pcm1_frames_engine.inc"),
     "sdv_k_pcm16_frames_lean": ("stc007_device.h", "pcm1_bin_device.h", "pcm16_bin_device.h", "markerless_frames_device.h", "pcm16_frames_device.h", "markerless_chain_device.h", "markerless_frames_engine.inc", "pcm16_frames_engine.inc"),
     "sdv_k_pcm16_prescan": ("stc007_device.h", "pcm1_bin_device.h", "pcm16_bin_device.h", "markerless_frames_device.h", "pcm16_frames_device.h", "markerless_chain_device.h", "markerless_frames_engine.inc", "pcm16_frames_engine.inc"),
-    "sdv_k_ap_": ("audio_device.h", "audio_engine.inc"),
-    "sdv_k_deemph": ("audio_device.h", "audio_deemph_device.h", "audio_engine.inc"),
-    "sdv_k_resample": ("audio_device.h", "audio_resample_device.h", "audio_engine.inc"),
-    "sdv_k_skew": ("audio_device.h", "audio_resample_device.h", "audio_skew_device.h", "audio_engine.inc"),
+    "sdv_k_ap_": ("audio_device.h", "stage_common.inc", "audio_engine.inc"),
+    "sdv_k_deemph": ("audio_device.h", "audio_deemph_device.h", "stage_common.inc", "audio_deemph_engine.inc"),
+    "sdv_k_resample": ("audio_device.h", "audio_resample_device.h", "stage_common.inc", "audio_resample_engine.inc"),
+    "sdv_k_skew": ("audio_device.h", "audio_resample_device.h", "audio_skew_device.h", "stage_common.inc", "audio_resample_engine.inc"),
     "sdv_k_ingest": ("ingest_device.h", "ingest_engine.inc"),
     "sdv_k_encode": ("encode_device.h", "encode_engine.inc"),
     "sdv_k_encode_raster_packed": ("encode_device.h", "encode_packed_device.h", "encode_engine.inc"),
     "sdv_k_mlenc": ("encode_device.h", "encode_markerless_device.h", "encode_engine.inc", "encode_markerless_engine.inc"),
-    "sdv_k_preemph": ("pcm_preemph_device.h", "pcm_condition_engine.inc"),
-    "sdv_k_pcmrs": ("pcm_preemph_device.h", "pcm_resample_device.h", "pcm_condition_engine.inc"),
+    "sdv_k_preemph": ("pcm_preemph_device.h", "stage_common.inc", "pcm_condition_engine.inc"),
+    "sdv_k_pcmrs": ("pcm_preemph_device.h", "pcm_resample_device.h", "stage_common.inc", "pcm_condition_engine.inc"),
     "sdv_k_pcm16_frames_bin": ("stc007_device.h", "pcm1_bin_device.h", "pcm16_bin_device.h", "markerless_frames_device.h", "pcm16_frames_device.h", "markerless_chain_device.h", "markerless_frames_engine.inc", "pcm16_frames_engine.inc"),
 }
 

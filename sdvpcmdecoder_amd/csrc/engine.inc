@@ -167,7 +167,7 @@ static inline rt::status_t launch_predict(const sdv::PredictArgs &a, rt::stream_
 struct sdv_stitcher;                /* stitch stage state, stitch_engine.inc */
 struct sdv_pcm1_stitcher;           /* PCM-1 back half, pcm1_engine.inc */
 struct sdv_pcm16_stitcher;          /* PCM-16x0 back half, pcm16_engine.inc */
-struct sdv_audio;                   /* AudioProcessor, audio_engine.inc */
+struct sdv_audio;                   /* AudioProcessor and the stages behind it (audio_engine.inc ...), decode_frames_engine.inc */
 struct sdv_vis;                     /* visualiser canvases, vis_engine.inc */
 struct sdv_encoder;                 /* the tape sdv_encode_frames writes, encode_engine.inc */
 struct sdv_pcm_cond;                /* pre-emphasis and 44 100 -> 44 056 Hz ahead of the encoders, pcm_condition_engine.inc */
@@ -599,4 +599,5 @@ int sdv_deinterleave_blocks(sdv_engine *e, const sdv_deint_line *lines, size_t n
 #include "ingest_engine.inc"         /* sdv_ingest_geometry, sdv_ingest_frames */
 #include "encode_engine.inc"         /* sdv_encode_geometry, sdv_encode_frames, sdv_reset_encoder */
 #include "encode_markerless_engine.inc"  /* sdv_encode_markerless_geometry, sdv_encode_markerless_frames */
+#include "stage_common.inc"          /* what the sample-stream stages share: pcm_condition_engine.inc, audio_engine.inc and the stage files behind it */
 #include "pcm_condition_engine.inc"  /* sdv_pcm_preemphasis, sdv_pcm_resample */

@@ -3,12 +3,16 @@
 The emulator build can be told to fail its n-th next allocation once (sdv_emu_fail_alloc, tests/emu/emu_engine.cpp).  For every allocation a large
 call makes on a fresh engine - counted in a clean run, not written down here - that call is made to fail there: it returns SDV_ERR_HIP, and a
 smaller call on the same engine then succeeds with the bytes of the oracle and of a fresh engine.  A buffer whose capacity outlived its memory, or a
-group of buffers grown by half, would hand the smaller call a NULL or a too small buffer."""
+group of buffers grown by half, would hand the smaller call a NULL or a too small buffer.
+
+The sample-stream stages promise more (include/sdvpcm.h): a failed call leaves the stream where it was.  test_failed_allocation_keeps_the_stream makes
+every allocation of every call of a stream fail once and repeats that call on the same engine, without a reset: the stream's bytes are the clean run's."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import audio_api as A
 import engine_api as ea
 import kernel_path_tapes as kt
 import libs
@@ -17,6 +21,7 @@ import pcm16_api as p16
 import stitch_api as sa
 import stitch_cases as sc
 from oracle_run import oracle_binarize
+from sdvpcmdecoder_amd import abi
 from sdvpcmdecoder_amd.abi import ERR_HIP as SDV_ERR_HIP
 
 FAR = 1 << 30
@@ -101,3 +106,106 @@ def test_failed_allocation_leaves_engine_usable(case, emu_lib, oracle_lib):
         assert rc == 0, f"after a failure at allocation {k} of {n_allocs}: {emu_lib.sdv_last_error(eng)}"
         assert got == want, f"after a failure at allocation {k} of {n_allocs} the smaller call differs from the oracle"
         emu_lib.sdv_engine_destroy(eng)
+
+
+# ---- the sample-stream stages: the stream survives a failed call ----------------------------------------------------------------------------------
+STREAM_CUTS = (0, 300, 9000)            # a stream of 9000 pairs in two calls; the second one ends it (stop / flush) where the call has such an argument
+
+
+def _audio_process_stream(lib):
+    # dropouts for the linear mode to work on, and an END_FILE / NEW_FILE pair in the second call: three stretches, and the purge drops a pair, so
+    # the output does not lie where the work array has it (the staged path)
+    pairs = A.tape([A.audio(4000, 41, runs=((100, 3, 0), (2000, 5, 2)), p_bad=0.01), "E", "N", A.audio(4998, 42, runs=((4000, 4, 1),), p_bad=0.01)])
+
+    def setup(eng):
+        assert lib.sdv_set_audio_masking(eng, abi.DROP_INTER_LIN_WORD) == 0
+
+    def call(eng, a, b, last):
+        rc, out, pur, masked, _, _ = A.emu_audio(lib, eng, pairs[a:b], 1 if last else 0)
+        return rc, out.tobytes() + pur.tobytes() + masked.to_bytes(8, "little")
+    return setup, call
+
+
+def _deemphasis_stream(lib):
+    pairs = A.audio(9000, 43, emphasis=1)
+
+    def setup(eng):
+        assert lib.sdv_set_deemphasis(eng, abi.DEEMPH_FORCE) == 0
+
+    def call(eng, a, b, last):
+        src, out = np.ascontiguousarray(pairs[a:b]), np.zeros(b - a, dtype=A.PAIR_DTYPE)
+        return lib.sdv_audio_deemphasis(eng, src.ctypes.data, b - a, out.ctypes.data, None), out.tobytes()
+    return setup, call
+
+
+def _resample_stream(mode):
+    def case(lib):
+        pairs = A.audio(9000, 44)
+
+        def setup(eng):
+            assert lib.sdv_set_resample(eng, mode) == 0
+
+        def call(eng, a, b, last):
+            cap = lib.sdv_audio_resample_room(eng, b - a)
+            src, out, n_out = np.ascontiguousarray(pairs[a:b]), np.zeros(cap + 1, dtype=A.PAIR_DTYPE), C.c_size_t(0)
+            rc = lib.sdv_audio_resample(eng, src.ctypes.data, b - a, 1 if last else 0, out.ctypes.data, cap, C.byref(n_out), None)
+            return rc, out[:n_out.value].tobytes()
+        return setup, call
+    return case
+
+
+def _pcm_stream(resample):
+    def case(lib):
+        pcm = np.random.default_rng(45).integers(-20000, 20001, (9000, 2)).astype(np.int16)
+
+        def call(eng, a, b, last):
+            src = np.ascontiguousarray(pcm[a:b])
+            if not resample:
+                out = np.zeros((b - a, 2), dtype=np.int16)
+                return lib.sdv_pcm_preemphasis(eng, src.ctypes.data, b - a, 44100, out.ctypes.data, None), out.tobytes()
+            cap = lib.sdv_pcm_resample_room(eng, b - a)
+            out, n_out = np.zeros((cap + 1, 2), dtype=np.int16), C.c_size_t(0)
+            rc = lib.sdv_pcm_resample(eng, src.ctypes.data, b - a, 1 if last else 0, out.ctypes.data, cap, C.byref(n_out), None)
+            return rc, out[:n_out.value].tobytes()
+        return (lambda eng: None), call
+    return case
+
+
+STREAM_CASES = {"audio_process": _audio_process_stream, "audio_deemphasis": _deemphasis_stream, "audio_resample_mode1": _resample_stream(1),
+                "audio_resample_mode4": _resample_stream(4), "audio_resample_mode5": _resample_stream(5),
+                "pcm_preemphasis": _pcm_stream(False), "pcm_resample": _pcm_stream(True)}
+
+
+@pytest.mark.parametrize("name", list(STREAM_CASES))
+def test_failed_allocation_keeps_the_stream(name, emu_lib):
+    setup, call = STREAM_CASES[name](emu_lib)
+    spans = list(zip(STREAM_CUTS[:-1], STREAM_CUTS[1:]))
+
+    def stream(fail_call=None, nth=0):
+        """The stream on a fresh engine -> (its bytes, the allocations of every call); with `fail_call`: allocation `nth` of that call fails, the call is
+        made again."""
+        eng = emu_lib.sdv_engine_create(0)
+        setup(eng)
+        got, allocs = [], []
+        for i, (a, b) in enumerate(spans):
+            last = i == len(spans) - 1
+            if i == fail_call:
+                emu_lib.sdv_emu_fail_alloc(nth)
+                rc, _ = call(eng, a, b, last)
+                left = emu_lib.sdv_emu_fail_alloc(0)
+                assert left == 0, f"call {i}: allocation {nth} was never asked for"
+                assert rc == SDV_ERR_HIP, f"call {i}: allocation {nth} failed and the call returned {rc}"
+            emu_lib.sdv_emu_fail_alloc(FAR)
+            rc, out = call(eng, a, b, last)
+            allocs.append(FAR - emu_lib.sdv_emu_fail_alloc(0))
+            assert rc == 0, f"call {i}{' repeated after a failure at allocation %d' % nth if i == fail_call else ''}: {emu_lib.sdv_last_error(eng)}"
+            got.append(out)
+        emu_lib.sdv_engine_destroy(eng)
+        return b"".join(got), allocs
+
+    want, allocs = stream()
+    assert allocs[0] >= 1, "the first call allocates nothing?"
+    for i, n_allocs in enumerate(allocs):
+        for k in range(1, n_allocs + 1):
+            got, _ = stream(i, k)
+            assert got == want, f"after a failure at allocation {k} of {n_allocs} in call {i} the stream differs from the clean run"

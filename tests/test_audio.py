@@ -453,7 +453,7 @@ def test_gpu_long_tape_properties(oracle_lib):
 @pytest.mark.gpu
 def test_gpu_follows_the_reference_into_its_dead_ends(gpu, oracle_lib):
     """The one refusal that is no small buffer - a tag that is neither NEW_FILE nor END_FILE - is the host's, from the tag list read back ahead of
-    every kernel that writes (audio_engine.inc:98-122; the work array is made at :155-184)."""
+    every kernel that writes (`audio_process_span`, step 1; the work array is made in step 2)."""
     _follows_the_reference_into_its_dead_ends(gpu, dc.DEVICE, oracle_lib)
 
 
@@ -465,7 +465,7 @@ def test_gpu_edge_inputs(gpu, oracle_lib):
 @pytest.mark.gpu
 def test_gpu_in_place_and_staged_paths_agree(gpu, oracle_lib):
     """The second call of every burst states exactly the room the refused one reported (out_cap = its n_out): less than the work array needs wherever
-    something stays behind in the window (audio_engine.inc:155), so the pairs go through the engine's buffer and the emit pass."""
+    something stays behind in the window (`audio_process_span`, step 2: the work array), so the pairs go through the engine's buffer and the emit pass."""
     _in_place_and_staged_paths_agree(gpu, dc.DEVICE, oracle_lib)
 
 
@@ -476,7 +476,7 @@ def test_gpu_next_index_runs_on_across_calls(gpu, oracle_lib):
 
 @pytest.mark.gpu
 def test_gpu_call_in_place(gpu, oracle_lib):
-    """out_pairs == pairs, literally: the overlap branch of audio_engine.inc:156-157, among the waves of a real launch."""
+    """out_pairs == pairs, literally: the overlap test of `audio_process_span`, among the waves of a real launch."""
     _call_in_place(gpu, dc.DEVICE, oracle_lib)
 
 

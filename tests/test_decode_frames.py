@@ -585,6 +585,6 @@ def test_gpu_stitch_and_fused_calls_interleaved_with_the_visualiser_feeds_toggle
 
 @pytest.mark.gpu
 def test_gpu_fused_refuses_bad_arguments():
-    """The three refusals are the host's, ahead of any device work: the PCM type and the audio arguments at audio_engine.inc:556-557, the null video
-    in the frame entry the fused one calls first (check_frame_call, engine.inc:424, ahead of its first launch; on a new engine nothing is armed for it, stitch_engine.inc:274)."""
+    """The three refusals are the host's, ahead of any device work: the PCM type and the audio arguments at the head of `sdv_decode_frames`, the null video
+    in the frame entry the fused one calls first (`check_frame_call`, ahead of its first launch; on a new engine nothing is armed for it, `stitch_prepare_direct`)."""
     _fused_refuses_bad_arguments(dc.product_lib(), dc.DEVICE)

@@ -227,6 +227,6 @@ def test_gpu_full_size_batch_decodes_to_what_was_rendered():
 # ---- the GPU twin of the emulator's refusals: the same body through tests/device_calls.py -------------------------------------------------------------
 @pytest.mark.gpu
 def test_gpu_bad_arguments():
-    """Every one of these refusals is the host's, ahead of any device work: check_frame_call, engine.inc:424-435, called at
-    markerless_frames_engine.inc:35 (null video, short line, the record count against the capacity that is stated)."""
+    """Every one of these refusals is the host's, ahead of any device work: `check_frame_call` (engine.inc), called at the head of
+    `markerless_binarize_frames` (null video, short line, the record count against the capacity that is stated)."""
     _bad_arguments(dc.product_lib(), dc.DEVICE)

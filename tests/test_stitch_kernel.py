@@ -480,6 +480,6 @@ def test_gpu_empty_and_tiny_inputs(gpu, oracle_lib):
 @pytest.mark.gpu
 def test_gpu_rejects_what_it_cannot_reproduce(gpu, oracle_lib):
     """Both refusals come before anything is written to the caller's buffers: on a cold engine the call is not pipelined, the stranger is found in the
-    analysis' briefs read back ahead of the first turn (stitch_engine.inc:476-482), and the small buffer at the host's sum of the turns' counts ahead of
-    the packing kernel (stitch_engine.inc:646; no direct writes without a steady stream, :514)."""
+    analysis' briefs read back ahead of the first turn (`stitch_frames_impl`), and the small buffer at the host's sum of the turns' counts ahead of
+    the packing kernel (no direct writes without a steady stream: `try_direct`)."""
     _rejects_what_it_cannot_reproduce(gpu, dc.DEVICE)
