@@ -379,7 +379,10 @@ PROTOTYPES = {
 # exported by developer and emulator builds only
 DEV_PROTOTYPES = {
     "sdv_dev_launch_counts": (I, [VP, VP, SZ]),
+    "sdv_dev_poisoned": (I, [P(U64), P(U64)]),
+    "sdv_dev_peek_fresh": (I, [I, SZ, VP]),
     "sdv_emu_fail_alloc": (I, [I]),
+    "sdv_emu_poison_alloc": (I, [I]),
     "sdv_emu_selftest_bursts": (I, [U64, I]),
 }
 

@@ -10,6 +10,7 @@
  *   rt::launch_waves / RT_LAUNCH64     wave kernels: a workgroup is k waves of 64 lanes working together, a workgroup per unit of work
  *   RT_LAUNCH_ITEMS / RT_LAUNCH_ROWS   thread-per-item kernels: item i is body(args, i); the product launches the __global__ wrapper around the body
  */
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -23,9 +24,36 @@ typedef hipError_t status_t;
 static const status_t OK = hipSuccess;
 static const bool CONCURRENT = true;            /* streams run beside each other: work may be queued on side streams (SideStreams) */
 static inline const char *err_str(status_t e) { return hipGetErrorString(e); }
+#ifndef SDV_DEV_AIDS
 static inline status_t dmalloc(void **p, size_t n) { return hipMalloc(p, n); }
-static inline status_t dfree(void *p) { return hipFree(p); }
 static inline status_t hpin(void **p, size_t n) { return hipHostMalloc(p, n, hipHostMallocDefault); }      /* page-locked host memory: copies into it are asynchronous */
+#else
+/* Developer builds (tests): with SDV_POISON_ALLOC=<byte> in the environment every new allocation is filled with that byte before it is handed out, so
+ * that what a kernel reads before anything wrote it is not the zero a young process usually finds there (tests/test_memory_history.py).  Unset:
+ * nothing is filled.  sdv_dev_poisoned counts what was filled since the library was loaded. */
+static std::atomic<uint64_t> poisoned_allocs{ 0 }, poisoned_bytes{ 0 };
+static inline int poison_byte() { const char *v = getenv("SDV_POISON_ALLOC"); return v && *v ? (int)(strtol(v, NULL, 0) & 0xFF) : -1; }
+static inline void poisoned(size_t n) { poisoned_allocs++; poisoned_bytes += n; }
+static inline status_t dmalloc(void **p, size_t n)
+{
+    status_t st = hipMalloc(p, n);
+    const int b = poison_byte();
+    if (st != OK || b < 0 || n == 0) return st;
+    st = hipMemset(*p, b, n);
+    if (st == OK) st = hipDeviceSynchronize();          /* (the fill is there before any stream of the engine touches the memory) */
+    if (st != OK) { (void)hipFree(*p); *p = NULL; return st; }
+    poisoned(n);
+    return OK;
+}
+static inline status_t hpin(void **p, size_t n)
+{
+    const status_t st = hipHostMalloc(p, n, hipHostMallocDefault);
+    const int b = poison_byte();
+    if (st == OK && b >= 0 && n > 0) { memset(*p, b, n); poisoned(n); }
+    return st;
+}
+#endif
+static inline status_t dfree(void *p) { return hipFree(p); }
 static inline status_t hunpin(void *p) { return hipHostFree(p); }
 static inline status_t ssync(stream_t s) { return hipStreamSynchronize(s); }
 static inline status_t h2d(void *d, const void *h, size_t n, stream_t s) { return hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, s); }
@@ -166,7 +194,15 @@ static const bool CONCURRENT = false;           /* everything runs where it is q
 static inline const char *err_str(status_t) { return "the emulated runtime refused"; }
 /* (tests: the fail_alloc_in-th allocation from now fails, once - sdv_emu_fail_alloc, tests/emu/emu_engine.cpp) */
 static int fail_alloc_in = 0;
-static inline status_t emu_alloc(void **p, size_t n) { if (fail_alloc_in > 0 && --fail_alloc_in == 0) { *p = NULL; return 1; } *p = malloc(n ? n : 1); return *p ? 0 : 1; }
+/* (tests: every allocation that succeeds is filled with this byte; negative: left as malloc gives it - sdv_emu_poison_alloc, tests/emu/emu_engine.cpp) */
+static int poison_alloc = -1;
+static inline status_t emu_alloc(void **p, size_t n)
+{
+    if (fail_alloc_in > 0 && --fail_alloc_in == 0) { *p = NULL; return 1; }
+    *p = malloc(n ? n : 1);
+    if (*p && poison_alloc >= 0) memset(*p, poison_alloc, n ? n : 1);
+    return *p ? 0 : 1;
+}
 static inline status_t dmalloc(void **p, size_t n) { return emu_alloc(p, n); }
 static inline status_t dfree(void *p) { free(p); return OK; }
 static inline status_t hpin(void **p, size_t n) { return emu_alloc(p, n); }
@@ -265,3 +301,26 @@ template <typename T> using PinBuf = Buf<T, PinMem>;
 /* buffers that grow by one rule, in one statement: the first failure ends it */
 template <typename... B> static inline status_t reserve_all(size_t n, size_t alloc_n, B &...b) { status_t st = OK; (void)(((st = b.reserve(n, alloc_n)) == OK) && ...); return st; }
 } // namespace rt
+
+#if defined(SDV_DEV_AIDS) && !defined(SDV_EMU)
+/* Developer builds of the HIP library (tests): what SDV_POISON_ALLOC has filled since the library was loaded ... */
+extern "C" int sdv_dev_poisoned(uint64_t *allocations, uint64_t *bytes)
+{
+    if (allocations) *allocations = rt::poisoned_allocs.load();
+    if (bytes) *bytes = rt::poisoned_bytes.load();
+    return rt::poison_byte();           /* the byte in force, -1: none */
+}
+/* ... and what a fresh allocation of `bytes` bytes holds, device (pinned 0) or page-locked (pinned 1), through the calls the engines' buffers make: the
+ * proof that the fill lands in both kinds of memory.  0, or the runtime's error. */
+extern "C" int sdv_dev_peek_fresh(int pinned, size_t bytes, uint8_t *out)
+{
+    if (!out || bytes == 0) return -1;
+    void *p = NULL;
+    rt::status_t st = pinned ? rt::hpin(&p, bytes) : rt::dmalloc(&p, bytes);
+    if (st != rt::OK) return (int)st;
+    if (pinned) memcpy(out, p, bytes);
+    else st = hipMemcpy(out, p, bytes, hipMemcpyDeviceToHost);
+    (void)(pinned ? rt::hunpin(p) : rt::dfree(p));
+    return (int)st;
+}
+#endif

@@ -28,10 +28,16 @@ PATTERN = 0xA5
 
 # ---- memory -----------------------------------------------------------------------------------------------------------------------------
 class Host:
-    """numpy arrays: what the emulator build reads and writes."""
+    """numpy arrays: what the emulator build reads and writes.  dirty: an output buffer starts as PATTERN bytes, not as zeros - a call has to write
+    every byte of every record it counts (tests/test_memory_history.py)."""
     name = "host"
 
+    def __init__(self, dirty=False):
+        self.dirty = dirty
+
     def zeros(self, n, dtype, full=None):
+        if self.dirty:
+            return np.full(int(n) * np.dtype(dtype).itemsize, PATTERN, dtype=np.uint8).view(dtype)
         return np.zeros(n, dtype=dtype)
 
     def array(self, a):
@@ -51,9 +57,9 @@ class Host:
 
 
 class DevBuf:
-    """`n` records of `dtype` on the device, zeroed, with the guard behind them."""
+    """`n` records of `dtype` on the device, zeroed (dirty: left as PATTERN bytes, like the guard), with the guard behind them."""
 
-    def __init__(self, n, dtype, full=None, data=None, device="cuda:0"):
+    def __init__(self, n, dtype, full=None, data=None, device="cuda:0", dirty=False):
         import torch
         self.dtype, self.n = np.dtype(dtype), int(n)
         self.total = max(self.n, int(full or 0)) + GUARD
@@ -61,7 +67,7 @@ class DevBuf:
         self.t = torch.full((self.total * size,), PATTERN, dtype=torch.uint8, device=device)
         if data is not None:
             self.t[:self.n * size] = torch.from_numpy(np.ascontiguousarray(data).view(np.uint8).reshape(-1).copy()).to(device)
-        else:
+        elif not dirty:
             self.t[:self.n * size] = 0
 
     def __len__(self):
@@ -82,11 +88,14 @@ class DevBuf:
 
 
 class Device:
-    """torch device buffers with guards: what the product library reads and writes."""
+    """torch device buffers with guards: what the product library reads and writes.  dirty: as Host's."""
     name = "device"
 
+    def __init__(self, dirty=False):
+        self.dirty = dirty
+
     def zeros(self, n, dtype, full=None):
-        return DevBuf(n, dtype, full)
+        return DevBuf(n, dtype, full, dirty=self.dirty)
 
     def array(self, a):
         a = np.ascontiguousarray(a)

@@ -34,6 +34,10 @@ struct uint2 { uint32_t x, y; };
  * that a test can count the allocations of a call: arm with a large nth, make the call, ask what is left. */
 extern "C" int sdv_emu_fail_alloc(int nth) { const int left = rt::fail_alloc_in; rt::fail_alloc_in = nth > 0 ? nth : 0; return left; }
 
+/* Test hook: every allocation from now is filled with `byte` (0..255) before it is handed out; negative: off (memory as malloc gives it).  Returns the
+ * previous setting, so that a test restores it and can see that its own setting was still in force. */
+extern "C" int sdv_emu_poison_alloc(int byte) { const int prev = rt::poison_alloc; rt::poison_alloc = byte < 0 ? -1 : (byte & 0xFF); return prev; }
+
 /* ---- test hooks (emulator build only) -------------------------------------------------------------------------------------------- */
 /* bursts_word (64 blocks per call, mask arithmetic) against bursts_block (one block per call) on random flag sequences: returns the number of
  * sequences on which the two disagree.  Flags per block are independent bits with the given densities (per mille), in runs of random length so

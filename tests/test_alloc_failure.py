@@ -112,10 +112,27 @@ def test_failed_allocation_leaves_engine_usable(case, emu_lib, oracle_lib):
 STREAM_CUTS = (0, 300, 9000)            # a stream of 9000 pairs in two calls; the second one ends it (stop / flush) where the call has such an argument
 
 
-def _audio_process_stream(lib):
+# the streams of the cases below, 9000 pairs each (tests/memory_history.py runs the same ones)
+def audio_process_tape():
     # dropouts for the linear mode to work on, and an END_FILE / NEW_FILE pair in the second call: three stretches, and the purge drops a pair, so
     # the output does not lie where the work array has it (the staged path)
-    pairs = A.tape([A.audio(4000, 41, runs=((100, 3, 0), (2000, 5, 2)), p_bad=0.01), "E", "N", A.audio(4998, 42, runs=((4000, 4, 1),), p_bad=0.01)])
+    return A.tape([A.audio(4000, 41, runs=((100, 3, 0), (2000, 5, 2)), p_bad=0.01), "E", "N", A.audio(4998, 42, runs=((4000, 4, 1),), p_bad=0.01)])
+
+
+def deemphasis_tape():
+    return A.audio(9000, 43, emphasis=1)
+
+
+def resample_tape():
+    return A.audio(9000, 44)
+
+
+def pcm_tape():
+    return np.random.default_rng(45).integers(-20000, 20001, (9000, 2)).astype(np.int16)
+
+
+def _audio_process_stream(lib):
+    pairs = audio_process_tape()
 
     def setup(eng):
         assert lib.sdv_set_audio_masking(eng, abi.DROP_INTER_LIN_WORD) == 0
@@ -127,7 +144,7 @@ def _audio_process_stream(lib):
 
 
 def _deemphasis_stream(lib):
-    pairs = A.audio(9000, 43, emphasis=1)
+    pairs = deemphasis_tape()
 
     def setup(eng):
         assert lib.sdv_set_deemphasis(eng, abi.DEEMPH_FORCE) == 0
@@ -140,7 +157,7 @@ def _deemphasis_stream(lib):
 
 def _resample_stream(mode):
     def case(lib):
-        pairs = A.audio(9000, 44)
+        pairs = resample_tape()
 
         def setup(eng):
             assert lib.sdv_set_resample(eng, mode) == 0
@@ -156,7 +173,7 @@ def _resample_stream(mode):
 
 def _pcm_stream(resample):
     def case(lib):
-        pcm = np.random.default_rng(45).integers(-20000, 20001, (9000, 2)).astype(np.int16)
+        pcm = pcm_tape()
 
         def call(eng, a, b, last):
             src = np.ascontiguousarray(pcm[a:b])

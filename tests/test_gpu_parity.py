@@ -154,6 +154,66 @@ def test_hip_full_size_properties(torch_cuda):
     assert (body[:, 243]["service_type"] == 4).all() and (body[:, 487]["service_type"] == 4).all() and (body[:, 488]["service_type"] == 5).all()
 
 
+def test_gpu_end_of_file_frame_and_next_source(torch_cuda):
+    """test_emu_end_of_file_frame_and_next_source on the GPU, the same tapes: SDV_FLAG_END_FILE appends the filler frame + END_FILE, and a second source
+    decoded by the same engine behind it starts like the oracle's."""
+    import ctypes as C
+    import libs
+    from sdvpcmdecoder_amd import Engine
+    luma, _, _ = synth.stc007_frames(n_frames=3, seed=21, height=48, noise_sigma=3.0)
+    luma2, _, _ = synth.stc007_frames(n_frames=2, seed=22, height=48, x0=20, x1=690)
+    lib = libs.load_oracle()
+    lib.orc_v2d_new.restype = C.c_void_p
+    h = C.c_void_p(lib.orc_v2d_new())
+    lib.orc_v2d_set_mode.argtypes = [C.c_void_p, C.c_int]
+    lib.orc_v2d_set_mode(h, 2)
+    want1, ws1 = oracle_binarize(luma, handle=h, new_file=True, end_file=True)
+    want2, ws2 = oracle_binarize(luma2, handle=h, new_file=True, first_frame_no=1)
+    eng = Engine(0)
+    eng.setBinarizationMode(2)
+    got1, gs1, _ = gpu_run(torch_cuda, luma, 2, new_file=True, end_file=True, eng=eng)
+    got2, gs2, _ = gpu_run(torch_cuda, luma2, 2, new_file=True, eng=eng)
+    eng.close()
+    assert len(got1) == 3 * 51 + 1 + 52 and (got1["service_type"][-52:] != 0).all()
+    assert got1.tobytes() == want1.tobytes(), golden_cases.diff_report(got1, want1)
+    assert gs1.tobytes() == ws1.tobytes()
+    assert got2.tobytes() == want2.tobytes(), golden_cases.diff_report(got2, want2)
+    assert gs2.tobytes() == ws2.tobytes()
+
+
+def test_gpu_batch_path_corner_cases(torch_cuda):
+    """test_emu_batch_path_corner_cases on the GPU, the same tapes: duplicated rows (the dup-line rule), silent audio (almost-silent lines are exempt
+    from it), a bad row in the middle of a batch, a doubled-width source, the dup check switched off."""
+    from sdvpcmdecoder_amd import Engine
+    luma, _, _ = synth.stc007_frames(3, seed=5, height=80)
+    luma = luma.copy()
+    luma[1, 20] = luma[1, 18]            # same field: line copies the previous one
+    luma[1, 41] = luma[1, 39]
+    luma[2, 30] = 20                     # dropout inside a batch
+    for kw in (dict(mode=2), dict(mode=1, check_line_dup=False)):
+        want, want_stats = oracle_binarize(luma, **kw)
+        eng = Engine(0)
+        eng.setBinarizationMode(kw["mode"])
+        eng.setCheckLineDup(bool(kw.get("check_line_dup", True)))
+        got, got_stats, _ = gpu_run(torch_cuda, luma, kw["mode"], eng=eng)
+        eng.close()
+        assert got.tobytes() == want.tobytes(), golden_cases.diff_report(got, want)
+        assert got_stats.tobytes() == want_stats.tobytes()
+    luma, _, _ = synth.stc007_frames(2, seed=6, height=60, silent=True)
+    want, want_stats = oracle_binarize(luma, mode=2)
+    got, got_stats, _ = gpu_run(torch_cuda, luma, 2)
+    assert got.tobytes() == want.tobytes(), golden_cases.diff_report(got, want)
+    luma, _, _ = synth.stc007_frames(2, seed=7, height=40, width=1440, x0=24, x1=1416)
+    want, want_stats = oracle_binarize(luma, mode=1, doubled=True, m2=True)
+    eng = Engine(0)
+    eng.setPCMType(3)           # TYPE_M2
+    eng.setBinarizationMode(1)
+    got, got_stats, _ = gpu_run(torch_cuda, luma, 1, eng=eng, doubled=True)
+    eng.close()
+    assert got.tobytes() == want.tobytes(), golden_cases.diff_report(got, want)
+    assert got_stats.tobytes() == want_stats.tobytes()
+
+
 @pytest.mark.parametrize("width,height,pad,shift", [(720, 487, 0, 0), (721, 120, 0, 0), (712, 120, 8, 0), (720, 120, 13, 0), (720, 120, 0, 5),
                                                      (736, 122, 16, 16)])
 def test_hip_ragged_geometry(torch_cuda, width, height, pad, shift):

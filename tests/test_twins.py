@@ -7,7 +7,8 @@ LDS limits or code generation.  So for every `test_emu_<x>` of tests/test_*.py o
   (b) COVERED_BY names the GPU test that covers it, as "module::name" - that test exists and carries the `gpu` mark;
   (c) COVERED_BY says "emulator only: <reason>".
 
-NOT_YET_TWINNED is the open rest, from tests/test_emu_parity.py (the STC-007 front half) only: what has no GPU counterpart yet."""
+NOT_YET_TWINNED was the open rest, from tests/test_emu_parity.py (the STC-007 front half): it is empty and stays empty - a new emulator test comes with
+its twin, or with its reason."""
 import ast
 import glob
 import os
@@ -18,6 +19,8 @@ _KP = "test_gpu_kernel_paths::test_gpu_tape_equals_the_sequential_oracle"      #
 COVERED_BY = {
     # ---- the STC-007 front half: tests/test_emu_parity.py against test_gpu_parity.py (test_hip_*) and test_gpu_kernel_paths.py, read side by side
     "test_emu_parity::test_emu_small_frames": "test_gpu_parity::test_hip_vs_oracle_degraded",                       # the four modes against the oracle
+    "test_emu_parity::test_emu_end_of_file_frame_and_next_source": "test_gpu_parity::test_gpu_end_of_file_frame_and_next_source",      # the same tapes
+    "test_emu_parity::test_emu_batch_path_corner_cases": "test_gpu_parity::test_gpu_batch_path_corner_cases",                          # the same tapes
     "test_emu_parity::test_emu_ragged_geometry": "test_gpu_parity::test_hip_ragged_geometry",
     "test_emu_parity::test_emu_golden_rough_draft": "test_gpu_parity::test_hip_matches_reference_golden",          # every case of golden_cases.CASES
     "test_emu_parity::test_emu_speculation_rounds": "test_gpu_parity::test_hip_stream_continuation_and_rounds",
@@ -100,12 +103,7 @@ COVERED_BY = {
         "emulator only: the checks of sdv_pcm16x0_binarize_lines are the host's, ahead of its launch (check_lines_call, markerless_frames_engine.inc:27-40); the rows nothing is preset for "
         "that follow them are an input like those of test_gpu_lines_match_oracle",
 }
-NOT_YET_TWINNED = [
-    # the second source on the same engine behind an END_FILE call: the GPU tests with END_FILE end there, or reset the stream in between
-    "test_emu_parity::test_emu_end_of_file_frame_and_next_source",
-    # duplicated rows (the dup-line rule), silent audio and a dropout inside a line batch at small sizes: on the GPU only as part of the golden cases
-    "test_emu_parity::test_emu_batch_path_corner_cases",
-]
+NOT_YET_TWINNED = []
 
 
 def _marks(node, module_marks):
@@ -190,6 +188,7 @@ def test_every_emulator_test_has_a_gpu_twin():
     print("test_emu_* by kind: %s" % {k: sum(1 for v in kinds.values() if v == k) for k in ("a", "b", "c", "open")})
     print("NOT_YET_TWINNED:\n  " + "\n  ".join(NOT_YET_TWINNED))
     assert not bad, "\n" + "\n".join(bad)
+    assert NOT_YET_TWINNED == [] and "open" not in kinds.values(), "every emulator test has its GPU twin or its reason: the list stays empty"
 
 
 def test_the_guard_sees_what_it_should():
