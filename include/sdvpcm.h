@@ -539,6 +539,11 @@ size_t sdv_binarize_records(int height, int n_frames, unsigned flags);
  *  out_stats    device pointer to stats_cap rows, one FrameBinDescriptor per frame (signal guiUpdFrameBin); one more row with
  *               SDV_FLAG_END_FILE (the worker reports the filler frame too).
  *  frame_stride at least (height-1)*row_stride + width when n_frames > 1 (frames do not overlap), else SDV_ERR_BAD_ARG.
+ *  Strides.     row_stride and frame_stride are size_t and are taken as such: any stride that satisfies the lower bounds (row_stride >= width, frame_stride
+ *               as above) is accepted, rows and frames may lie gigabytes apart, and the records do not depend on the strides - only on the pixels.  This
+ *               one rule holds for the three frame entries (sdv_binarize_frames, sdv_pcm1_binarize_frames, sdv_pcm16x0_binarize_frames), for
+ *               sdv_decode_frames and for the per-line entries.  (The whole-frame captures of the lean kernels form offsets inside a frame in 32 bits and
+ *               are taken only where row_stride * height < 2^31; beyond that the same lines are read one by one at 64-bit addresses.)
  *  stream       hipStream_t (NULL = default stream).  All device work goes to it.  The call returns when the outputs are
  *               complete: behind the read-back of the last round, which validates the batch (it synchronises `stream` in every round).
  * Returns SDV_OK or an SDV_ERR_* code; invalid input is refused up front like the reference's early

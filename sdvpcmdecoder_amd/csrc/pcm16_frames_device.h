@@ -325,7 +325,7 @@ __device__ inline int batch16(V2D16 &w, const FrameArgs16 &a16, Lds16 &lds, cons
     {
         constexpr int D = SDV_P16_CAPTURE_D;
         static_assert(BATCH16_LINES % D == 0, "whole groups of D lines make a run of up to BATCH16_LINES");
-        const uint32_t rs2 = 2u * (uint32_t)a.row_stride;
+        const uint32_t rs2 = 2u * (uint32_t)a.row_stride;        /* offsets inside a frame fit 32 bits (frame_body16 checks) */
         const uint8_t *row0 = frame + (size_t)(2 * idx + field) * a.row_stride;
         const uint32_t x0 = n.x0, x1 = n.x1, x2 = n.x2, xc = n.x_ctrl;
         uint8_t q[D][4];
@@ -464,6 +464,9 @@ __device__ inline void frame_body16(const FrameArgs16 &a16, Lds16 &lds, int f)
         for (int k = 0; k < COORD_CHECK_LINES; k++) { pre_row[k] = frame_buf_row(a, f, (k + 1) * gap); pre_done[k] = uni(a16.prescan[((size_t)((w.pre_variant >> k) & 1) * a.n_total + f) * COORD_CHECK_LINES + k].pad[0]) != 0; }
     }
     const int n_field[2] = { (a.height + 1) / 2, a.height / 2 };
+    /* batch16 forms its offsets inside the frame in 32 bits: taken only where they fit, the rule of the STC-007 capture (stc007_device.h); rows
+     * farther apart are staged line by line, at 64-bit addresses */
+    const bool near_rows = (uint64_t)a.row_stride * (uint64_t)a.height < (1ull << 31);
     uint16_t line_num = 0;
     Lean16 lean; lean_reset(lean);
     const bool empty_frame = frame_is_empty(a, f);
@@ -485,7 +488,7 @@ __device__ inline void frame_body16(const FrameArgs16 &a16, Lds16 &lds, int f)
                 BinCtx cb0;
                 ctx_for_line(a, cb0, v.bin);
                 P16_T(t_g);
-                if (lean16_prepare(lean, cb0, v.bin)) {
+                if (near_rows && lean16_prepare(lean, cb0, v.bin)) {
                     const int took = batch16(w, a16, lds, lean, frame, field, idx, nl, frame_no, rec, fv_keys, wl);
                     P16_T(t_h); P16_ADD(1, t_g, t_h);
                     if (took > 0) { rec += 3 * took; idx += took - 1; continue; }

@@ -276,7 +276,7 @@ __device__ inline int batch1(V2D1 &w, const FrameArgs &a, WaveLds &lds, const Le
          * fetched again by whatever takes that line. */
         constexpr int D = SDV_P1_CAPTURE_D;
         static_assert(64 % D == 0, "whole groups of D lines make a run of up to 64");
-        const uint32_t rs2 = 2u * (uint32_t)a.row_stride;
+        const uint32_t rs2 = 2u * (uint32_t)a.row_stride;        /* offsets inside a frame fit 32 bits (frame_body1 checks) */
         const uint8_t *row0 = frame + (size_t)(2 * idx + field) * a.row_stride;
         const uint32_t x0 = n.x0, x1 = n.x1, lo = n.low, hi = n.high;
         const bool second = lane + 64 < P1_BITS;
@@ -394,6 +394,9 @@ __device__ inline void frame_body1(const FrameArgs1 &a1, P1Lds &lds, int f)
     const bool empty_frame = frame_is_empty(a, f);
     Lean1 lean; lean_reset(lean);
     const int n_field[2] = { (a.height + 1) / 2, a.height / 2 };
+    /* batch1 forms its offsets inside the frame in 32 bits: taken only where they fit, the rule of the STC-007 capture (stc007_device.h); rows
+     * farther apart are staged line by line, at 64-bit addresses */
+    const bool near_rows = (uint64_t)a.row_stride * (uint64_t)a.height < (1ull << 31);
     uint16_t line_num = 0;
     if (f == a.new_file_frame) { v2d1_service_line(w, a, wl, SDV_SRV_NEW_FILE); emit_rec(wl, frame_no, 0, false, rec++); }
     for (int field = 0; field < 2; field++) {
@@ -416,7 +419,7 @@ __device__ inline void frame_body1(const FrameArgs1 &a1, P1Lds &lds, int f)
             BinCtx c;
             ctx_for_line(a, c, v.bin);
 #if SDV_P1_BATCH
-            if (lean1_prepare(lean, c, v.bin)) {
+            if (near_rows && lean1_prepare(lean, c, v.bin)) {
                 const int took = batch1(w, a, lds.w, lean, frame, field, idx, nl, frame_no, rec, fv_keys, wl);
                 if (took > 0) { rec += took; idx += took - 1; continue; }
             }
